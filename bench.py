@@ -17,11 +17,16 @@ Workload (BASELINE.json metric / north_star): [[1922,50]] hypergraph-product cod
 factor, max_iter = n = 1922, osd_cs order 7, iid bit-flip noise p = 0.05.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the fields).  Its top-level fields are the headline
-configuration.  Without --config (and N = 1) the line also carries, under "configs", a short run of every other
-BASELINE.json configuration that fits one GPU -- configs[1] h1922_ms_osd0, configs[2] h1922_ps_cs60 (as the reference
-computes it) and h1922_ps_cs60_clip20, configs[4] l29k_ms_e15 -- and the headline at B = 2^20 on the one GPU (configs[3]'s
-whole batch): value, ms_per_step, kernel times, the BINDING roofline of the dominant kernel, the cross-kernel check.
---config NAME runs that one configuration alone with its full CPU legs (the numbers of record under profiles/).
+configuration.  A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the line (metric,
+value, unit, ms_per_step, the workload, the kernel times of the timed steps).  --dump-outputs DIR also writes what the last
+timed step computed (DIR/<name>.npy, float32; the inputs are seeded, so two builds compare output for output).
+
+--full adds everything else: the CPU baseline legs, the verification decode of batch 0 (logical error rates, isolated kernel
+times, the BINDING roofline of the dominant kernel, every correction against its syndrome), the cross-kernel check, the
+host-to-host leg and -- without --config (and N = 1) -- under "configs", a short run of every other BASELINE.json
+configuration that fits one GPU: configs[1] h1922_ms_osd0, configs[2] h1922_ps_cs60 (as the reference computes it) and
+h1922_ps_cs60_clip20, configs[4] l29k_ms_e15, and the headline at B = 2^20 on the one GPU (configs[3]'s whole batch).
+--config NAME --full runs that one configuration alone with its full CPU legs (the numbers of record under profiles/).
 """
 from __future__ import annotations
 
@@ -80,6 +85,12 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md)
 CLOCK_HZ = 2.4e9        # peak shader clock (MI355X_MICROARCH.md, chip-level parameters)
 LDS_READ_B64_BYTES_PER_CLK = 256.0        # ds_read_b64, per CU (MI355X_MICROARCH.md, LDS table)
 LDS_WRITE_B64_BYTES_PER_CLK = 512.0 / 6   # ds_write_b64: 6 cycles per wave-instruction of 512 bytes
+# --dump-outputs: the rows of osdw / osd0 / bp written (a seeded sample, the same for every run of the same arguments) and the
+# bytes they may take; converged / iters are written for every row while that fits the whole dump into 64 MiB
+DUMP_SEED = 20240601
+DUMP_MAX_ROWS = 2048
+DUMP_ROW_BUDGET = 48 << 20
+DUMP_TOTAL_BUDGET = 64 << 20
 
 _BATCH_CACHE = {}  # (code key, q, seed) -> (err, syn): a prefix of a larger batch of the same stream IS the smaller batch
 
@@ -152,12 +163,14 @@ def prepare(a, rank, world):
     cpu_one, cpu_per_proc = CPU_SAMPLE.get(a.config, CPU_SAMPLE_DEFAULT)
     if a.cpu_sample >= 0:
         cpu_one = a.cpu_sample
-    # logical operators: the reference's generic route for H1922, the closed-form product basis for the large code
+    # logical operators (--full: the logical error rates): the reference's generic route for H1922, the closed-form product
+    # basis for the large code
+    lz_wanted = rank == 0 and a.full
     if ref400:
         seed = np.loadtxt(os.path.join(ROOT, "tests", "golden", ref_seed[0]), dtype=int).astype(np.uint8)
-        code = hgp(seed, compute_logicals=(rank == 0))
+        code = hgp(seed, compute_logicals=lz_wanted)
     else:
-        code = l29k(compute_logicals="closed_form" if rank == 0 else False) if large else h1922(compute_logicals=(rank == 0))
+        code = l29k(compute_logicals="closed_form" if lz_wanted else False) if large else h1922(compute_logicals=lz_wanted)
     H = code.hz
     kw = dict(error_rate=q, max_iter=max_iter, bp_method=bp_method, ms_scaling_factor=ms,
               osd_method=osd_method, osd_order=osd_order, ps_clip=ps_clip)
@@ -171,8 +184,8 @@ def prepare(a, rank, world):
     ckey = "l29k" if large else (a.config[:6] if ref400 else "h1922")
     P["batches"] = [make_batch(H, q, B, seed=1000 * rank + k, cache_key=ckey) for k in range(P["nbatch"])]
 
-    # ---- CPU baseline legs (rank 0, N = 1 only), before the GPU is initialised in this process.
-    if rank == 0 and world == 1 and cpu_one > 0:
+    # ---- CPU baseline legs (--full, rank 0, N = 1 only), before the GPU is initialised in this process.
+    if a.full and rank == 0 and world == 1 and cpu_one > 0:
         ns = min(cpu_one, B)
         sample = np.ascontiguousarray(P["batches"][0][1][:ns])
         import threading
@@ -373,6 +386,84 @@ def measure(P, rank, local_rank, world):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
+    if rank == 0 and a.dump_outputs and a.warmup + a.steps > 0:
+        # what the last timed step handed its caller (this rank's shard), before anything below decodes into the same buffers
+        k_last = a.warmup + a.steps - 1
+        o = outs[k_last % nslots]
+        nrows = max(1, min(DUMP_MAX_ROWS, B, DUMP_ROW_BUDGET // (3 * 4 * n)))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=nrows, replace=False))
+        idx = torch.from_numpy(rows).to(dev)
+        if native_gather:  # the kernels wrote bit-packed rows: bit j of a row is bit j % 64 of its word j // 64
+            unpack = lambda w: np.unpackbits(w.index_select(0, idx).cpu().numpy().view(np.uint8), axis=1, bitorder="little")[:, :n]
+            dump = dict(osdw=unpack(d_packed[k_last % nbuf]), osd0=unpack(pouts[k_last % nslots]["osd0"]),
+                        bp=unpack(pouts[k_last % nslots]["bp"]))
+        else:
+            dump = {k: o[k].index_select(0, idx).cpu().numpy() for k in ("osdw", "osd0", "bp")}
+        every_row = 3 * 4 * nrows * n + 2 * 4 * B <= DUMP_TOTAL_BUDGET
+        dump["converged"] = (o["conv"] if every_row else o["conv"].index_select(0, idx)).cpu().numpy()
+        dump["iters"] = (o["iters"] if every_row else o["iters"].index_select(0, idx)).cpu().numpy()
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        del idx, dump
+
+    steps = max(a.steps, 1)
+    value = world * B * steps / elapsed
+    code_label = ("[[29524,484]] HGP of a seeded (5,6)-regular 110x132 matrix, hz 14520x29524, " if large else
+                  f"{ref_seed[1]} HGP of {ref_seed[0][:-4]} (the reference's example codes), hz {ref_seed[2]}, " if ref400 else
+                  "[[1922,50]] HGP (31x31 circulant 1+x^2+x^5) hz 961x1922, ")
+    head = {
+        "metric": "syndromes decoded/sec (whole node), large HGP 14520x29524 (BASELINE configs[4])" if large else
+                  f"syndromes decoded/sec (whole node) + logical error rate, HGP {ref_seed[1]} p=0.05 (reference example)" if ref400 else
+                  "syndromes decoded/sec (whole node) + logical error rate, HGP [[1922,50]] p=0.05",
+        "value": value,
+        "unit": "syndromes/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * elapsed / steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{a.config}: " + code_label +
+                        f"{'min-sum' if bp_method == 'ms' else 'product-sum'} BP"
+                        f"{' variable scaling' if bp_method == 'ms' and ms == 0 else (f' scaling {ms}' if bp_method == 'ms' else '')}"
+                        f"{f' (ps_clip {ps_clip})' if bp_method == 'ps' and ps_clip else (' (no clipping, as the reference)' if bp_method == 'ps' else '')}, "
+                        f"max_iter={max_iter or n}, {osd_method} order {osd_order}, iid bit-flip q={q}",
+            "per_gpu_batch": B,
+            "global_batch": B * world,
+            "sharding": f"independent syndromes, contiguous shards x{world}" +
+                        ("" if not do_gather else ", RCCL gather of bit-packed corrections to rank 0" +
+                         (" (rows packed by the decode kernels themselves)" if native_gather else " (bposd_pack_rows_device)") +
+                         f", {nbuf} packed buffers for {nslots} steps in flight"),
+            "bp_variant": a.variant,
+            "pipelined_steps": nslots,
+            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+            "timed_outputs": ["osdw", "osd0", "bp", "converged", "iters"],
+            "batches": f"{nbatch} distinct seeded batches alternate over the timed steps" +
+                       ("; the logical error rates, the CPU comparison and the isolated kernel times are on batch 0" if a.full else "") +
+                       ("" if batches is not None else "; drawn on the device (torch generator, seeds 1000 * rank + k), not numpy's PCG64"),
+        },
+    }
+    if not a.full:
+        # the headline figure alone: no verification decode, no checks, no other legs (all of them: --full)
+        if rank != 0:
+            return None
+        out = dict(head, kernel_ms={"bp": float(np.mean(bp_ms)) if bp_ms else float("nan"),
+                                    "osd": float(np.mean(osd_ms)) if osd_ms else 0.0},
+                   osd_invocations_per_step=osd_tot / steps)
+        if per_rank is not None:
+            out["per_rank"] = per_rank
+        if gather_ms is not None:
+            out["gather_ms"] = gather_ms
+            out["gather"] = {"backend": ("gloo" if a.rehearse_on_one_gpu else "nccl (RCCL)"), "world_size": world,
+                             "native_packed_rows": native_gather, "packed_buffers": nbuf,
+                             "launches_that_waited_for_a_gather": pipe.launch_waited_for_gather}
+        return out
+
     # ---- one more decode of batch 0 for verification / LER (outside the timed region, nothing else on the GPU: these are
     # the "isolated" kernel durations)
     o = outs[0]
@@ -510,8 +601,6 @@ def measure(P, rank, local_rank, world):
 
     if rank != 0:
         return None
-    steps = max(a.steps, 1)
-    value = world * B * steps / elapsed
     # algorithmic bytes of the dominant kernel (BP): SURVEY.md §8(d)
     bytes_per_iter = (4 * E + 2 * n) * 8
     large_note = "algorithmic fp64 message bytes (4E+2n)*8 per executed iteration; "
@@ -576,9 +665,6 @@ def measure(P, rank, local_rank, world):
     # which BP kernel ran (asked of the library), and what it moves through LDS per syndrome-iteration
     kinfo = dec.bp_kernel_info()
     local_edge = kinfo["kernel"] == "bp_local_kernel"
-    code_label = ("[[29524,484]] HGP of a seeded (5,6)-regular 110x132 matrix, hz 14520x29524, " if large else
-                  f"{ref_seed[1]} HGP of {ref_seed[0][:-4]} (the reference's example codes), hz {ref_seed[2]}, " if ref400 else
-                  "[[1922,50]] HGP (31x31 circulant 1+x^2+x^5) hz 961x1922, ")
     num_cu = torch.cuda.get_device_properties(dev).multi_processor_count
     math_form = None
     if bp_method == "ps":
@@ -597,40 +683,7 @@ def measure(P, rank, local_rank, world):
                  "never leave LDS / registers, so this fraction exceeds 1 and is NOT a utilisation"),
     }
     out = {
-        "metric": "syndromes decoded/sec (whole node), large HGP 14520x29524 (BASELINE configs[4])" if large else
-                  f"syndromes decoded/sec (whole node) + logical error rate, HGP {ref_seed[1]} p=0.05 (reference example)" if ref400 else
-                  "syndromes decoded/sec (whole node) + logical error rate, HGP [[1922,50]] p=0.05",
-        "value": value,
-        "unit": "syndromes/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": 1e3 * elapsed / steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{a.config}: " + code_label +
-                        f"{'min-sum' if bp_method == 'ms' else 'product-sum'} BP"
-                        f"{' variable scaling' if bp_method == 'ms' and ms == 0 else (f' scaling {ms}' if bp_method == 'ms' else '')}"
-                        f"{f' (ps_clip {ps_clip})' if bp_method == 'ps' and ps_clip else (' (no clipping, as the reference)' if bp_method == 'ps' else '')}, "
-                        f"max_iter={max_iter or n}, {osd_method} order {osd_order}, iid bit-flip q={q}",
-            "per_gpu_batch": B,
-            "global_batch": B * world,
-            "sharding": f"independent syndromes, contiguous shards x{world}" +
-                        ("" if not do_gather else ", RCCL gather of bit-packed corrections to rank 0" +
-                         (" (rows packed by the decode kernels themselves)" if native_gather else " (bposd_pack_rows_device)") +
-                         f", {nbuf} packed buffers for {nslots} steps in flight"),
-            "bp_variant": a.variant,
-            "pipelined_steps": nslots,
-            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-            "timed_outputs": ["osdw", "osd0", "bp", "converged", "iters"],
-            "batches": (f"{nbatch} distinct seeded batches alternate over the timed steps; the logical error rates, the CPU "
-                        "comparison and the isolated kernel times are on batch 0") +
-                       ("" if batches is not None else "; drawn on the device (torch generator, seeds 1000 * rank + k), not numpy's PCG64"),
-        },
+        **head,
         "logical_error_rate": ler,
         "logical_error_rate_eb": None if ler is None else float(np.sqrt(ler * (1 - ler) / B)),
         "osd0_logical_error_rate": ler0,
@@ -895,23 +948,31 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="run this configuration alone (default: h1922_ms_cs7, plus a short run of every other BASELINE configuration "
-                         "under \"configs\" when N = 1)")
-    ap.add_argument("--no-extras", action="store_true", help="default run without the other configurations")
-    ap.add_argument("--extra-steps", type=int, default=4, help="timed steps of each extra configuration of the default run")
+                         "under \"configs\" when N = 1 and --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the CPU baseline legs, the verification decode (logical error "
+                         "rates, isolated kernel times, rooflines, syndrome check), the cross-kernel check, the host-to-host leg "
+                         "and, without --config, the other configurations under \"configs\"")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): osdw, "
+                         "osd0, bp on a fixed sample of rows (seed %d, at most %d rows), converged and iters on every row" %
+                         (DUMP_SEED, DUMP_MAX_ROWS))
+    ap.add_argument("--no-extras", action="store_true", help="--full run without the other configurations")
+    ap.add_argument("--extra-steps", type=int, default=4, help="timed steps of each extra configuration of the --full run")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
     ap.add_argument("--p", type=float, default=0.05, help="bit-flip probability q")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="syndromes timed on one CPU thread (0 = skip both CPU legs; default 8192, 1 for the large code)")
+                    help="--full: syndromes timed on one CPU thread (0 = skip both CPU legs; default 8192, 1 for the large code)")
     ap.add_argument("--cpu-procs", type=int, default=-1,
-                    help="worker processes of the all-cores CPU leg (0 = skip it; default: usable cores, at most 64)")
-    ap.add_argument("--host-steps", type=int, default=3, help="steps of the host-to-host leg (0 = skip)")
+                    help="--full: worker processes of the all-cores CPU leg (0 = skip it; default: usable cores, at most 64)")
+    ap.add_argument("--host-steps", type=int, default=3, help="--full: steps of the host-to-host leg (0 = skip)")
     ap.add_argument("--variant", type=int, default=0, help="BP kernel / workgroup shape (0 auto; see bposd_set_bp_variant)")
     ap.add_argument("--ps-math-form", type=int, default=0, choices=(0, 1),
                     help="product-sum evaluation order: 0 the reference's (default), 1 two divisions per edge")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the final RCCL gather")
     ap.add_argument("--force-gather", action="store_true",
                     help="N = 1: initialise the RCCL backend at world size 1 and run the exchange step (packed rows, gather, all-reduce) anyway")
-    ap.add_argument("--no-cross", action="store_true", help="skip the cross-kernel check")
+    ap.add_argument("--no-cross", action="store_true", help="--full: skip the cross-kernel check")
     ap.add_argument("--no-pipeline", action="store_true", help="one step at a time (no overlap of consecutive steps)")
     ap.add_argument("--slots", type=int, default=0, help="steps in flight (default 2; more needs that many lanes)")
     ap.add_argument("--max-iter", type=int, default=-1, help="override max_iter (diagnostics; -1 = the config's)")
@@ -932,14 +993,15 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
 
     t_start = time.time()
-    with_extras = args.config is None and world == 1 and not args.no_extras and not args.force_gather and not args.batch and args.variant == 0
+    with_extras = (args.full and args.config is None and world == 1 and not args.no_extras and not args.force_gather and not args.batch
+                   and args.variant == 0)
     if args.config is None:
         args.config = "h1922_ms_cs7"
     runs = [args]
     if with_extras:
         for label, cfg, batch, gen in EXTRA_RUNS:
             e = copy.copy(args)
-            e.label, e.config, e.batch, e.gen = label, cfg, batch, gen
+            e.label, e.config, e.batch, e.gen, e.dump_outputs = label, cfg, batch, gen, None
             e.steps, e.warmup, e.host_steps, e.cpu_procs = args.extra_steps, 1, 0, 0
             if cfg.startswith("l29k"):  # (100 ms steps whose first two still warm the workspaces up: a few more, for a number close to the one of record)
                 e.steps, e.warmup = 2 * args.extra_steps, 2
@@ -992,7 +1054,7 @@ def main():
             torch.cuda.empty_cache()
         out["configs_note"] = ("short runs of the other BASELINE.json configurations in the same process (extra-steps timed steps, one seeded batch -- two alternating on l29k_ms_e15 --, "
                                "cross-kernel check on the whole batch, a one-core CPU sample where it costs < 10 s; their numbers of record "
-                               "with both CPU legs: python bench.py --config NAME, kept under profiles/); h1922_ms_cs7_b1048576 = the headline "
+                               "with both CPU legs: python bench.py --config NAME --full, kept under profiles/); h1922_ms_cs7_b1048576 = the headline "
                                "configuration with configs[3]'s whole batch of 2^20 syndromes on the one GPU")
         out["wall_s"] = time.time() - t_start
     if world > 1 or args.force_gather:

@@ -2,7 +2,7 @@
 # A/B bench of library builds x BP shapes on the GPU box.  Usage: bash tools/ab_bench.sh lib1.so lib2.so ...
 for lib in "$@"; do
   for v in 1 2 4; do
-    BPOSD_LIB=$lib timeout -k 10 120 python bench.py --steps 4 --warmup 1 --cpu-sample 0 --variant $v > /tmp/ab.log 2>&1 || { echo "$lib v$v FAILED"; tail -3 /tmp/ab.log; continue; }
+    BPOSD_LIB=$lib timeout -k 10 120 python bench.py --full --steps 4 --warmup 1 --cpu-sample 0 --variant $v > /tmp/ab.log 2>&1 || { echo "$lib v$v FAILED"; tail -3 /tmp/ab.log; continue; }
     python - "$lib" $v <<'PY'
 import json,sys
 d=json.loads(open("/tmp/ab.log").read().strip().splitlines()[-1])

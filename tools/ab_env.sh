@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
 for rep in $(seq 1 ${REPS:-3}); do
   for setting in "$@"; do
-    env $setting timeout -k 10 200 python bench.py --steps 5 --warmup 2 --cpu-sample 0 --host-steps 0 ${ARGS:---no-pipeline} > /tmp/ab.json 2>/tmp/ab.err || { echo "$setting FAILED"; tail -3 /tmp/ab.err; continue; }
+    env $setting timeout -k 10 200 python bench.py --full --steps 5 --warmup 2 --cpu-sample 0 --host-steps 0 ${ARGS:---no-pipeline} > /tmp/ab.json 2>/tmp/ab.err || { echo "$setting FAILED"; tail -3 /tmp/ab.err; continue; }
     python - "$setting" $rep <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
 for rep in $(seq 1 ${REPS:-2}); do
   for setting in "$@"; do
-    env $setting timeout -k 10 300 python bench.py --config l29k_ms_e15 --steps ${STEPS:-4} --warmup 1 --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "$setting FAILED"; tail -3 /tmp/ab.err; continue; }
+    env $setting timeout -k 10 300 python bench.py --full --config l29k_ms_e15 --steps ${STEPS:-4} --warmup 1 --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "$setting FAILED"; tail -3 /tmp/ab.err; continue; }
     python - "$setting" $rep <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

@@ -4,7 +4,7 @@
 for rep in $(seq 1 ${REPS:-2}); do
   for lib in "$@"; do
     for v in ${VARIANTS:-22 24}; do
-      BPOSD_LIB=$PWD/$lib timeout -k 10 200 python bench.py --steps 4 --warmup 1 --cpu-sample 0 --host-steps 0 --no-pipeline --variant $v > /tmp/ab.json 2>/tmp/ab.err || { echo "$lib v$v FAILED"; tail -3 /tmp/ab.err; continue; }
+      BPOSD_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --steps 4 --warmup 1 --cpu-sample 0 --host-steps 0 --no-pipeline --variant $v > /tmp/ab.json 2>/tmp/ab.err || { echo "$lib v$v FAILED"; tail -3 /tmp/ab.err; continue; }
       python - "$lib" $v $rep <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

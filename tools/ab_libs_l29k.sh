@@ -2,7 +2,7 @@
 # A/B of library builds on BASELINE configs[4] (l29k_ms_e15) IN ONE RUN.  Usage: REPS=2 bash tools/ab_libs_l29k.sh tools/_diag/libab_*.so
 for rep in $(seq 1 ${REPS:-2}); do
   for lib in "$@"; do
-    BPOSD_LIB=$PWD/$lib timeout -k 10 300 python bench.py --config l29k_ms_e15 --steps ${STEPS:-4} --warmup 1 --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "$lib FAILED"; tail -3 /tmp/ab.err; continue; }
+    BPOSD_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --config l29k_ms_e15 --steps ${STEPS:-4} --warmup 1 --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "$lib FAILED"; tail -3 /tmp/ab.err; continue; }
     python - "$lib" $rep <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

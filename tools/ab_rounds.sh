@@ -4,7 +4,8 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 for rep in $(seq 1 ${REPS:-3}); do
   for tree in "$REPO" "$REPO/_ab/$1"; do
-    (cd $tree && timeout -k 10 200 python bench.py --steps 5 --warmup 2 --cpu-sample 0 --host-steps 0 ${ARGS:---no-pipeline} > /tmp/ab.json 2>/tmp/ab.err) || { echo "$tree FAILED"; tail -3 /tmp/ab.err; continue; }
+    FULL=$(grep -q -- '"--full"' $tree/bench.py && echo --full)   # (trees older than the option: their plain line carries everything)
+    (cd $tree && timeout -k 10 200 python bench.py $FULL --steps 5 --warmup 2 --cpu-sample 0 --host-steps 0 ${ARGS:---no-pipeline} > /tmp/ab.json 2>/tmp/ab.err) || { echo "$tree FAILED"; tail -3 /tmp/ab.err; continue; }
     python - "$tree" $rep <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

@@ -3,7 +3,7 @@
 for rep in 1 2; do
 for cs in ${CASES:-256:2 160:3 128:3 128:4 96:4}; do
 g=${cs%%:*}; l=${cs##*:}
-BPOSD_LARGE_BP_GRID=$g BPOSD_LARGE_LANES=$l timeout -k 10 300 python bench.py --config l29k_ms_e15 --steps 12 --warmup 3 --slots $l --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "grid $g lanes $l FAILED"; tail -3 /tmp/ab.err; continue; }
+BPOSD_LARGE_BP_GRID=$g BPOSD_LARGE_LANES=$l timeout -k 10 300 python bench.py --full --config l29k_ms_e15 --steps 12 --warmup 3 --slots $l --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "grid $g lanes $l FAILED"; tail -3 /tmp/ab.err; continue; }
 python - $g $l <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

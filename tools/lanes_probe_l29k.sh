@@ -4,7 +4,7 @@
 # 35 ms of BP + ~50 ms of CU time in eliminations).
 for rep in 1 2; do
 for cfg in "2 2" "3 3" "4 4"; do set -- $cfg
-BPOSD_LARGE_LANES=$1 timeout -k 10 300 python bench.py --config l29k_ms_e15 --steps 8 --warmup 2 --slots $2 --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "lanes $1 FAILED"; tail -3 /tmp/ab.err; continue; }
+BPOSD_LARGE_LANES=$1 timeout -k 10 300 python bench.py --full --config l29k_ms_e15 --steps 8 --warmup 2 --slots $2 --cpu-sample 0 --host-steps 0 > /tmp/ab.json 2>/tmp/ab.err || { echo "lanes $1 FAILED"; tail -3 /tmp/ab.err; continue; }
 python - $1 <<'PY'
 import json,sys
 d=json.load(open('/tmp/ab.json'))

@@ -4,7 +4,7 @@
 set -o pipefail
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 SETTINGS=(); while [ "$1" != "--" ] && [ $# -gt 0 ]; do SETTINGS+=("$1"); shift; done; shift
-ARGS="--steps 1 --warmup 1 --cpu-sample 0 --host-steps 0 --no-pipeline $@"
+ARGS="--full --steps 1 --warmup 1 --cpu-sample 0 --host-steps 0 --no-pipeline $@"
 cd /tmp && export TMPDIR=/tmp
 for s in "${SETTINGS[@]}"; do
   OUT=$REPO/gpurun_out/pmcab_$(echo $s | tr -c 'A-Za-z0-9\n' '_')

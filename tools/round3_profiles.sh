@@ -17,7 +17,7 @@ bash tools/profile_bench.sh r03_nopipe --no-pipeline > $OUT/profile_nopipe.log 2
 bash tools/profile_bench.sh r03_hgp400 --config hgp400_ms_cs42 > $OUT/profile_hgp400.log 2>&1; echo "profile hgp400 done"
 cd $REPO
 # N > 1 rehearsal: the launcher starts the ranks before any GPU call; both ranks decode on device 0, gloo gather
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 4 --warmup 1 \
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 4 --warmup 1 \
     --rehearse-on-one-gpu > $OUT/bench_rehearsal_2ranks.json 2> $OUT/bench_rehearsal_2ranks.err; echo "rehearsal rc $?"
 for f in $(find $REPO/gpurun_out/prof_r03_* -name "*kernel_stats.csv"); do cp $f $OUT/$(echo $f | sed 's#.*/prof_\(r03_[a-z0-9]*\)/.*#\1#')_kernel_stats.csv; done
 ls $OUT

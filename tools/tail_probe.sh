@@ -1,6 +1,6 @@
 #!/bin/bash
 for mi in 0 600 300 150 60; do
-  timeout -k 10 120 python bench.py --steps 4 --warmup 1 --cpu-sample 0 --max-iter $mi > /tmp/tp.log 2>&1 || { echo "mi $mi FAILED"; tail -3 /tmp/tp.log; continue; }
+  timeout -k 10 120 python bench.py --full --steps 4 --warmup 1 --cpu-sample 0 --max-iter $mi > /tmp/tp.log 2>&1 || { echo "mi $mi FAILED"; tail -3 /tmp/tp.log; continue; }
   python - $mi <<'PY'
 import json,sys
 d=json.loads(open("/tmp/tp.log").read().strip().splitlines()[-1])
