@@ -57,6 +57,7 @@ DEBUG_SYMBOLS = (
     "bposd_bp_kernel_info",
     "bposd_debug_local_layout",
     "bposd_debug_class_layout",
+    "bposd_debug_last_instance",
 )
 
 
@@ -155,6 +156,8 @@ def load():
     lib.bposd_debug_local_layout.restype = C.c_int
     lib.bposd_debug_class_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.bposd_debug_class_layout.restype = C.c_int
+    lib.bposd_debug_last_instance.argtypes = [vp, vp, vp]
+    lib.bposd_debug_last_instance.restype = C.c_int
     lib.bposd_set_osd_variant.argtypes = [vp, C.c_int32]
     lib.bposd_set_osd_variant.restype = C.c_int
     lib.bposd_last_osd_kernel.argtypes = [vp]

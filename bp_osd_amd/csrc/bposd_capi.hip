@@ -459,6 +459,10 @@ const ClassShape* class_shape_for(const std::vector<int>& rp, const std::vector<
     return nullptr;
 }
 
+// annealing steps of the class layout search: bposd_create and the host-only bposd_debug_class_layout take the same
+// number, so that the diagnostic reports the tables (and the stride) the kernel runs with
+static int class_layout_iters() { return getenv("BPOSD_LAYOUT_ITERS") ? atoi(getenv("BPOSD_LAYOUT_ITERS")) : 200000; }
+
 int build_tables_class(bposd_handle* h) {
     h->class_ok = false;
     if (h->bp_hbm || h->m > 1024) return 0;
@@ -467,7 +471,7 @@ int build_tables_class(bposd_handle* h) {
     class_layout::Tables T;
     bool ok = false;
     int MP = 0;
-    const int iters = getenv("BPOSD_LAYOUT_ITERS") ? atoi(getenv("BPOSD_LAYOUT_ITERS")) : 200000;
+    const int iters = class_layout_iters();
     for (int mp : {256, 512, 1024}) {
         if (h->m > mp) continue;
         if (class_layout::build(h->rp, h->ci, h->m, h->n, shp->dclo, shp->dc, shp->dvlo, shp->dvhi, kClassVPT, mp, mp, iters, T)) { ok = true; MP = mp; break; }
@@ -1025,6 +1029,13 @@ int bposd_bp_kernel_info(bposd_handle* h, int32_t* kernel, int64_t* lds_model) {
             lds_model[0] = h->large_form;  // (no bank model: which form of the kernel ran -- bp_large_kernel.hip.h)
         }
     }
+    return BPOSD_OK;
+}
+
+int bposd_debug_last_instance(bposd_handle* h, int32_t bp[6], int32_t osd[6]) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (bp) std::copy(h->last_bp_inst, h->last_bp_inst + 6, bp);
+    if (osd) std::copy(h->last_osd_inst, h->last_osd_inst + 6, osd);
     return BPOSD_OK;
 }
 
@@ -1802,7 +1813,7 @@ int bposd_debug_class_layout(const int32_t* indptr, const int32_t* indices, int3
     bool ok = false;
     for (int mp : {256, 512, 1024}) {
         if (m > mp) continue;
-        if (class_layout::build(rp, ci, m, n, shp->dclo, shp->dc, shp->dvlo, shp->dvhi, kClassVPT, mp, mp, 50000, T)) { ok = true; break; }
+        if (class_layout::build(rp, ci, m, n, shp->dclo, shp->dc, shp->dvlo, shp->dvhi, kClassVPT, mp, mp, class_layout_iters(), T)) { ok = true; break; }
     }
     if (!ok) return BPOSD_ERR_UNSUPPORTED;
     info[0] = shp->dc; info[1] = shp->dvlo; info[2] = shp->dvhi; info[3] = kClassVPT; info[4] = T.MP; info[5] = T.NT;

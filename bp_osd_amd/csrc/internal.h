@@ -115,6 +115,8 @@ struct bposd_handle {
     int last_bp_kernel = -1;  // BPOSD_BP_KERNEL_* of the last BP launch
     int osd_variant = 0;      // 0 auto, 1 = one workgroup per elimination (osd_kernel), 2 = one wave per elimination where it applies
     int last_osd_kernel = -1; // 0 none yet, 1 osd_kernel, 2 osd_wave_kernel, 3 osd_large_kernel
+    int32_t last_bp_inst[6] = {-1, 0, 0, 0, 0, 0};   // bposd_debug_last_instance: the instance the last launch_* template launched
+    int32_t last_osd_inst[6] = {-1, 0, 0, 0, 0, 0};
     // host copies
     std::vector<int> rp, ci;
     std::vector<double> probs;
@@ -155,6 +157,12 @@ int fail(bposd_handle* h, int code, const char* fmt, ...) __attribute__((format(
             return bposd_host::fail(h, BPOSD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
                                     __FILE__, __LINE__);                                       \
     } while (0)
+
+// bposd_debug_last_instance: family code, the instance's template integers, packed-I/O flag
+inline void note_instance(int32_t (&dst)[6], int family, int a, int b, int c, int d, bool packed) {
+    const int32_t v[6] = {family, a, b, c, d, packed ? 1 : 0};
+    std::copy(v, v + 6, dst);
+}
 
 int sync_all_lanes(bposd_handle* h);
 int set_max_lds(bposd_handle* h, const void* kernel, size_t lds);

@@ -44,6 +44,7 @@ static int launch_bp_class_t(bposd_handle* h, const BpClassParams& C) {
     Cq.queue_shift = 1;
     while ((1ll << Cq.queue_shift) < grid * 2) Cq.queue_shift++;
     if (const char* e = getenv("BPOSD_CLASS_QUEUE_BATCH")) Cq.queue_batch = std::max(1, std::min(64, atoi(e)));
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_CLASS, DCLO, DC, DVHI, MP, Cq.packed_io != 0);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, h->cur->stream, Cq);
     HIP_TRY(h, hipGetLastError());
     return 0;

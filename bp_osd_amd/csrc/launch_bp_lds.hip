@@ -15,6 +15,7 @@ static int launch_bp_t(bposd_handle* h, const BpParams& P, int NT) {
     wg_per_cu = std::max(1, std::min(wg_per_cu, 8));
     long long grid = std::min<long long>(P.B, (long long)h->num_cu * wg_per_cu);
     if (grid < 1) grid = 1;
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LDS, DC, DV, CPT, MAXNT, P.packed_io != 0);
     if (h->cfg.bp_method == BPOSD_BP_MIN_SUM) {
         auto k = bp_kernel<DC, DV, CPT, VPT, MAXNT, MINW, REG, 1, MPT>;
         { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; }

@@ -39,6 +39,7 @@ static int launch_bp_local_tp(bposd_handle* h, const BpLocalParams& L) {
     if (rc) return rc;
     BpLocalParams Lq = L;
     Lq.llr_tmp = (double*)h->cur->bpl_llr.p;
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LOCAL, CPT, MP, MINW, EARLY, PACKED);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, h->cur->stream, Lq);
     HIP_TRY(h, hipGetLastError());
     return 0;

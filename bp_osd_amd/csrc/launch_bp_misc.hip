@@ -32,6 +32,7 @@ static int launch_bp_large_tm(bposd_handle* h, BpLargeParams& P) {
     if ((rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n))) return rc;
     P.msg_ws = (double*)h->cur->bpl_msg.p;
     P.llr_tmp = (double*)h->cur->bpl_llr.p;
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LARGE, DC, DV, METHOD, 0, P.packed_io != 0);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(bp_large_threads(METHOD)), lds, h->cur->stream, P);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -77,6 +78,7 @@ int launch_bp_serial(bposd_handle* h, const BpParams& P) {
     S.msg_ws = (double*)h->cur->bpl_msg.p;
     S.llr_tmp = (double*)h->cur->bpl_llr.p;
     { int rc_lds = set_max_lds(h, (const void*)bp_serial_kernel, lds); if (rc_lds) return rc_lds; }
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_SERIAL, 0, 0, 0, 0, false);
     hipLaunchKernelGGL(bp_serial_kernel, dim3((unsigned)grid), dim3(BPS_NT), lds, h->cur->stream, S);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -101,6 +103,7 @@ int launch_bp_any(bposd_handle* h, const BpParams& P) {
     A.msg_ws = (double*)h->cur->bpl_msg.p;
     A.llr_tmp = (double*)h->cur->bpl_llr.p;
     { int rc_lds = set_max_lds(h, (const void*)bp_anydeg_kernel, lds); if (rc_lds) return rc_lds; }
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_ANYDEG, 0, 0, 0, 0, false);
     hipLaunchKernelGGL(bp_anydeg_kernel, dim3((unsigned)grid), dim3(BPA_NT), lds, h->cur->stream, A);
     HIP_TRY(h, hipGetLastError());
     return 0;

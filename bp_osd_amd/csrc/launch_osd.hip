@@ -28,6 +28,7 @@ static int launch_osd_tp(bposd_handle* h, const OsdParams& P, long long B) {
     if (rc) return rc;
     OsdParams Q = P;
     Q.rows_ws = (unsigned long long*)h->cur->osd_rows_ws.p;
+    note_instance(h->last_osd_inst, 1, W, 0, 0, 0, PACKED);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, h->osd_now ? h->osd_now : h->cur->osd_stream, Q);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -62,6 +63,7 @@ static int launch_osd_wave_tp(bposd_handle* h, const OsdParams& P, long long B) 
     wg_per_cu = std::max(1, std::min(wg_per_cu, 8));
     long long grid = std::min<long long>((B + OSDW_WAVES - 1) / OSDW_WAVES, (long long)h->num_cu * wg_per_cu);
     if (grid < 1) grid = 1;
+    note_instance(h->last_osd_inst, 2, RPL, W, 0, 0, PACKED);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * OSDW_WAVES), lds, h->osd_now ? h->osd_now : h->cur->osd_stream, P);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -103,6 +105,7 @@ static int launch_osd_mw_tp(bposd_handle* h, const OsdParams& P, long long B) {
     if (getenv("BPOSD_DEBUG_OCC")) fprintf(stderr, "[bposd] osd_mw_kernel<%d,%d,%d>: %zu B LDS, %d workgroups per CU\n", NWV, RPL, W, lds, wg_per_cu);
     long long grid = std::min<long long>(B, (long long)h->num_cu * wg_per_cu);
     if (grid < 1) grid = 1;
+    note_instance(h->last_osd_inst, 4, NWV, RPL, W, MINW, PACKED);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(64 * NWV), lds, h->osd_now ? h->osd_now : h->cur->osd_stream, P);
     HIP_TRY(h, hipGetLastError());
     return 0;

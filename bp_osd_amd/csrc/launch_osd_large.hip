@@ -113,6 +113,7 @@ int launch_osd_large(bposd_handle* h, const OsdParams& P, long long B, int* d_ra
     case R: {                                                                                               \
         auto k = osd_large_kernel<R>;                                                                       \
         { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; } \
+        note_instance(h->last_osd_inst, 3, R, 0, 0, 0, Q.packed_io != 0);                                 \
         hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(OSDL_NT), lds, h->osd_now ? h->osd_now : h->cur->osd_stream, Q); \
     } break;
     switch (RPT) {

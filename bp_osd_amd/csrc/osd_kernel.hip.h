@@ -372,6 +372,9 @@ __global__ __launch_bounds__(64 * OSD_MAXW) void osd_kernel(const OsdParams P) {
         for (int i = tid; i < 32 * W; i += NT) L.wt[i] = 0x00010001;  // 16-bit single-candidate weights, two per word: 1 each
         for (int i = tid; i < 2 * 64; i += NT) L.pcol[i] = 0u;          // no value claimed yet: the panel phase's sub-blocks count from 1
         unsigned int sbc = 1u;  // number of the current six-column sub-block of this elimination (uniform; <= 11 * W)
+        // claims are (sbc << 10) | row, per-value pivot info (sbc << 13) | (column << 10) | row, rowbuf is indexed by row & 1023
+        static_assert(OSD_RPT * 64 * OSD_MAXW <= 1024, "the panel phase's claims carry the row in 10 bits");
+        static_assert(1 + 11 * W < (1 << 19), "the sub-block number overflows the 19 bits the pivot info leaves it");
         __syncthreads();
         for (int k = 2; k <= NS; k <<= 1) {
             for (int j = k >> 1; j > 0; j >>= 1) {
@@ -474,15 +477,18 @@ __global__ __launch_bounds__(64 * OSD_MAXW) void osd_kernel(const OsdParams P) {
 #ifdef BPOSD_OSD_DIAG
                     diag_t1 = OSD_TICK();
 #endif
-                    // (A) claims: a plain store of (sub-block number, row) per claimed value -- whichever claimant's store lands
-                    // last is the row the solvers see -- and every claimant's (panel word, mask) into its own slot of rowbuf:
-                    // nothing to wait for before the barrier (an atomic with return, the first form of this, cost a round trip)
+                    // (A) claims: (sub-block number, row) per claimed value by an LDS atomic max without return -- the
+                    // highest claiming row is the one the solvers see, the same row on every run (a plain store let whichever
+                    // claimant's store landed last win: on a syndrome outside the column space of H the pivot rows decide which
+                    // checks the solution leaves unsatisfied, so the output changed from run to run) -- and every claimant's
+                    // (panel word, mask) into its own slot of rowbuf: nothing to wait for before the barrier (an atomic with
+                    // return, the first form of this, cost a round trip)
                     unsigned int bv[RPT];
 #pragma unroll
                     for (int k = 0; k < RPT; ++k) {
                         bv[k] = (unsigned int)(row[k][0] >> c0) & vmask;
                         if (pinfo[k] < 0 && bv[k] != 0u) {  // rows beyond m are zero: they never claim
-                            claim[bv[k]] = (sbc << 10) | (unsigned int)(tid + k * NT);
+                            atomicMax(&claim[bv[k]], (sbc << 10) | (unsigned int)(tid + k * NT));
                             rowbuf[tid + k * NT] = make_ulonglong2(row[k][0], t[k]);
                         }
                     }
@@ -498,7 +504,7 @@ __global__ __launch_bounds__(64 * OSD_MAXW) void osd_kernel(const OsdParams P) {
                         // the valid columns, so j >= wsb never finds a candidate.  (The same on the scalar unit -- value sets
                         // as 64-bit masks, s_bitcmp1 / s_cselect / s_xor -- was built and measured no faster: a lone wave
                         // issues about one instruction per eight cycles whatever the unit, and this form has fewer.)
-                        const unsigned int cw = claim[lane];  // last claim of value `lane`: (sub-block number << 10) | row
+                        const unsigned int cw = claim[lane];  // highest claim of value `lane`: (sub-block number << 10) | row
                         const unsigned long long avm0 = __ballot((cw >> 10) == sbc) & ~1ull;  // claimed values
                         unsigned int X = (unsigned int)lane, Y = 0u;
                         unsigned int pivmask = 0u;  // columns of the sub-block that are pivot columns (uniform)

@@ -619,6 +619,27 @@ class BpOsdDecoder:
         """Name of the OSD kernel the last decode call launched ("none" before the first one)."""
         return self.OSD_KERNEL_NAMES.get(self._lib.bposd_last_osd_kernel(self._h), "none")
 
+    # template integers bposd_debug_last_instance reports per family (include/bposd_mi355x_debug.h)
+    _BP_INSTANCE_ARITY = {0: 4, 1: 4, 2: 4, 3: 3, 4: 0, 5: 0}
+    _OSD_INSTANCE_ARITY = {1: 1, 2: 2, 3: 1, 4: 4}
+
+    def last_instance(self):
+        """The exact kernel instances the last launches ran: ``{"bp": (name, template integers, packed), "osd": (...)}``,
+        e.g. ``("bp_kernel", (16, 8, 2, 1024), False)`` and ``("osd_kernel", (31,), False)`` -- the template integers of each
+        family are listed in include/bposd_mi355x_debug.h.  ``("none", (), False)`` before the first launch."""
+        bp = np.zeros(6, dtype=np.int32)
+        osd = np.zeros(6, dtype=np.int32)
+        _lib.check(self._lib, self._h, self._lib.bposd_debug_last_instance(self._h, bp.ctypes.data, osd.ctypes.data))
+
+        def entry(v, names, arity):
+            code = int(v[0])
+            if code not in names:
+                return ("none", (), False)
+            return (names[code], tuple(int(x) for x in v[1:1 + arity[code]]), bool(v[5]))
+
+        return {"bp": entry(bp, self.BP_KERNEL_NAMES, self._BP_INSTANCE_ARITY),
+                "osd": entry(osd, self.OSD_KERNEL_NAMES, self._OSD_INSTANCE_ARITY)}
+
     def set_bp_variant(self, variant: int):
         """Tuning / test knob: 0 auto; 1, 2, 4 LDS kernel shapes; 16 .. 26 local-edge kernel; 32 class kernel; 63 HBM-resident min-sum with whole check records in the workspace; 64 any-degree kernel (slow; cross-checks) -- see the C header."""
         _lib.check(self._lib, self._h, self._lib.bposd_set_bp_variant(self._h, int(variant)))

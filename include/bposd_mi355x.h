@@ -110,6 +110,11 @@ int bposd_update_channel_probs(bposd_handle *h, const double *channel_probs);
  *   iters[B]   -> `.iter`;  llr[B*n] -> `.log_prob_ratios` (final BP LLRs, fp64)
  * Replaces: `.decode(syndrome)` -- README.md:197; css_decode_sim.py:174-202 (B = 1),
  * and is the batched form the MI355X path is built around.
+ * A syndrome outside the column space of H (rank-deficient H) has no exact solution: BP's outputs are unaffected, and
+ * osd0 is then a solution of the checks of the pivot rows the OSD kernel kept.  Which rows those are is the kernel's
+ * choice -- not the reference's partial pivoting, so other checks may stay unsatisfied than there -- but it is the same
+ * on every run, and osdw is the candidate search from that osd0: the reference's OSD on the syndrome H osd0, with the
+ * same LLRs, returns the same osd0 and osdw.  Inside the column space every output is the reference's.
  */
 int bposd_decode_batch(bposd_handle *h, const uint8_t *syndromes, int64_t B, uint8_t *osdw,
                        uint8_t *osd0, uint8_t *bp, uint8_t *converged, int32_t *iters, double *llr);

@@ -30,6 +30,20 @@ int bposd_layout_info(bposd_handle *h, int64_t *natural_cycles, int64_t *chosen_
 #define BPOSD_BP_KERNEL_ANYDEG 5 /* bp_anydeg_kernel: check degree > 16 or bit degree > 8 (run-time degree loops) */
 int bposd_bp_kernel_info(bposd_handle *h, int32_t *kernel, int64_t *lds_model);
 
+/* Diagnostics: the exact kernel instances the last launches of this handle ran (a later change of the dispatch rules shows
+ * up here).  bp[6] / osd[6], either may be NULL: [0] the family code -- BPOSD_BP_KERNEL_* for bp, the bposd_last_osd_kernel
+ * code for osd (1 osd_kernel, 2 osd_wave_kernel, 3 osd_large_kernel, 4 osd_mw_kernel) -- or -1 before the first launch;
+ * [1..4] the instance's template integers in declaration order, zeros where there are fewer; [5] 1 if the kernel read
+ * packed syndromes and wrote packed rows.  Template integers per family:
+ *   bp_kernel <DC, DV, CPT, MAXNT>          (CPT 1 / MAXNT 1024: shape 1; 2 / 512: shape 2; 4 / 256: shape 4; 2 / 1024: shape 8)
+ *   bp_local_kernel <CPT, MP, MINW, EARLY>
+ *   bp_class_kernel <DCLO, DC, DVHI, MP>    (DVLO follows from the degree class)
+ *   bp_large_kernel <DC, DV, METHOD>
+ *   bp_serial_kernel, bp_anydeg_kernel      (no template integers)
+ *   osd_kernel <W>,  osd_wave_kernel <RPL, W>,  osd_mw_kernel <NWV, RPL, W, MINW>,  osd_large_kernel <RPT>
+ * The OSD record is also written by the rank probe of an HBM-resident handle at creation. */
+int bposd_debug_last_instance(bposd_handle *h, int32_t bp[6], int32_t osd[6]);
+
 /* Diagnostics, host only (needs no device): the ownership / position layout the local-edge BP kernel would use for a
  * (3,6)-regular pcm with n = 2m.  out[16]: modelled ds_read_b64 cycles of one bit pass, their conflict-free
  * floor, positions in select-free (uniform) groups, mixed (group, slot) pairs, positions, nine class sizes, modelled
