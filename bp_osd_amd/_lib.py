@@ -47,6 +47,12 @@ EXPORTED_SYMBOLS = (
     "bposd_set_bp_variant",
     "bposd_set_osd_variant",
     "bposd_last_osd_kernel",
+    "bposd_mc_create",
+    "bposd_mc_run",
+    "bposd_mc_fetch",
+    "bposd_mc_device_bytes",
+    "bposd_mc_last_error",
+    "bposd_mc_destroy",
     "bposd_last_error",
     "bposd_destroy",
 )
@@ -76,6 +82,20 @@ class BposdConfig(C.Structure):
         ("osd_e_bit_order", C.c_int32),
         ("ps_math_form", C.c_int32),
     ]
+
+
+class BposdMcConfig(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("channel_update", C.c_int32),
+        ("seed", C.c_uint64),
+        ("capacity", C.c_int64),
+    ]
+
+
+# bposd_mc_config.channel_update / bposd_mc_fetch(what)
+MC_UPDATE = {None: 0, "x->z": 1, "z->x": 2}
+MC_ITEMS = {"error_x": 0, "error_z": 1, "syndrome_x": 2, "syndrome_z": 3, "flags": 4, "syndrome_x_packed": 5, "syndrome_z_packed": 6}
 
 
 _lib = None
@@ -168,8 +188,32 @@ def load():
     lib.bposd_last_error.restype = C.c_char_p
     lib.bposd_destroy.argtypes = [vp]
     lib.bposd_destroy.restype = None
+    lib.bposd_mc_create.argtypes = [C.POINTER(BposdMcConfig), vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32,
+                                    vp, vp, vp, vp, C.POINTER(vp)]
+    lib.bposd_mc_create.restype = C.c_int
+    lib.bposd_mc_run.argtypes = [vp, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]
+    lib.bposd_mc_run.restype = C.c_int
+    lib.bposd_mc_fetch.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+    lib.bposd_mc_fetch.restype = C.c_int
+    lib.bposd_mc_device_bytes.argtypes = [vp]
+    lib.bposd_mc_device_bytes.restype = C.c_int64
+    lib.bposd_mc_last_error.argtypes = [vp]
+    lib.bposd_mc_last_error.restype = C.c_char_p
+    lib.bposd_mc_destroy.argtypes = [vp]
+    lib.bposd_mc_destroy.restype = None
     _lib = lib
     return lib
+
+
+def check_mc(lib, mc, rc):
+    """check() for the Monte-Carlo engine's calls (mc None: a failed bposd_mc_create)."""
+    if rc == BPOSD_OK:
+        return
+    msg = lib.bposd_mc_last_error(mc)
+    msg = msg.decode() if msg else f"error {rc}"
+    if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
+        raise ValueError(msg)
+    raise RuntimeError(msg)
 
 
 def check(lib, handle, rc):

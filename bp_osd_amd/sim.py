@@ -18,6 +18,13 @@ harness runs at the decoders' rate instead of numpy's (34 k runs/s on the [[1922
 random numbers still come from numpy's legacy stream (uploaded), which makes the counters identical to the default
 engine's; ``rng="torch"`` draws them on the device (seeded, but a different stream).  torch is plumbing here (device
 buffers, sparse products); every decode runs in the HIP kernels either way.
+
+``engine="native"`` is the device-resident harness without torch: one call into libbposd_mi355x.so per batch samples the
+errors, computes both syndromes, runs the two decodes and the logical checks in HIP kernels and returns seven integers
+(include/bposd_mi355x.h "Monte-Carlo engine", DESIGN.md "Monte-Carlo engine").  Its random numbers are the project's own
+counter-based stream, ``rng="philox"``: Philox4x32-10 keyed by the seed and indexed by (shot, qubit), restated below in
+numpy (``philox4x32_10``, ``philox_uniforms``).  ``engine="numpy", rng="philox"`` draws the same numbers on the host, so
+both engines see the same shots whatever their batch sizes.
 """
 from __future__ import annotations
 
@@ -30,7 +37,40 @@ import scipy.sparse as sp
 
 from .codes import CssCode
 
-__all__ = ["css_decode_sim"]
+__all__ = ["css_decode_sim", "philox4x32_10", "philox_uniforms"]
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., Random123): ``counter`` = four and ``key`` = two arrays (or ints) of 32-bit words,
+    broadcast against each other; returns the four output words as uint64 arrays holding 32-bit values."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _M32 for c in counter)
+    k0, k1 = (np.asarray(k, dtype=np.uint64) & _M32 for k in key)
+    for _ in range(10):
+        p0 = c0 * np.uint64(0xD2511F53)  # 32 x 32 -> 64 bits: no overflow in uint64
+        p1 = c2 * np.uint64(0xCD9E8D57)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _M32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _M32
+        k0 = (k0 + np.uint64(0x9E3779B9)) & _M32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c0, c1, c2, c3
+
+
+def philox_uniforms(seed, first_shot, B, N):
+    """float64 [B, N]: u(s, i) of shots first_shot .. first_shot + B - 1 -- the stream mc_sample_kernel draws on the device.
+
+    counter = (s & 0xffffffff, s >> 32, i >> 1, 0), key = (seed & 0xffffffff, seed >> 32); qubit 2j takes the first two
+    output words of pair j and qubit 2j + 1 the last two; (a, b) = (hi >> 5, lo >> 6), u = (a * 2^26 + b) * 2^-53 (numpy's
+    legacy recipe for a double, exact in fp64)."""
+    seed, first_shot = int(seed) & (2 ** 64 - 1), int(first_shot)
+    s = (np.arange(B, dtype=np.uint64) + np.uint64(first_shot))[:, None]
+    pair = np.arange((N + 1) // 2, dtype=np.uint64)[None, :]
+    o = philox4x32_10((s & _M32, s >> np.uint64(32), pair, 0), (seed & 0xFFFFFFFF, seed >> 32))
+    u = np.empty((B, 2 * pair.shape[1]), dtype=np.float64)
+    for half in (0, 1):
+        a, b = o[2 * half] >> np.uint64(5), o[2 * half + 1] >> np.uint64(6)
+        u[:, half::2] = (a.astype(np.float64) * 67108864.0 + b.astype(np.float64)) * (1.0 / 9007199254740992.0)
+    return u[:, :N]
 
 _DEFAULT_INPUT = {  # css_decode_sim.py:65-84
     "error_rate": None,
@@ -104,13 +144,19 @@ class css_decode_sim:
         ``BpOsdDecoder``); tests inject a CPU-oracle adapter here.
     """
 
-    def __init__(self, hx=None, hz=None, batch_size=4096, decoder_factory=None, engine="numpy", rng="numpy", **input_dict):
-        if engine not in ("numpy", "torch") or rng not in ("numpy", "torch"):
-            raise ValueError("engine and rng must be 'numpy' or 'torch'")
-        if engine == "torch" and decoder_factory is not None:
-            raise ValueError("engine='torch' drives the MI355X decoders through device pointers; decoder_factory must be None")
+    def __init__(self, hx=None, hz=None, batch_size=4096, decoder_factory=None, engine="numpy", rng=None, **input_dict):
+        if rng is None:
+            rng = "philox" if engine == "native" else "numpy"
+        if engine not in ("numpy", "torch", "native") or rng not in ("numpy", "torch", "philox"):
+            raise ValueError("engine must be 'numpy', 'torch' or 'native', rng 'numpy', 'torch' or 'philox'")
+        if engine in ("torch", "native") and decoder_factory is not None:
+            raise ValueError(f"engine='{engine}' drives the MI355X decoders through device pointers; decoder_factory must be None")
         if engine == "numpy" and rng == "torch":
             raise ValueError("rng='torch' needs engine='torch'")
+        if engine == "native" and rng != "philox":
+            raise ValueError("engine='native' draws on the device from the Philox stream: rng must be 'philox'")
+        if engine == "torch" and rng == "philox":
+            raise ValueError("rng='philox' needs engine='numpy' or engine='native'")
         self._engine, self._rng = engine, rng
         for key, val in input_dict.items():  # css_decode_sim.py:87-91: anything passed overrides
             self.__dict__[key] = val
@@ -186,7 +232,10 @@ class css_decode_sim:
 
     # ------------------------------------------------------------------ one batch
     def _generate_errors(self, B):  # css_decode_sim.py:465-498, vectorised over B shots
-        rand = np.random.random((B, self.N))
+        if self._rng == "philox":  # shots run_count .. run_count + B - 1 of the counter-based stream
+            rand = philox_uniforms(self.seed, self.run_count, B, self.N)
+        else:
+            rand = np.random.random((B, self.N))
         pz, px, py = self.channel_probs_z, self.channel_probs_x, self.channel_probs_y
         is_z = rand < pz
         is_x = (pz <= rand) & (rand < pz + px)
@@ -312,9 +361,100 @@ class css_decode_sim:
             setattr(self, f"{key}_success_count", getattr(self, f"{key}_success_count") + int((~failed).sum().item()))
         self._update_rates()
 
+    # ------------------------------------------------------------------ one batch in the library's Monte-Carlo engine
+    def _native_setup(self):
+        import ctypes as C
+
+        from . import _lib
+        from .decoder import BpOsdDecoder
+
+        if self.channel_update not in _lib.MC_UPDATE:
+            raise ValueError(f"channel_update='{self.channel_update}' is invalid")
+        alt = None
+        if self.channel_update == "x->z":  # the per-batch update_channel_probs of the other engines: the same values every batch
+            alt, p0 = self._updated_channel(self.channel_probs_x, self.channel_probs_z)
+            self.bpd_z.update_channel_probs(p0)
+        elif self.channel_update == "z->x":
+            alt, p0 = self._updated_channel(self.channel_probs_z, self.channel_probs_x)
+            self.bpd_x.update_channel_probs(p0)
+        lib = self._mc_lib = _lib.load()
+        cfg = _lib.BposdMcConfig(device=int(self.bpd_x.device), channel_update=_lib.MC_UPDATE[self.channel_update],
+                                 seed=int(self.seed) & (2 ** 64 - 1), capacity=self._batch_size)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        hx, hz = sp.csr_matrix(self.hx), sp.csr_matrix(self.hz)
+        hx.sort_indices()
+        hz.sort_indices()
+        keep = [i32(hx.indptr), i32(hx.indices), i32(hz.indptr), i32(hz.indices),
+                BpOsdDecoder.pack_rows(np.asarray(self.lx, dtype=np.uint8) & 1), BpOsdDecoder.pack_rows(np.asarray(self.lz, dtype=np.uint8) & 1),
+                f64(self.channel_probs_x), f64(self.channel_probs_y), f64(self.channel_probs_z), None if alt is None else f64(alt)]
+        ptr = [None if a is None else a.ctypes.data for a in keep]
+        self._mc = C.c_void_p()
+        rc = lib.bposd_mc_create(C.byref(cfg), self.bpd_x._h, self.bpd_z._h, ptr[0], ptr[1], hx.shape[0], ptr[2], ptr[3], hz.shape[0],
+                                 self.N, ptr[4], ptr[5], int(np.asarray(self.lx).shape[0]), ptr[6], ptr[7], ptr[8], ptr[9], C.byref(self._mc))
+        if rc != 0:
+            self._mc = None
+            _lib.check_mc(lib, None, rc)
+        self._mc_rows = {"error_x": (np.dtype("<u8"), (self.N + 63) // 64), "error_z": (np.dtype("<u8"), (self.N + 63) // 64),
+                         "syndrome_x": (np.dtype(np.uint8), hz.shape[0]), "syndrome_z": (np.dtype(np.uint8), hx.shape[0]),
+                         "flags": (np.dtype(np.uint8), None), "syndrome_x_packed": (np.dtype("<u8"), (hz.shape[0] + 63) // 64),
+                         "syndrome_z_packed": (np.dtype("<u8"), (hx.shape[0] + 63) // 64)}
+        self._mc_last_B = 0
+
+    def _run_batch_native(self, B):
+        import ctypes as C
+
+        from . import _lib
+
+        if getattr(self, "_mc", None) is None:
+            self._native_setup()
+        c = (C.c_int64 * 7)()
+        _lib.check_mc(self._mc_lib, self._mc, self._mc_lib.bposd_mc_run(self._mc, int(self.run_count), int(B), c))
+        self._mc_last_B = B
+        self.run_count += B
+        self.bp_converge_count_x += int(c[0])
+        self.bp_converge_count_z += int(c[1])
+        self.bp_success_count += int(c[2])
+        self.osd0_success_count += int(c[3])
+        self.osdw_success_count += int(c[4])
+        wmin = min(int(c[5]), int(c[6]))  # INT32_MAX where nothing failed
+        if wmin < self.min_logical_weight:
+            self.min_logical_weight = wmin
+        self._update_rates()
+
+    def last_batch(self, what):
+        """engine="native": one array of the last batch, copied from the device -- "error_x" / "error_z" (bit-packed rows,
+        uint64 [B, ceil(N/64)]: ``BpOsdDecoder.unpack_rows`` expands them), "syndrome_x" / "syndrome_z" (uint8 rows),
+        "syndrome_x_packed" / "syndrome_z_packed", or "flags" (uint8 [B]: bit 0 / 1 = the bp output failed the X- / Z-logical
+        check, bits 2 / 3 osd0, bits 4 / 5 osdw)."""
+        from . import _lib
+
+        if self._engine != "native" or not getattr(self, "_mc_last_B", 0):
+            raise RuntimeError("last_batch needs engine='native' and a batch that has run")
+        if what not in self._mc_rows:
+            raise ValueError(f"what must be one of {sorted(self._mc_rows)}")
+        dtype, cols = self._mc_rows[what]
+        out = np.empty(self._mc_last_B if cols is None else (self._mc_last_B, cols), dtype=dtype)
+        rc = self._mc_lib.bposd_mc_fetch(self._mc, _lib.MC_ITEMS[what], out.ctypes.data, out.nbytes)
+        _lib.check_mc(self._mc_lib, self._mc, rc)
+        return out
+
+    def mc_device_bytes(self):
+        """engine="native": bytes of device memory the engine holds for its batches (the decoders' workspaces are theirs)."""
+        if getattr(self, "_mc", None) is None:
+            self._native_setup()
+        return int(self._mc_lib.bposd_mc_device_bytes(self._mc))
+
+    def __del__(self):
+        mc, self._mc = getattr(self, "_mc", None), None
+        if mc is not None:  # before the decoders it points to go
+            self._mc_lib.bposd_mc_destroy(mc)
+
     def _run_batch(self, B):
         if self._engine == "torch":
             return self._run_batch_torch(B)
+        if self._engine == "native":
+            return self._run_batch_native(B)
         error_x, error_z = self._generate_errors(B)
         synd_z = _mod2_mul(self.hx, error_z)
         synd_x = _mod2_mul(self.hz, error_x)

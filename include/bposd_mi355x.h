@@ -267,6 +267,77 @@ int bposd_last_osd_kernel(bposd_handle *h);
  * kernel on any code (slow; a second implementation for cross-checks, also of the HBM-resident BP kernel). */
 int bposd_set_bp_variant(bposd_handle *h, int32_t variant);
 
+/*
+ * Monte-Carlo engine: the device-resident form of the reference's harness loop
+ * (/root/reference/src/bposd/css_decode_sim.py:174-365, 465-498).  One bposd_mc_run is one batch of shots:
+ * sample the errors -> both syndromes -> the two decodes -> logical checks of the bp / osd0 / osdw outputs -> seven
+ * integers.  The handle owns every device buffer of a batch, so a device-resident simulation needs no torch (or any
+ * other tensor library); bp_osd_amd/sim.py drives it as css_decode_sim(engine="native").
+ *
+ * Random stream (defined by this project, the same on host and device, independent of the batch size): Philox4x32-10.
+ * For shot s (global, 64 bit), qubit i and the 64-bit seed:
+ *   counter = (s & 0xffffffff, s >> 32, i >> 1, 0), key = (seed & 0xffffffff, seed >> 32), (o0, o1, o2, o3) = philox(counter, key)
+ *   (a, b) = (o0 >> 5, o1 >> 6) for even i, (o2 >> 5, o3 >> 6) for odd i;  u = (a * 2^26 + b) * 2^-53
+ *   Z if u < pz, X if pz <= u < pz + px, Y if pz + px <= u < px + py + pz; error_z = Z | Y, error_x = X | Y
+ * (the thresholds in fp64, in that operation order: css_decode_sim.py:476-490).  Shot s of a run is row s - first_shot.
+ */
+typedef struct bposd_mc bposd_mc;
+
+enum { BPOSD_MC_UPDATE_NONE = 0, BPOSD_MC_UPDATE_X_TO_Z = 1, BPOSD_MC_UPDATE_Z_TO_X = 2 };
+
+typedef struct {
+    int32_t device;          /* HIP device ordinal; both decoders must live there                              */
+    int32_t channel_update;  /* BPOSD_MC_UPDATE_*: css_decode_sim.py:207-248                                     */
+    uint64_t seed;           /* key of the random stream                                                       */
+    int64_t capacity;        /* largest batch a run may ask for: every per-batch buffer is allocated for it     */
+} bposd_mc_config;
+
+/* What bposd_mc_fetch copies out of the last batch (B rows each). */
+enum {
+    BPOSD_MC_ERROR_X = 0,           /* uint64[B][ceil(n/64)]: packed rows, the layout of bposd_decode_batch_packed    */
+    BPOSD_MC_ERROR_Z = 1,
+    BPOSD_MC_SYNDROME_X = 2,        /* uint8[B][mz]: hz . error_x                                                   */
+    BPOSD_MC_SYNDROME_Z = 3,        /* uint8[B][mx]: hx . error_z                                                   */
+    BPOSD_MC_FLAGS = 4,             /* uint8[B]: bit 0 / 1 bp failed the X- / Z-logical check, 2 / 3 osd0, 4 / 5 osdw */
+    BPOSD_MC_SYNDROME_X_PACKED = 5, /* uint64[B][ceil(mz/64)]                                                       */
+    BPOSD_MC_SYNDROME_Z_PACKED = 6  /* uint64[B][ceil(mx/64)]                                                       */
+};
+
+/*
+ * dec_x decodes hz . error_x, dec_z decodes hx . error_z (css_decode_sim.py:444-463); they stay the caller's and must
+ * outlive the engine.  hx [mx x n] and hz [mz x n] as CSR; lx, lz as k packed rows of ceil(n/64) words; probs_* [n] the
+ * per-qubit probabilities of X, Y and Z errors.  With a channel update, the decoder that runs second must already hold
+ * the probabilities for "the first decoder's osdw bit is 0" (bposd_update_channel_probs), and alt_probs [n] are those for
+ * "bit is 1" (css_decode_sim.py:217-227, 236-246); alt_probs may be NULL without a channel update.  Everything is copied.
+ */
+int bposd_mc_create(const bposd_mc_config *cfg, bposd_handle *dec_x, bposd_handle *dec_z, const int32_t *hx_indptr,
+                    const int32_t *hx_indices, int32_t mx, const int32_t *hz_indptr, const int32_t *hz_indices, int32_t mz,
+                    int32_t n, const uint64_t *lx_words, const uint64_t *lz_words, int32_t k, const double *probs_x,
+                    const double *probs_y, const double *probs_z, const double *alt_probs, bposd_mc **out);
+
+/*
+ * One batch: shots first_shot .. first_shot + B - 1 (B <= capacity).  Returns with the counters on the host:
+ *   [0] bp_converge_count_x  [1] bp_converge_count_z  [2] bp_success_count (both converged, no logical failure)
+ *   [3] osd0_success_count   [4] osdw_success_count
+ *   [5], [6] smallest weight of a failing residual of osd0 / osdw (INT32_MAX when nothing failed); the weight is that of
+ *   residual_x where the X-logical check failed, else of residual_z (css_decode_sim.py:257-272)
+ * Without a channel update the two decodes run side by side on their handles' lanes, otherwise the second one takes the
+ * first one's osdw rows through the per-shot channel of bposd_decode_batch_select_device.  The engine's stream and the
+ * lanes are ordered by events; the one host wait of a batch is the one for the counters.
+ */
+int bposd_mc_run(bposd_mc *mc, uint64_t first_shot, int64_t B, int64_t counters[7]);
+
+/* Copy one item (BPOSD_MC_ERROR_X ...) of the last batch to host memory; bytes must be that item's size for the last B. */
+int bposd_mc_fetch(bposd_mc *mc, int32_t what, void *host_dst, size_t bytes);
+
+/* Device memory the engine holds (the sum of its own allocations; the decoders' workspaces are theirs). */
+int64_t bposd_mc_device_bytes(bposd_mc *mc);
+
+/* Message for the last error on this engine (mc == NULL: the last bposd_mc_create failure). */
+const char *bposd_mc_last_error(bposd_mc *mc);
+
+void bposd_mc_destroy(bposd_mc *mc);
+
 /* Message for the last error on this handle (h == NULL: last create() failure). */
 const char *bposd_last_error(bposd_handle *h);
 
