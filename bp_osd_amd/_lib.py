@@ -62,6 +62,7 @@ DEBUG_SYMBOLS = (
     "bposd_layout_info",
     "bposd_bp_kernel_info",
     "bposd_debug_local_layout",
+    "bposd_debug_local_keys",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
 )
@@ -174,6 +175,8 @@ def load():
     lib.bposd_bp_kernel_info.restype = C.c_int
     lib.bposd_debug_local_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
     lib.bposd_debug_local_layout.restype = C.c_int
+    lib.bposd_debug_local_keys.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+    lib.bposd_debug_local_keys.restype = C.c_int
     lib.bposd_debug_class_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.bposd_debug_class_layout.restype = C.c_int
     lib.bposd_debug_last_instance.argtypes = [vp, vp, vp]

@@ -13,10 +13,12 @@
 // top of the column including the prior, suffix from the bottom -- SURVEY.md Appendix A.3), so the local
 // message has to enter the sums at the position dl in {0,1,2} its check has among the bit's three checks in
 // ascending order.  The host therefore sorts checks into 64-position groups (a wave = one group per owned
-// check) whose slot-b bits share one dl wherever it can; the kernel switches on the wave-uniform code
-// (0, 1, 2: straight-line code, instruction for instruction the arithmetic of bp_kernel; 3: a mixed group, the
-// operands are routed by per-lane selects).  The position count MP is a compile-time power of two, as in
-// bp_kernel, so LDS offsets are instruction immediates.
+// check) whose slot-b bits share one dl wherever it can.  The code is wave-uniform and never changes (0, 1, 2:
+// straight-line code, instruction for instruction the arithmetic of bp_kernel; 3: a mixed group, the operands are
+// routed by per-lane selects), so it is decided once, outside the iteration loop: the loop exists as one body per
+// key of a group's two codes (local_keys.h), the host puts groups of equal key into the same wave, and a wave whose
+// groups differ runs a generic body with one switch per group.  The position count MP is a compile-time power of
+// two, as in bp_kernel, so LDS offsets are instruction immediates.
 //
 // Everything else -- persistent workgroups on an atomic queue, in-place messages, incremental convergence
 // bitmap with a speculative check pass, outputs, OSD hand-off -- is the scheme of bp_kernel.hip.h (rows a3-a7).
@@ -25,6 +27,7 @@
 #include <stdint.h>
 
 #include "bp_kernel.hip.h"
+#include "local_keys.h"
 
 #ifndef BPOSD_BPL_SIGN_ON_MAG
 #define BPOSD_BPL_SIGN_ON_MAG 0
@@ -136,6 +139,16 @@ __device__ __forceinline__ bpl_args_ptr bpl_args() {
     return a;
 }
 
+template <int V>
+struct bpl_int {
+    static constexpr int value = V;
+};
+
+// the instances launch_bp_local.hip selects without a variant being asked for (and their packed-I/O forms)
+__host__ __device__ constexpr bool bpl_specialised(int cpt, int mpt, int minw, bool early) {
+    return !early && ((cpt == 1 && mpt == 1024 && minw == 8) || (cpt == 2 && mpt == 1024 && (minw == 8 || minw == 6)) || (cpt == 2 && mpt == 2048 && minw == 4));
+}
+
 // CPT: checks per thread (each with its two owned bits); MPT: positions (power of two) = blockDim.x * CPT;
 // EARLY: the check pass requests the LDS messages of all its checks before it computes the first one (the LDS accesses
 // are volatile, i.e. issued in program order: without this the read latency is exposed once per check)
@@ -174,7 +187,7 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
     typedef __attribute__((address_space(3))) unsigned char* lds_bytes;
     const unsigned int msg_base = (unsigned int)(uintptr_t)(lds_bytes)smem;
     unsigned int alo[NB], ahi[NB];
-    int dl[NB];
+    int dl[NB];                // the groups' dl codes: they only form the keys below, none is live in the iteration loop
     unsigned int dlpack = 0u;  // 2 bits per owned bit: its dl (needed per lane only in mixed groups)
     double l0[UPRIOR ? 1 : NB];
     if (UPRIOR) {  // into a scalar register pair
@@ -202,6 +215,17 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
             dlpack |= (unsigned int)bpl_args()->pos_dl[b * MP + p] << (2 * r);
         }
     }
+
+    // key of each of the wave's groups, and of the wave: the groups' common key if they share one (the host pairs groups of
+    // equal key into a wave: local_layout::pair_groups), else -1 = the generic body.  Constant for the kernel's lifetime.
+    int gkey[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) gkey[j] = bposd_local_keys::group_key(dl[2 * j], dl[2 * j + 1]);
+    int wkey = gkey[0];
+#pragma unroll
+    for (int j = 1; j < CPT; ++j) wkey = (gkey[j] == wkey) ? wkey : -1;
+    // instances that auto-selection takes get a loop body per key; the A/B variants run the generic body
+    constexpr bool SPEC = bpl_specialised(CPT, MPT, MINW, EARLY);
 
     const int want_llr_s = __builtin_amdgcn_readfirstlane(bpl_args()->out_llr != nullptr ? 1 : 0);
     // tested from ONE scalar register wherever it is needed (as a loop-invariant condition it became a lane mask plus a
@@ -274,10 +298,19 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
         __syncthreads();
 
         int it_done = 0;
-        bool conv = (sh[0] == 0);
-        if (!conv) {
+        int conv = __builtin_amdgcn_readfirstlane(sh[0]) == 0 ? 1 : 0;  // (an int in one scalar register, not a lane mask)
+        // The iteration loop, as a body per (KEY, LLR).  KEY >= 0: every group of the wave has this key (local_keys.h) and the
+        // bit pass is straight-line code; KEY < 0: the generic body, one switch per group on its key.  LLR: the body that
+        // stores the posterior LLRs (every iteration if out_llr is set, else the last one only); the body without them runs
+        // iterations it0 .. max_iter - 1 and holds no test of it.  Returns 1 once conv / it_done are final.  The control
+        // words are read through readfirstlane (every lane reads the same LDS word), so the exits are scalar branches.
+        auto iterate = [&](auto key_c, auto llr_c, const int it0) __attribute__((always_inline)) -> int {
+            constexpr int KEY = decltype(key_c)::value;
+            constexpr bool LLR = decltype(llr_c)::value;
+            const int max_iter = bpl_args()->max_iter;  // (read here: hoisted out of the syndrome loop it and the tests on it occupy scalar registers)
 #pragma clang loop unroll(disable)
-            for (int it = 1;; ++it) {
+            for (int it = it0; LLR || it < max_iter; ++it) {
+                asm volatile("; bpl_body key=%0 llr=%1" ::"n"(KEY), "n"((int)LLR));  // names the loop in the ISA listing (tools/isa_loop_count.py)
                 const int fi = it & 1;
                 {
                     // the wave's 64 positions of group j are one aligned pair of bitmap words: one broadcast read per group
@@ -289,11 +322,11 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                             diffw_base + (unsigned int)(((wave << 6) + j * NT) >> 3));  // (padding positions never raise their bits)
                     if (lane == 0 && mis) sh[fi] = 1;
                 }
-                if (it > P.max_iter) {
+                if (LLR && it > max_iter) {
                     __syncthreads();
-                    conv = (sh[fi] == 0);
-                    it_done = P.max_iter;
-                    break;
+                    conv = __builtin_amdgcn_readfirstlane(sh[fi]) == 0 ? 1 : 0;
+                    it_done = max_iter;
+                    return 1;
                 }
                 // =================== check -> bit pass (a4), speculative for it >= 2 ===========
                 const unsigned long long alpha_u = alpha_bits_for_iteration(P.ms_scaling, it);  // scalar instructions
@@ -363,36 +396,28 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
 #endif
                 }
                 __syncthreads();
-                if (sh[fi] == 0) {
-                    conv = true;
+                if (__builtin_amdgcn_readfirstlane(sh[fi]) == 0) {
+                    conv = 1;
                     it_done = it - 1;
-                    break;
+                    return 1;
                 }
                 if (tid == 0) sh[fi ^ 1] = 0;
                 // ============ bit pass: posterior, decision, bit -> check (a6 / a7) ============
-                const bool keep_llr = (it == P.max_iter) || want_llr();  // uniform
                 // the two LDS messages of every owned bit: all of them up front (latency hidden inside the thread), or,
-                // for the register-capped high-occupancy variant, two bits at a time
+                // for the register-capped high-occupancy variant, one group (two bits) at a time
 #ifndef BPOSD_BPL_BATCH
 #define BPOSD_BPL_BATCH 2
 #endif
                 constexpr int BATCH = (MINW >= 8 && NB > 2) ? BPOSD_BPL_BATCH : NB;
+                static_assert(BATCH % 2 == 0 && NB % BATCH == 0, "the bit pass loads the messages of whole groups");
                 double X[NB], Y[NB];
-#pragma unroll
-                for (int r = 0; r < NB; ++r) {
-                    if (r % BATCH == 0) {
-#pragma unroll
-                        for (int q = r; q < r + BATCH; ++q) {
-                            X[q] = *BPL_AT(alo[q]);
-                            Y[q] = *BPL_AT(ahi[q]);
-                        }
-                    }
+                // one owned bit with its dl (3: per lane) as a compile-time constant: sums, stores, decision update
+                auto bit_step = [&](const int r, auto dl_c) __attribute__((always_inline)) {
+                    constexpr int DL = decltype(dl_c)::value;
                     double oR, oX, oY, t;
-                    if (dl[r] == 0) bit_update<0>(BPL_L0(r), loc[r], X[r], Y[r], t, oR, oX, oY);
-                    else if (dl[r] == 1) bit_update<1>(BPL_L0(r), loc[r], X[r], Y[r], t, oR, oX, oY);
-                    else if (dl[r] == 2) bit_update<2>(BPL_L0(r), loc[r], X[r], Y[r], t, oR, oX, oY);
-                    else bit_update_mixed((int)((dlpack >> (2 * r)) & 3u), BPL_L0(r), loc[r], X[r], Y[r], t, oR, oX, oY);
-                    if (keep_llr) {
+                    if constexpr (DL == 3) bit_update_mixed((int)((dlpack >> (2 * r)) & 3u), BPL_L0(r), loc[r], X[r], Y[r], t, oR, oX, oY);
+                    else bit_update<DL>(BPL_L0(r), loc[r], X[r], Y[r], t, oR, oX, oY);
+                    if (LLR) {
                         const int bi = BPL_BIT(r);
                         if (bi >= 0) BPL_LLRT[bi] = t;
                     }
@@ -410,9 +435,63 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                         atomicXor(&diffw[cb >> 5], 1u << (cb & 31));
                         atomicXor(&diffw[co >> 5], 1u << (co & 31));
                     }
+                };
+                auto group_step = [&](const int j, auto gk_c) __attribute__((always_inline)) {
+                    constexpr int GK = decltype(gk_c)::value;
+                    bit_step(2 * j, bpl_int<bposd_local_keys::key_dl(GK, 0)>{});
+                    bit_step(2 * j + 1, bpl_int<bposd_local_keys::key_dl(GK, 1)>{});
+                };
+#pragma unroll
+                for (int j = 0; j < CPT; ++j) {
+                    if ((2 * j) % BATCH == 0) {
+#pragma unroll
+                        for (int q = 2 * j; q < 2 * j + BATCH; ++q) {
+                            X[q] = *BPL_AT(alo[q]);
+                            Y[q] = *BPL_AT(ahi[q]);
+                        }
+                    }
+                    if constexpr (KEY >= 0) group_step(j, bpl_int<KEY>{});
+                    else {
+                        switch (gkey[j]) {  // wave-uniform; both bits of the group inside one arm
+                            case 0: group_step(j, bpl_int<0>{}); break;
+                            case 1: group_step(j, bpl_int<1>{}); break;
+                            case 2: group_step(j, bpl_int<2>{}); break;
+                            case 5: group_step(j, bpl_int<5>{}); break;
+                            case 6: group_step(j, bpl_int<6>{}); break;
+                            case 10: group_step(j, bpl_int<10>{}); break;
+                            default: group_step(j, bpl_int<bposd_local_keys::kMixedKey>{}); break;
+                        }
+                    }
                 }
                 __syncthreads();
             }
+            return 0;
+        };
+        if (!conv) {
+            // the body is chosen here, once per syndrome, from a scalar register; every wave of the workgroup passes the same
+            // barriers and leaves at the same iteration whichever body it runs
+            int done = 0;  // (an int in one scalar register, not a lane mask)
+            int it_llr = 1;  // (out_llr set: every iteration stores LLRs, the LLR body runs from the start)
+            if (!want_llr()) {
+                int wk = wkey;
+                asm volatile("" : "+s"(wk));
+                if constexpr (SPEC) {
+                    switch (wk) {
+                        case 0: done = iterate(bpl_int<0>{}, bpl_int<0>{}, 1); break;
+                        case 1: done = iterate(bpl_int<1>{}, bpl_int<0>{}, 1); break;
+                        case 2: done = iterate(bpl_int<2>{}, bpl_int<0>{}, 1); break;
+                        case 5: done = iterate(bpl_int<5>{}, bpl_int<0>{}, 1); break;
+                        case 6: done = iterate(bpl_int<6>{}, bpl_int<0>{}, 1); break;
+                        case 10: done = iterate(bpl_int<10>{}, bpl_int<0>{}, 1); break;
+                        case bposd_local_keys::kMixedKey: done = iterate(bpl_int<bposd_local_keys::kMixedKey>{}, bpl_int<0>{}, 1); break;
+                        default: done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1); break;
+                    }
+                } else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1);
+                asm volatile("" : "+s"(done));
+                it_llr = bpl_args()->max_iter;
+                it_llr = it_llr > 1 ? it_llr : 1;
+            }
+            if (!done) iterate(bpl_int<-1>{}, bpl_int<1>{}, it_llr);
         }
 
         // ---- results

@@ -372,20 +372,8 @@ int build_tables_local(bposd_handle* h) {
     h->local_wcycles = best.wcycles;
 
     // ---- tables
-    const int G = MP / 64;
     const std::vector<int>&owner = best.owner, &load = best.load, &pos_of = best.pos_of, &pos_chk = best.pos_chk;
-    std::vector<int> grp_dl(2 * (size_t)G, 0);
-    for (int gq = 0; gq < G; ++gq)
-        for (int b = 0; b < 2; ++b) {
-            int code = -1;
-            for (int p = 64 * gq; p < 64 * gq + 64; ++p) {
-                const int c = pos_chk[p];
-                if (c < 0) continue;
-                const int d = g.rank_of(load[2 * c + b], c);
-                code = (code < 0 || code == d) ? d : 3;
-            }
-            grp_dl[(size_t)b * G + gq] = code < 0 ? 0 : code;
-        }
+    const std::vector<int> grp_dl = group_dl_table(g, best);
     // LDS slot of (check c, bit i) for the check's four non-local edges, ascending column order
     auto slot_of = [&](int c, int i) {
         int k = 0;
@@ -1795,6 +1783,39 @@ int bposd_debug_local_layout(const int32_t* indptr, const int32_t* indices, int3
         if (a > b) std::swap(a, b);
         out[5 + a * 3 + b]++;
     }
+    return BPOSD_OK;
+}
+
+int bposd_debug_local_keys(const int32_t* indptr, const int32_t* indices, int32_t m, int32_t n, int32_t* group_key, int32_t* pos_chk, int64_t* info) {
+    // host-only: the wave pairing of the local-edge BP kernel's layout.  group_key[MP / 64]: key of every group as the kernel
+    // forms it (local_keys.h); pos_chk[MP]: check at a position (-1: padding); info[0..2]: modelled read cycles, write cycles
+    // and mixed (group, slot) pairs of the search's layout, info[3..5]: the same after pairing, info[6]: positions MP,
+    // info[7]: waves of the two-checks-per-thread kernel (groups w and w + MP / 128) that run the generic loop body
+    if (!indptr || !indices || !group_key || !pos_chk || !info || n != 2 * m) return BPOSD_ERR_INVALID;
+    std::vector<int> rp(indptr, indptr + m + 1), ci(indices, indices + indptr[m]);
+    const int MP = m <= 1024 ? 1024 : 2048;
+    if (m > MP) return BPOSD_ERR_UNSUPPORTED;
+    for (int c = 0; c < m; ++c)
+        if (rp[c + 1] - rp[c] != 6) return BPOSD_ERR_UNSUPPORTED;
+    std::vector<int> deg(n, 0);
+    for (int e : ci) {
+        if (e < 0 || e >= n) return BPOSD_ERR_INVALID;
+        deg[e]++;
+    }
+    for (int i = 0; i < n; ++i)
+        if (deg[i] != 3) return BPOSD_ERR_UNSUPPORTED;
+    local_layout::Graph g;
+    local_layout::Layout best;
+    if (!local_layout_host(rp, ci, m, n, MP, g, best, false)) return BPOSD_ERR_UNSUPPORTED;
+    local_layout::LdsCost t = local_layout::lds_cost(g, best);
+    info[0] = t.read_cycles; info[1] = t.write_cycles; info[2] = t.mixed;
+    if (local_layout::pair_groups(g, best) < 0) return BPOSD_ERR_UNSUPPORTED;
+    t = local_layout::lds_cost(g, best);
+    info[3] = t.read_cycles; info[4] = t.write_cycles; info[5] = t.mixed;
+    info[6] = MP; info[7] = best.generic_waves;
+    const std::vector<int> keys = local_layout::group_keys(g, best);
+    for (int gq = 0; gq < MP / 64; ++gq) group_key[gq] = keys[gq];
+    for (int p = 0; p < MP; ++p) pos_chk[p] = best.pos_chk[p];
     return BPOSD_OK;
 }
 

@@ -10,6 +10,8 @@
 #include <thread>
 #include <vector>
 
+#include "local_keys.h"
+
 // ------------------------------------------------------------------ local-edge BP kernel: tables + launch
 // Every check owns two of its six bits (perfect b-matching, Kuhn's augmenting paths with capacity 2); checks are
 // grouped into 64-position groups whose slot-b bits share the position dl of the owner among the bit's checks.
@@ -21,11 +23,12 @@ struct Layout {
     std::vector<int> load;     // [2m] load[2c + b] = b-th owned bit of check c
     std::vector<int> pos_of;   // [m]  position of a check
     std::vector<int> pos_chk;  // [MP] check at a position, -1 = empty
-    int nfull = 0;             // positions [0, nfull) are class-uniform groups that the search must keep uniform
+    int nfull = 0;             // positions [0, nfull) are class-uniform groups that the search must keep uniform (before pair_groups())
     double cost = 1e30;        // read cycles + write cycles beyond their floor + 5 * mixed (group, slot) pairs (measured exchange rate)
     long long passes = 0;      // modelled ds_read_b64 cycles of the bit pass (ideal: 4 * MP / 32)
     long long wcycles = 0;     // modelled ds_write_b64 cycles of the bit pass (floor: 6 per wave-level store)
     int mixed = 0;             // (group, slot) pairs whose lanes do not share one dl
+    int generic_waves = 0;     // after pair_groups(): waves (groups w and w + MP/128) whose two groups differ in key
 };
 
 struct Graph {
@@ -340,6 +343,88 @@ inline bool rebalance_classes(const Graph& g, Layout& L, int G, int max_moves, b
     return F <= G;
 }
 
+// dl code of (group, slot b): the rank its owners share, 3 if they differ, -1 if the group holds no check
+inline int group_code(const Graph& g, const Layout& L, int gq, int b) {
+    int code = -1;
+    for (int p = 64 * gq; p < 64 * gq + 64; ++p) {
+        const int c = L.pos_chk[p];
+        if (c < 0) continue;
+        const int d = g.rank_of(L.load[2 * c + b], c);
+        code = (code < 0 || code == d) ? d : 3;
+    }
+    return code;
+}
+
+// The kernel's grp_dl table, entry b * G + group.  A group without checks (padding only: any dl computes its toy graph)
+// takes the codes of the group it shares a wave with, so that it does not cost the wave its specialised loop body.
+inline std::vector<int> group_dl_table(const Graph& g, const Layout& L) {
+    const int G = g.MP / 64;
+    std::vector<int> t(2 * (size_t)G, 0);
+    for (int gq = 0; gq < G; ++gq)
+        for (int b = 0; b < 2; ++b) {
+            int code = group_code(g, L, gq, b);
+            if (code < 0) code = group_code(g, L, (gq + G / 2) % G, b);
+            t[(size_t)b * G + gq] = code < 0 ? 0 : code;
+        }
+    return t;
+}
+
+// key (local_keys.h) of every group as the kernel derives it from grp_dl
+inline std::vector<int> group_keys(const Graph& g, const Layout& L) {
+    const int G = g.MP / 64;
+    const std::vector<int> t = group_dl_table(g, L);
+    std::vector<int> k(G);
+    for (int gq = 0; gq < G; ++gq) k[gq] = bposd_local_keys::group_key(t[gq], t[(size_t)G + gq]);
+    return k;
+}
+
+// Wave pairing.  With two checks per thread a wave runs groups w and w + G/2; it runs a loop body without any decision on
+// dl if the two have the same key.  Whole groups are permuted so that equal keys share a wave: every position moves by a
+// multiple of 64, so every column mod 32 and mod 16 of the bank model -- the LDS cost the search has minimised -- and every
+// group's content stay what they are.  Groups left over (one per key with an odd count) first take an empty group as
+// partner, then one another: those waves run the generic body.  Returns their number.
+inline int pair_groups(const Graph& g, Layout& L) {
+    const int G = g.MP / 64, W = G / 2;
+    std::vector<int> key(G);
+    for (int gq = 0; gq < G; ++gq) {
+        const int c0 = group_code(g, L, gq, 0), c1 = group_code(g, L, gq, 1);
+        key[gq] = c0 < 0 ? -1 : bposd_local_keys::group_key(c0, c1);
+    }
+    std::vector<std::pair<int, int>> pairs;  // (group of wave w, group of wave w + W)
+    std::vector<int> singles, empties;
+    std::vector<char> used(G, 0);
+    for (int gq = 0; gq < G; ++gq) {
+        if (used[gq]) continue;
+        if (key[gq] < 0) { empties.push_back(gq); used[gq] = 1; continue; }
+        int mate = -1;
+        for (int q = gq + 1; q < G && mate < 0; ++q)
+            if (!used[q] && key[q] == key[gq]) mate = q;
+        used[gq] = 1;
+        if (mate < 0) { singles.push_back(gq); continue; }
+        used[mate] = 1;
+        pairs.push_back({gq, mate});
+    }
+    int generic = 0;
+    size_t e = 0, s1 = 0;
+    for (; s1 < singles.size() && e < empties.size(); ++s1, ++e) pairs.push_back({std::min(singles[s1], empties[e]), std::max(singles[s1], empties[e])});
+    for (; s1 + 1 < singles.size(); s1 += 2, ++generic) pairs.push_back({singles[s1], singles[s1 + 1]});
+    for (; e + 1 < empties.size(); e += 2) pairs.push_back({empties[e], empties[e + 1]});
+    if ((int)pairs.size() != W) return -1;  // (G is even, so every group has a partner)
+    std::sort(pairs.begin(), pairs.end());
+    std::vector<int> new_of(G);
+    for (int w = 0; w < W; ++w) { new_of[pairs[w].first] = w; new_of[pairs[w].second] = w + W; }
+    std::vector<int> pos_chk(g.MP, -1);
+    for (int p = 0; p < g.MP; ++p) {
+        const int c = L.pos_chk[p];
+        const int q = 64 * new_of[p >> 6] + (p & 63);
+        pos_chk[q] = c;
+        if (c >= 0) L.pos_of[c] = q;
+    }
+    L.pos_chk = pos_chk;
+    L.generic_waves = generic;
+    return generic;
+}
+
 }  // namespace local_layout
 
 // Every check owns two of its six bits; positions are chosen so that (a) as many 64-position groups as possible
@@ -351,8 +436,9 @@ inline bool rebalance_classes(const Graph& g, Layout& L, int G, int max_moves, b
 // every group mixed, and measured on the GPU a mixed pair costs as much as five extra passes: 36.3 ms against 29.8.)
 // Host-only part: ownership assignment + positions for a (3,6)-regular code with n = 2m (rp / ci: CSR of the pcm).
 // Returns false when no perfect assignment exists.
+// pair: finish with pair_groups() (the tables the kernel runs with); false gives the search's own result.
 inline bool local_layout_host(const std::vector<int>& rp, const std::vector<int>& ci, int m, int n, int MP,
-                              local_layout::Graph& g, local_layout::Layout& best) {
+                              local_layout::Graph& g, local_layout::Layout& best, bool pair = true) {
     using namespace local_layout;
     g.m = m; g.n = n; g.MP = MP;
     g.cols.assign(3 * (size_t)n, 0);
@@ -477,6 +563,14 @@ inline bool local_layout_host(const std::vector<int>& rp, const std::vector<int>
                         fin[q].wcycles, fin[q].mixed);
             if (q == 0 || total(fin[q]) < total(best)) best = fin[q];
         }
+    }
+    if (pair) {
+        if (pair_groups(g, best) < 0) return false;
+        const LdsCost t = lds_cost(g, best);  // (what the search returned: the permutation changes none of the three)
+        best.passes = t.read_cycles;
+        best.wcycles = t.write_cycles;
+        best.mixed = t.mixed;
+        if (getenv("BPOSD_DEBUG_OCC")) fprintf(stderr, "[bposd] wave pairing: %d generic wave(s) of %d\n", best.generic_waves, MP / 128);
     }
     return true;
 }

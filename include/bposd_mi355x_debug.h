@@ -50,6 +50,14 @@ int bposd_debug_last_instance(bposd_handle *h, int32_t bp[6], int32_t osd[6]);
  * ds_write_b64 cycles of one bit pass, their floor. */
 int bposd_debug_local_layout(const int32_t *csr_indptr, const int32_t *csr_indices, int32_t m, int32_t n, int64_t *out);
 
+/* Diagnostics, host only: the wave pairing of that layout.  The two-checks-per-thread kernels run groups w and w + MP / 128
+ * in wave w; groups of equal key (4 * dl(slot 0) + dl(slot 1), 15 = a slot whose lanes differ) are moved into the same wave,
+ * which then runs a loop body compiled for that key.  group_key [MP / 64], pos_chk [MP] (check at a position, -1 padding),
+ * info[8]: modelled read cycles, write cycles, mixed (group, slot) pairs before the pairing; the same three after it (equal);
+ * positions MP; waves whose two groups differ in key (they run the generic body). */
+int bposd_debug_local_keys(const int32_t *csr_indptr, const int32_t *csr_indices, int32_t m, int32_t n, int32_t *group_key,
+                           int32_t *pos_chk, int64_t *info);
+
 /* Diagnostics, host only: the tables bp_class_kernel would run with for a pcm whose check and bit degrees fall inside one
  * compiled instance -- (check degrees; bit degrees) = (7; 3..4), (6; 3), (4; 2), (8; 4), (3..4; 1..2) -- and
  * BPOSD_ERR_UNSUPPORTED otherwise.  info[11]: highest check degree, lowest / highest bit degree, bit slots per thread, LDS
