@@ -63,6 +63,8 @@ DEBUG_SYMBOLS = (
     "bposd_bp_kernel_info",
     "bposd_debug_local_layout",
     "bposd_debug_local_keys",
+    "bposd_debug_local_waves",
+    "bposd_debug_last_pair_key",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
 )
@@ -177,6 +179,10 @@ def load():
     lib.bposd_debug_local_layout.restype = C.c_int
     lib.bposd_debug_local_keys.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
     lib.bposd_debug_local_keys.restype = C.c_int
+    lib.bposd_debug_local_waves.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]
+    lib.bposd_debug_local_waves.restype = C.c_int
+    lib.bposd_debug_last_pair_key.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.bposd_debug_last_pair_key.restype = C.c_int
     lib.bposd_debug_class_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.bposd_debug_class_layout.restype = C.c_int
     lib.bposd_debug_last_instance.argtypes = [vp, vp, vp]

@@ -17,8 +17,10 @@
 // straight-line code, instruction for instruction the arithmetic of bp_kernel; 3: a mixed group, the operands are
 // routed by per-lane selects), so it is decided once, outside the iteration loop: the loop exists as one body per
 // key of a group's two codes (local_keys.h), the host puts groups of equal key into the same wave, and a wave whose
-// groups differ runs a generic body with one switch per group.  The position count MP is a compile-time power of
-// two, as in bp_kernel, so LDS offsets are instruction immediates.
+// groups differ runs a generic body with one switch per group -- except the wave (uniform key PAIRKEY, mixed group) of an
+// instance compiled with that PAIRKEY, which has a straight-line body of its own (the host launches the instance its
+// layout's wave table asks for).  The position count MP is a compile-time power of two, as in bp_kernel, so LDS offsets
+// are instruction immediates.
 //
 // Everything else -- persistent workgroups on an atomic queue, in-place messages, incremental convergence
 // bitmap with a speculative check pass, outputs, OSD hand-off -- is the scheme of bp_kernel.hip.h (rows a3-a7).
@@ -155,10 +157,14 @@ __host__ __device__ constexpr bool bpl_specialised(int cpt, int mpt, int minw, b
 // UPRIOR: every bit has the same prior (uniform channel, no per-shot channel): it lives in a scalar register pair
 // PACKED: the packed-I/O form (BpLocalParams::packed_io) as a compile-time switch: the byte form is then instruction for
 // instruction what it was before the packed form existed (as a run-time switch it cost the headline launch 1.2 %, same-box A/B)
-template <int CPT, int MPT, int MINW, bool EARLY, bool UPRIOR, bool PACKED = false>
+// PAIRKEY: -1, or the uniform key k of the one (k, mixed) wave this instance has a loop body for (local_keys.h: pair keys).
+// The host picks the instance from the layout's wave table; any other wave of unequal groups runs the generic body.
+template <int CPT, int MPT, int MINW, bool EARLY, bool UPRIOR, bool PACKED = false, int PAIRKEY = -1>
 __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocalParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int m = P.m, n = P.n;
+    // (a PAIRKEY instance reads m and n where they are used, like the other per-syndrome arguments: held next to B as one
+    // four-dword load, the byte form's register allocation left a dead 16-byte spill slot behind -- a private segment)
+    const int m = PAIRKEY >= 0 ? bpl_args()->m : P.m, n = PAIRKEY >= 0 ? bpl_args()->n : P.n;
 #ifdef BPOSD_DEBUG
     if (blockIdx.x == 0 && threadIdx.x == 0 && (bpl_args()->m != P.m || bpl_args()->counters != P.counters)) __builtin_trap();
 #endif
@@ -224,6 +230,11 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
     int wkey = gkey[0];
 #pragma unroll
     for (int j = 1; j < CPT; ++j) wkey = (gkey[j] == wkey) ? wkey : -1;
+    constexpr int PKEY = bposd_local_keys::pair_key(PAIRKEY);  // -1: the instance has no pair body
+    static_assert(PKEY < 0 || (CPT == 2 && bpl_specialised(CPT, MPT, MINW, EARLY)), "a pair body is for two groups per wave");
+    if constexpr (PKEY >= 0) {
+        if (gkey[0] == PAIRKEY && gkey[CPT - 1] == bposd_local_keys::kMixedKey) wkey = PKEY;
+    }
     // instances that auto-selection takes get a loop body per key; the A/B variants run the generic body
     constexpr bool SPEC = bpl_specialised(CPT, MPT, MINW, EARLY);
 
@@ -300,7 +311,8 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
         int it_done = 0;
         int conv = __builtin_amdgcn_readfirstlane(sh[0]) == 0 ? 1 : 0;  // (an int in one scalar register, not a lane mask)
         // The iteration loop, as a body per (KEY, LLR).  KEY >= 0: every group of the wave has this key (local_keys.h) and the
-        // bit pass is straight-line code; KEY < 0: the generic body, one switch per group on its key.  LLR: the body that
+        // bit pass is straight-line code (a pair key: group 0 has the uniform key, group 1 the mixed one); KEY < 0: the generic
+        // body, one switch per group on its key.  LLR: the body that
         // stores the posterior LLRs (every iteration if out_llr is set, else the last one only); the body without them runs
         // iterations it0 .. max_iter - 1 and holds no test of it.  Returns 1 once conv / it_done are final.  The control
         // words are read through readfirstlane (every lane reads the same LDS word), so the exits are scalar branches.
@@ -450,8 +462,10 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                             Y[q] = *BPL_AT(ahi[q]);
                         }
                     }
-                    if constexpr (KEY >= 0) group_step(j, bpl_int<KEY>{});
-                    else {
+                    if constexpr (KEY >= 0) {
+                        if (j == 0) group_step(j, bpl_int<bposd_local_keys::body_group_key(KEY, 0)>{});
+                        else group_step(j, bpl_int<bposd_local_keys::body_group_key(KEY, 1)>{});
+                    } else {
                         switch (gkey[j]) {  // wave-uniform; both bits of the group inside one arm
                             case 0: group_step(j, bpl_int<0>{}); break;
                             case 1: group_step(j, bpl_int<1>{}); break;
@@ -484,7 +498,10 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                         case 6: done = iterate(bpl_int<6>{}, bpl_int<0>{}, 1); break;
                         case 10: done = iterate(bpl_int<10>{}, bpl_int<0>{}, 1); break;
                         case bposd_local_keys::kMixedKey: done = iterate(bpl_int<bposd_local_keys::kMixedKey>{}, bpl_int<0>{}, 1); break;
-                        default: done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1); break;
+                        default:  // the instance's pair key, if it has one; else the generic body
+                            if (PKEY >= 0 && wk == PKEY) done = iterate(bpl_int<(PKEY >= 0 ? PKEY : -1)>{}, bpl_int<0>{}, 1);
+                            else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1);
+                            break;
                     }
                 } else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1);
                 asm volatile("" : "+s"(done));

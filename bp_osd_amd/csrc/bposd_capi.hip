@@ -373,7 +373,14 @@ int build_tables_local(bposd_handle* h) {
 
     // ---- tables
     const std::vector<int>&owner = best.owner, &load = best.load, &pos_of = best.pos_of, &pos_chk = best.pos_chk;
-    const std::vector<int> grp_dl = group_dl_table(g, best);
+    const WavePlan plan = wave_plan(g, best, pair_mode());  // which body every wave runs; the instance that has them
+    const std::vector<int>& grp_dl = plan.grp_dl;
+    h->local_pair_key = plan.pair_key;
+    if (getenv("BPOSD_DEBUG_OCC")) {
+        fprintf(stderr, "[bposd] wave bodies (-1 generic):");
+        for (int b : plan.body) fprintf(stderr, " %d", b);
+        fprintf(stderr, "; instance PAIRKEY %d, %d generic wave(s)\n", plan.pair_key, plan.generic);
+    }
     // LDS slot of (check c, bit i) for the check's four non-local edges, ascending column order
     auto slot_of = [&](int c, int i) {
         int k = 0;
@@ -1024,6 +1031,12 @@ int bposd_debug_last_instance(bposd_handle* h, int32_t bp[6], int32_t osd[6]) {
     if (!h) return BPOSD_ERR_INVALID;
     if (bp) std::copy(h->last_bp_inst, h->last_bp_inst + 6, bp);
     if (osd) std::copy(h->last_osd_inst, h->last_osd_inst + 6, osd);
+    return BPOSD_OK;
+}
+
+int bposd_debug_last_pair_key(bposd_handle* h, int32_t* pair_key) {
+    if (!h || !pair_key) return BPOSD_ERR_INVALID;
+    *pair_key = h->last_bp_inst[0] == BPOSD_BP_KERNEL_LOCAL ? h->last_bp_pair_key : -1;
     return BPOSD_OK;
 }
 
@@ -1816,6 +1829,34 @@ int bposd_debug_local_keys(const int32_t* indptr, const int32_t* indices, int32_
     const std::vector<int> keys = local_layout::group_keys(g, best);
     for (int gq = 0; gq < MP / 64; ++gq) group_key[gq] = keys[gq];
     for (int p = 0; p < MP; ++p) pos_chk[p] = best.pos_chk[p];
+    return BPOSD_OK;
+}
+
+int bposd_debug_local_waves(const int32_t* indptr, const int32_t* indices, int32_t m, int32_t n, int32_t* wave_body, int64_t* info) {
+    // host-only: which loop body every wave of the two-checks-per-thread kernels runs (local_layout::wave_plan) and the
+    // instance that holds them.  wave_body[MP / 128]: one of the seven group keys, a pair key (local_keys.h), -1 = generic;
+    // info[0] positions MP, info[1] PAIRKEY of the instance the host launches (-1: the plain one), info[2] waves on the
+    // generic body, info[3] the mode (0 generic, 1 demotion, 2 pair body)
+    if (!indptr || !indices || !wave_body || !info || n != 2 * m) return BPOSD_ERR_INVALID;
+    std::vector<int> rp(indptr, indptr + m + 1), ci(indices, indices + indptr[m]);
+    const int MP = m <= 1024 ? 1024 : 2048;
+    if (m > MP) return BPOSD_ERR_UNSUPPORTED;
+    for (int c = 0; c < m; ++c)
+        if (rp[c + 1] - rp[c] != 6) return BPOSD_ERR_UNSUPPORTED;
+    std::vector<int> deg(n, 0);
+    for (int e : ci) {
+        if (e < 0 || e >= n) return BPOSD_ERR_INVALID;
+        deg[e]++;
+    }
+    for (int i = 0; i < n; ++i)
+        if (deg[i] != 3) return BPOSD_ERR_UNSUPPORTED;
+    local_layout::Graph g;
+    local_layout::Layout best;
+    if (!local_layout_host(rp, ci, m, n, MP, g, best)) return BPOSD_ERR_UNSUPPORTED;
+    const local_layout::PairMode mode = local_layout::pair_mode();
+    const local_layout::WavePlan plan = local_layout::wave_plan(g, best, mode);
+    for (int w = 0; w < MP / 128; ++w) wave_body[w] = plan.body[w];
+    info[0] = MP; info[1] = plan.pair_key; info[2] = plan.generic; info[3] = (int)mode;
     return BPOSD_OK;
 }
 

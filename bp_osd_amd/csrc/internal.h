@@ -117,6 +117,8 @@ struct bposd_handle {
     int last_osd_kernel = -1; // 0 none yet, 1 osd_kernel, 2 osd_wave_kernel, 3 osd_large_kernel
     int32_t last_bp_inst[6] = {-1, 0, 0, 0, 0, 0};   // bposd_debug_last_instance: the instance the last launch_* template launched
     int32_t last_osd_inst[6] = {-1, 0, 0, 0, 0, 0};
+    int local_pair_key = -1;    // PAIRKEY of the bp_local_kernel instance this layout's (uniform, mixed) wave wants (local_layout::wave_plan), -1 none
+    int last_bp_pair_key = -1;  // bposd_debug_last_pair_key: PAIRKEY of the last bp_local_kernel launch (-1: the plain instance)
     // host copies
     std::vector<int> rp, ci;
     std::vector<double> probs;

@@ -1,0 +1,41 @@
+// launch_bp_local.h -- the launch of one bp_local_kernel instance, shared by the translation units that instantiate the
+// family: launch_bp_local.hip (the plain instances and the dispatch) and launch_bp_local_pair_k*.hip (the instances with a
+// body for one (uniform key, mixed) wave, one unit per key so that no unit compiles longer than the plain one).
+#pragma once
+#include "internal.h"
+
+#include "bp_local_kernel.hip.h"
+
+namespace bposd_host {
+
+template <int CPT, int MP, int MINW, bool EARLY, bool UPRIOR, bool PACKED, int PAIRKEY = -1>
+static int launch_bp_local_tp(bposd_handle* h, const bposd::BpLocalParams& L) {
+    using namespace bposd;
+    auto k = bp_local_kernel<CPT, MP, MINW, EARLY, UPRIOR, PACKED, PAIRKEY>;
+    const int nt = MP / CPT;
+    const size_t lds = bp_local_lds_bytes(L.mp);
+    { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; }
+    int wg_per_cu = 1;
+    { int rc_occ = cached_occupancy(h, (const void*)k, nt, lds, &wg_per_cu); if (rc_occ) return rc_occ; }
+    if (getenv("BPOSD_DEBUG_OCC")) fprintf(stderr, "[bposd] local-edge BP kernel: %d threads, %zu B LDS, %d workgroups per CU, PAIRKEY %d\n", nt, lds, wg_per_cu, PAIRKEY);
+    wg_per_cu = std::max(1, std::min(wg_per_cu, 8));
+    long long grid = std::min<long long>(L.B, (long long)h->num_cu * wg_per_cu);
+    if (grid < 1) grid = 1;
+    int rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n);
+    if (rc) return rc;
+    BpLocalParams Lq = L;
+    Lq.llr_tmp = (double*)h->cur->bpl_llr.p;
+    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LOCAL, CPT, MP, MINW, EARLY, PACKED);
+    h->last_bp_pair_key = PAIRKEY;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, h->cur->stream, Lq);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// The instances with a pair body exist for the two-checks-per-thread shapes auto-selection takes, byte and packed forms:
+enum BplPairShape { kBplPair1024x8U = 0, kBplPair1024x6 = 1, kBplPair2048x4 = 2 };  // <2,1024,8,false,true> <2,1024,6,false,false> <2,2048,4,false,false>
+// defined in launch_bp_local_pair_k<KEY>.hip for the six uniform keys of local_keys.h
+template <int KEY>
+int launch_bp_local_pair(bposd_handle* h, const bposd::BpLocalParams& L, int shape);
+
+}  // namespace bposd_host

@@ -1,16 +1,11 @@
 // launch_bp_local.hip -- bp_local_kernel ((3,6)-regular codes with n = 2m, min-sum): launch
 // One translation unit of libbposd_mi355x.so: the kernels of this family are instantiated here and nowhere else.
-#include "internal.h"
-
-#include "bp_local_kernel.hip.h"
+#include "launch_bp_local.h"
 
 using namespace bposd;
 using namespace bposd_host;
 
 namespace bposd_host {
-template <int CPT, int MP, int MINW, bool EARLY, bool UPRIOR, bool PACKED>
-static int launch_bp_local_tp(bposd_handle* h, const BpLocalParams& L);
-
 // the packed-I/O form exists for the instances auto-selection takes (internal.h: native_packed() asks for bp_variant == 0)
 template <int CPT, int MP, int MINW, bool EARLY, bool UPRIOR = false>
 static int launch_bp_local_t(bposd_handle* h, const BpLocalParams& L) {
@@ -23,26 +18,17 @@ static int launch_bp_local_t(bposd_handle* h, const BpLocalParams& L) {
     return launch_bp_local_tp<CPT, MP, MINW, EARLY, UPRIOR, false>(h, L);
 }
 
-template <int CPT, int MP, int MINW, bool EARLY, bool UPRIOR, bool PACKED>
-static int launch_bp_local_tp(bposd_handle* h, const BpLocalParams& L) {
-    auto k = bp_local_kernel<CPT, MP, MINW, EARLY, UPRIOR, PACKED>;
-    const int nt = MP / CPT;
-    const size_t lds = bp_local_lds_bytes(L.mp);
-    { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; }
-    int wg_per_cu = 1;
-    { int rc_occ = cached_occupancy(h, (const void*)k, nt, lds, &wg_per_cu); if (rc_occ) return rc_occ; }
-    if (getenv("BPOSD_DEBUG_OCC")) fprintf(stderr, "[bposd] local-edge BP kernel: %d threads, %zu B LDS, %d workgroups per CU\n", nt, lds, wg_per_cu);
-    wg_per_cu = std::max(1, std::min(wg_per_cu, 8));
-    long long grid = std::min<long long>(L.B, (long long)h->num_cu * wg_per_cu);
-    if (grid < 1) grid = 1;
-    int rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n);
-    if (rc) return rc;
-    BpLocalParams Lq = L;
-    Lq.llr_tmp = (double*)h->cur->bpl_llr.p;
-    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LOCAL, CPT, MP, MINW, EARLY, PACKED);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, h->cur->stream, Lq);
-    HIP_TRY(h, hipGetLastError());
-    return 0;
+// the instance whose pair body serves this layout's (uniform key, mixed) wave, for the shapes auto-selection takes
+static int launch_bp_local_pair_any(bposd_handle* h, const BpLocalParams& L, int shape) {
+    switch (h->local_pair_key) {
+        case 0: return launch_bp_local_pair<0>(h, L, shape);
+        case 1: return launch_bp_local_pair<1>(h, L, shape);
+        case 2: return launch_bp_local_pair<2>(h, L, shape);
+        case 5: return launch_bp_local_pair<5>(h, L, shape);
+        case 6: return launch_bp_local_pair<6>(h, L, shape);
+        case 10: return launch_bp_local_pair<10>(h, L, shape);
+    }
+    return fail(h, BPOSD_ERR_UNSUPPORTED, "no bp_local_kernel instance with a pair body for key %d", h->local_pair_key);
 }
 
 int launch_bp_local(bposd_handle* h, const BpParams& P) {
@@ -54,7 +40,10 @@ int launch_bp_local(bposd_handle* h, const BpParams& P) {
     L.grp_dl = h->d_lgrp_dl; L.pos_dl = h->d_lpos_dl;
     L.out_bp = P.out_bp; L.out_osd0 = P.out_osd0; L.out_osdw = P.out_osdw; L.out_conv = P.out_conv; L.out_iters = P.out_iters;
     L.out_llr = P.out_llr; L.llr_ws = P.llr_ws; L.osd_list = P.osd_list; L.counters = P.counters; L.iter_total = P.iter_total; L.tail_flag = P.tail_flag; L.packed_io = P.packed_io;
-    if (h->local_mp == 2048) return launch_bp_local_t<2, 2048, 4, false>(h, L);  // 1024 threads, one workgroup per CU
+    // auto-selection launches the instance that has a body for the layout's (uniform key, mixed) wave, if it has one; a
+    // variant asked for by number is the plain instance (generic body for that wave)
+    const bool pair = h->bp_variant == 0 && h->local_pair_key >= 0;
+    if (h->local_mp == 2048) return pair ? launch_bp_local_pair_any(h, L, kBplPair2048x4) : launch_bp_local_t<2, 2048, 4, false>(h, L);  // 1024 threads, one workgroup per CU
     if (h->bp_variant == 17) return launch_bp_local_t<2, 1024, 8, false>(h, L);   // 512 threads, <= 64 VGPRs: 4 workgroups per CU
     if (h->bp_variant == 18) return launch_bp_local_t<1, 1024, 8, false>(h, L);   // 1024 threads, <= 64 VGPRs: 2 workgroups per CU
     if (h->bp_variant == 19) return launch_bp_local_t<4, 1024, 4, true>(h, L);    // 256 threads, <= 128 VGPRs: 4 workgroups per CU
@@ -69,6 +58,7 @@ int launch_bp_local(bposd_handle* h, const BpParams& P) {
     const long long work = h->batch_hint > 0 ? h->batch_hint : L.B;
     const bool small_call = h->bp_variant == 0 && work <= 40000;
     if (small_call) return uprior ? launch_bp_local_t<1, 1024, 8, false, true>(h, L) : launch_bp_local_t<1, 1024, 8, false>(h, L);
+    if (pair) return launch_bp_local_pair_any(h, L, uprior ? kBplPair1024x8U : kBplPair1024x6);
     if ((h->bp_variant == 22 || h->bp_variant == 0) && uprior) return launch_bp_local_t<2, 1024, 8, false, true>(h, L);  // <= 64 VGPRs: 4 workgroups per CU
     if (h->bp_variant == 23 && uprior) return launch_bp_local_t<2, 1024, 6, true, true>(h, L);
     if (h->bp_variant == 24 && uprior) return launch_bp_local_t<2, 1024, 6, false, true>(h, L);

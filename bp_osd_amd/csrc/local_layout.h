@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <thread>
 #include <vector>
@@ -382,7 +383,8 @@ inline std::vector<int> group_keys(const Graph& g, const Layout& L) {
 // dl if the two have the same key.  Whole groups are permuted so that equal keys share a wave: every position moves by a
 // multiple of 64, so every column mod 32 and mod 16 of the bank model -- the LDS cost the search has minimised -- and every
 // group's content stay what they are.  Groups left over (one per key with an odd count) first take an empty group as
-// partner, then one another: those waves run the generic body.  Returns their number.
+// partner, then one another: those are the waves whose two groups differ in key (wave_plan() says which loop body each of them
+// runs).  Returns their number.
 inline int pair_groups(const Graph& g, Layout& L) {
     const int G = g.MP / 64, W = G / 2;
     std::vector<int> key(G);
@@ -407,6 +409,9 @@ inline int pair_groups(const Graph& g, Layout& L) {
     int generic = 0;
     size_t e = 0, s1 = 0;
     for (; s1 < singles.size() && e < empties.size(); ++s1, ++e) pairs.push_back({std::min(singles[s1], empties[e]), std::max(singles[s1], empties[e])});
+    // (a mixed group goes second, into wave w + W: the order the kernels' pair bodies are compiled for -- local_keys.h)
+    if (singles.size() - s1 >= 2)
+        std::stable_sort(singles.begin() + s1, singles.end(), [&](int a, int b) { return (key[a] == bposd_local_keys::kMixedKey) < (key[b] == bposd_local_keys::kMixedKey); });
     for (; s1 + 1 < singles.size(); s1 += 2, ++generic) pairs.push_back({singles[s1], singles[s1 + 1]});
     for (; e + 1 < empties.size(); e += 2) pairs.push_back({empties[e], empties[e + 1]});
     if ((int)pairs.size() != W) return -1;  // (G is even, so every group has a partner)
@@ -423,6 +428,59 @@ inline int pair_groups(const Graph& g, Layout& L) {
     L.pos_chk = pos_chk;
     L.generic_waves = generic;
     return generic;
+}
+
+// What the waves of a paired layout run in the two-checks-per-thread kernels.  A wave whose two groups have the same key runs
+// that key's loop body.  For a wave (uniform key k, mixed group) there are three choices (BPOSD_PAIR_MODE, for A/B runs):
+//   kPairBody    (default) the kernel instance compiled with PAIRKEY = k runs a body of its own for it: group 0 straight-line
+//                code for k, group 1 the per-lane selects.  An instance has one such body, so the layout's most frequent k (the
+//                lowest on a tie) is served; a wave with another k, and any wave of two different uniform keys, stays generic.
+//   kPairDemote  the uniform group is handed to the kernel as mixed (grp_dl = 3 in both slots; pos_dl carries the per-lane
+//                codes anyway): the wave has key 15 and runs the mixed body.  Tables only; the model and a group's own key
+//                (group_keys) are unchanged.
+//   kPairGeneric the generic body (one switch per group and iteration).
+enum PairMode { kPairGeneric = 0, kPairDemote = 1, kPairBody = 2 };
+inline PairMode pair_mode() {
+    if (const char* e = getenv("BPOSD_PAIR_MODE")) {
+        if (!strcmp(e, "generic")) return kPairGeneric;
+        if (!strcmp(e, "demote")) return kPairDemote;
+        if (!strcmp(e, "body")) return kPairBody;
+    }
+    return kPairBody;
+}
+
+struct WavePlan {
+    std::vector<int> grp_dl;  // the kernel's table (group_dl_table, with the demoted groups' codes set to 3)
+    std::vector<int> body;    // [MP / 128] loop body of wave w: one of the seven keys, a pair key, or -1 = the generic body
+    int pair_key = -1;        // PAIRKEY of the instance to launch (-1: the plain instance)
+    int generic = 0;          // waves that run the generic body
+};
+
+inline WavePlan wave_plan(const Graph& g, const Layout& L, PairMode mode) {
+    using namespace bposd_local_keys;
+    const int G = g.MP / 64, W = G / 2;
+    WavePlan P;
+    P.grp_dl = group_dl_table(g, L);
+    P.body.assign(W, -1);
+    std::vector<int> key(G);
+    for (int gq = 0; gq < G; ++gq) key[gq] = group_key(P.grp_dl[gq], P.grp_dl[(size_t)G + gq]);
+    if (mode == kPairBody) {
+        int count[kMixedKey] = {0};
+        for (int w = 0; w < W; ++w)
+            if (key[w] != kMixedKey && key[w + W] == kMixedKey) count[key[w]]++;
+        for (int k = 0; k < kMixedKey; ++k)
+            if (count[k] > (P.pair_key < 0 ? 0 : count[P.pair_key])) P.pair_key = k;
+    }
+    for (int w = 0; w < W; ++w) {
+        const int a = key[w], b = key[w + W];
+        if (a == b) P.body[w] = a;
+        else if (mode == kPairDemote && (a == kMixedKey || b == kMixedKey)) {
+            for (int s = 0; s < 2; ++s) P.grp_dl[(size_t)s * G + w] = P.grp_dl[(size_t)s * G + w + W] = 3;
+            P.body[w] = kMixedKey;
+        } else if (mode == kPairBody && a == P.pair_key && b == kMixedKey) P.body[w] = pair_key(a);
+        P.generic += P.body[w] < 0;
+    }
+    return P;
 }
 
 }  // namespace local_layout
@@ -546,6 +604,11 @@ inline bool local_layout_host(const std::vector<int>& rp, const std::vector<int>
             rank.push_back({total(cands[k]), k});
         }
         std::sort(rank.begin(), rank.end());
+        // BPOSD_LAYOUT_PIN=k: candidate k and no other (measurements: what a layout the ranking does not choose runs at)
+        if (const char* e = getenv("BPOSD_LAYOUT_PIN")) {
+            const size_t k = (size_t)atoi(e);
+            if (k < cands.size()) rank.assign(1, {total(cands[k]), k});
+        }
         const size_t nfinish = std::min(rank.size(), getenv("BPOSD_LAYOUT_ALL") ? rank.size() : (size_t)3);
         // (0.4 M steps: 218 + 408 modelled cycles in 1.1 s; 1 M: 210 + 401 in 1.3 s; 2 M: 208 + 402 in 2.6 s -- and no measurable difference
         // in launch time between the three, same-box A/B of round 4: 26.1 +- 0.15 ms each)

@@ -640,6 +640,13 @@ class BpOsdDecoder:
         return {"bp": entry(bp, self.BP_KERNEL_NAMES, self._BP_INSTANCE_ARITY),
                 "osd": entry(osd, self.OSD_KERNEL_NAMES, self._OSD_INSTANCE_ARITY)}
 
+    def last_pair_key(self) -> int:
+        """PAIRKEY of the bp_local_kernel instance the last BP launch ran (the uniform key of the wave it has a pair body
+        for, csrc/local_keys.h); -1 for the plain instance and for every other kernel."""
+        k = C.c_int32(-1)
+        _lib.check(self._lib, self._h, self._lib.bposd_debug_last_pair_key(self._h, C.byref(k)))
+        return int(k.value)
+
     def set_bp_variant(self, variant: int):
         """Tuning / test knob: 0 auto; 1, 2, 4 LDS kernel shapes; 16 .. 26 local-edge kernel; 32 class kernel; 63 HBM-resident min-sum with whole check records in the workspace; 64 any-degree kernel (slow; cross-checks) -- see the C header."""
         _lib.check(self._lib, self._h, self._lib.bposd_set_bp_variant(self._h, int(variant)))

@@ -58,6 +58,19 @@ int bposd_debug_local_layout(const int32_t *csr_indptr, const int32_t *csr_indic
 int bposd_debug_local_keys(const int32_t *csr_indptr, const int32_t *csr_indices, int32_t m, int32_t n, int32_t *group_key,
                            int32_t *pos_chk, int64_t *info);
 
+/* Diagnostics, host only: which loop body every wave of that pairing runs.  A wave whose groups share a key runs that key's
+ * body; a wave (uniform key k, mixed group) runs the pair body 32 + k of the kernel instance compiled with PAIRKEY = k, which
+ * the host then launches (one k per instance: the layout's most frequent); every other wave of unequal groups runs the generic
+ * body.  wave_body [MP / 128]: a group key, a pair key, or -1 (generic).  info[4]: positions MP; PAIRKEY of the instance
+ * (-1: the plain one); waves on the generic body; mode (2 pair body; 0 generic / 1 uniform group demoted to mixed are
+ * measurement settings of BPOSD_PAIR_MODE). */
+int bposd_debug_local_waves(const int32_t *csr_indptr, const int32_t *csr_indices, int32_t m, int32_t n, int32_t *wave_body,
+                            int64_t *info);
+
+/* Diagnostics: PAIRKEY of the bp_local_kernel instance the last BP launch of this handle ran; -1 for the plain instance and
+ * after a launch of another kernel family. */
+int bposd_debug_last_pair_key(bposd_handle *h, int32_t *pair_key);
+
 /* Diagnostics, host only: the tables bp_class_kernel would run with for a pcm whose check and bit degrees fall inside one
  * compiled instance -- (check degrees; bit degrees) = (7; 3..4), (6; 3), (4; 2), (8; 4), (3..4; 1..2) -- and
  * BPOSD_ERR_UNSUPPORTED otherwise.  info[11]: highest check degree, lowest / highest bit degree, bit slots per thread, LDS

@@ -40,5 +40,18 @@ int main(int argc, char** argv) {
     const local_layout::LdsCost c = local_layout::lds_cost(g, best);
     printf("layout: %.2f s, read cycles %d (ideal %d), write cycles %d (ideal %d), mixed (group, slot) pairs %d, uniform positions %d\n", sec,
            c.read_cycles, 4 * (MP / 32), c.write_cycles, 6 * 4 * (MP / 64), c.mixed, best.nfull);
+    // the wave table of the two-checks-per-thread kernels: groups w and w + MP / 128 with their keys (local_keys.h) and real
+    // (non-padding) positions, the loop body the wave runs (a group key, a pair key, -1 = generic) under BPOSD_PAIR_MODE
+    const int G = MP / 64, W = G / 2;
+    const std::vector<int> keys = local_layout::group_keys(g, best);
+    const local_layout::WavePlan plan = local_layout::wave_plan(g, best, local_layout::pair_mode());
+    auto real = [&](int gq) {
+        int r = 0;
+        for (int p = 64 * gq; p < 64 * gq + 64; ++p) r += best.pos_chk[p] >= 0;
+        return r;
+    };
+    printf("waves [key (real positions) | key (real positions)] -> body:");
+    for (int w = 0; w < W; ++w) printf("  [%d (%d) | %d (%d)] -> %d", keys[w], real(w), keys[w + W], real(w + W), plan.body[w]);
+    printf("\nwaves of unequal groups %d, on the generic body %d, instance PAIRKEY %d\n", best.generic_waves, plan.generic, plan.pair_key);
     return 0;
 }
