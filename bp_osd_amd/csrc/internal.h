@@ -1,6 +1,7 @@
 // internal.h -- host-side state shared by the translation units of libbposd_mi355x.so (not part of the C-ABI).
-// bposd_capi.hip holds the C-ABI, table construction and the decode calls; every launch_*.hip holds the instantiations
-// and launch code of one kernel family, so that the families compile in parallel (bp_osd_amd/build.py).
+// bposd_capi.hip holds the C-ABI and the decode calls, host_tables.hip table construction and the layout searches; every
+// launch_*.hip holds the instantiations and launch code of one kernel family, so that the families compile in parallel
+// (bp_osd_amd/build.py).
 #pragma once
 #include "../../include/bposd_mi355x.h"
 #include "../../include/bposd_mi355x_debug.h"
@@ -81,12 +82,10 @@ struct bposd_handle {
     bposd_config cfg{};
     int device = 0;
     Lane lanes[BPOSD_LANES];
-    Lane* cur = nullptr;      // lane of the call being enqueued
     int nlanes = BPOSD_LANES; // lanes this handle cycles through
     int next_lane = 0;
     CallRecord lane_rec[BPOSD_LANES];  // device-pointer calls: the record of the last call queued on each lane
     CallRecord rec[BPOSD_MAX_CHUNKS];  // host-pointer calls: one record per chunk
-    CallRecord* currec = nullptr;
     int nrec = 0;             // > 0: the last call was a host-pointer call of that many chunks
     int last_lane = 0;        // lane of the last device-pointer call
     int num_cu = 0;
@@ -137,15 +136,24 @@ struct bposd_handle {
     int nlevels = 0;
     int tab_dc = 0, tab_dv = 0, tab_mp = 0;  // layout the tables were built for
     bool have_timing = false;
-    long long batch_hint = 0;          // > 0 while a chunked host call is being enqueued: its whole batch size
     bool async_pending = false;        // a device-pointer call may still be running on some lane
-    hipStream_t osd_now = nullptr;     // stream the OSD kernel of the call being enqueued goes to
-    uint8_t *cmp_osd0 = nullptr, *cmp_osdw = nullptr;  // compact OSD rows of the chunk being enqueued (host-pointer calls)
-    bool bp_only = false;              // the call being enqueued wants BP's outputs only (bposd_posterior_llr): no OSD kernel
-    bool lane_alt = false;             // the call being enqueued takes the alternative channel from its lane's buffers
-    bool packed_now = false;           // the call being enqueued hands the kernels packed syndromes and takes packed result rows
-    bool tail_gate = false;            // the call being enqueued is a chunk of a host-pointer call: its BP kernel reports its tail
     std::string err;
+};
+
+// One BP + OSD launch pair: what it needs beyond the handle's per-code state.  The entry point that makes the call fills
+// it in and every function below takes it by const reference; nothing per-call is kept in the handle.  Host state only:
+// never a kernel argument.
+struct DecodeCall {
+    Lane* lane = nullptr;              // the lane the pair is enqueued on
+    CallRecord* rec = nullptr;         // what bposd_last_timing reads back (null: the rank probe, which records nothing)
+    hipStream_t osd_stream = nullptr;  // stream the OSD kernel goes to: the lane's osd_stream, its main stream for a lean call
+    long long batch_hint = 0;          // > 0: a chunk of a host call of that many syndromes (kernel variants are chosen for the call)
+    uint8_t *cmp_osd0 = nullptr, *cmp_osdw = nullptr;  // compact OSD rows of the chunk (host-pointer calls)
+    bool bp_only = false;              // BP's outputs only (bposd_posterior_llr): no OSD kernel
+    bool lane_alt = false;             // the alternative channel comes from the lane's buffers (bposd_decode_batch_select_device)
+    bool packed = false;               // the kernels read packed syndromes and write packed result rows
+    bool tail_gate = false;            // a chunk of a synchronous host-pointer call: its BP kernel reports its tail
+    bool lean = false;                 // the small host-pointer call: one stream, no events (decode_device_impl)
 };
 
 namespace bposd_host {
@@ -173,8 +181,19 @@ int ensure(bposd_handle* h, DevBuf& b, size_t bytes);
 int ensure_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes);
 void release(DevBuf& b);
 
-// ---- table construction (bposd_capi.hip)
-int build_tables(bposd_handle* h, int DC, int DV, int MP, int NT, int VPT);
+// ---- table construction (host_tables.hip)
+int upload_ints(bposd_handle* h, int** dst, const std::vector<int>& v);  // (a table that exists is freed first)
+int build_tables(bposd_handle* h, int DC, int DV, int MP, int NT, int VPT);  // bp_kernel (rebuilt by launch_bp when the shape changes)
+int build_tables_local(bposd_handle* h);  // sets local_ok
+int build_tables_class(bposd_handle* h);  // sets class_ok
+int build_tables_large(bposd_handle* h, int DV, int MP);
+int build_tables_serial(bposd_handle* h);
+struct DegPair { int dc, dv; };
+bool pick_pair(int dc, int dv, DegPair* out);  // the compiled bp_kernel degree pair that covers (dc, dv)
+int gf2_rank_host(int m, int n, const std::vector<int>& rp, const std::vector<int>& ci);
+int upload_priors(bposd_handle* h);
+int probe_rank_large(bposd_handle* h, const DecodeCall& call, int* rank);
+int num_candidates(const bposd_handle* h);
 
 // ---- LDS-resident BP kernel: workgroup shapes (launch_bp_lds.hip)
 bool is_reg63(const bposd_handle* h);
@@ -183,18 +202,18 @@ int shape_threads(const bposd_handle* h, int shape);
 int pick_shape(const bposd_handle* h);
 
 // ---- kernel launches, one translation unit per family
-int launch_bp(bposd_handle* h, bposd::BpParams& P);                 // launch_bp_lds.hip    (bp_kernel)
-int launch_bp_local(bposd_handle* h, const bposd::BpParams& P);     // launch_bp_local.hip  (bp_local_kernel)
-int launch_bp_class(bposd_handle* h, const bposd::BpParams& P);     // launch_bp_class.hip  (bp_class_kernel)
+int launch_bp(bposd_handle* h, const DecodeCall& call, bposd::BpParams& P);              // launch_bp_lds.hip    (bp_kernel)
+int launch_bp_local(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);  // launch_bp_local.hip  (bp_local_kernel)
+int launch_bp_class(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);  // launch_bp_class.hip  (bp_class_kernel)
 bool class_preferred(const bposd_handle* h);
-int launch_bp_large(bposd_handle* h, const bposd::BpParams& P);     // launch_bp_misc.hip   (bp_large_kernel)
-int launch_bp_serial(bposd_handle* h, const bposd::BpParams& P);    //                      (bp_serial_kernel)
-int launch_bp_any(bposd_handle* h, const bposd::BpParams& P);       //                      (bp_anydeg_kernel)
+int launch_bp_large(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);  // launch_bp_misc.hip   (bp_large_kernel)
+int launch_bp_serial(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P); //                      (bp_serial_kernel)
+int launch_bp_any(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);    //                      (bp_anydeg_kernel)
 int bp_serial_max_dv();
 size_t bp_large_lds_need(int m, int n);
-int launch_osd(bposd_handle* h, const bposd::OsdParams& P, long long B);  // launch_osd.hip (osd_kernel, osd_wave_kernel)
+int launch_osd(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& P, long long B);  // launch_osd.hip (osd_kernel, osd_wave_kernel)
 int osd_words(int n);
-int launch_osd_large(bposd_handle* h, const bposd::OsdParams& P, long long B, int* d_rank_out);  // launch_osd_large.hip
+int launch_osd_large(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& P, long long B, int* d_rank_out);  // launch_osd_large.hip
 int osd_large_maxspan(bool cs);
 // do the kernels this handle runs read packed syndromes / write packed rows themselves (else unpack / pack kernels surround them)?
 inline bool native_packed(const bposd_handle* h) {

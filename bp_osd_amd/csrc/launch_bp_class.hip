@@ -21,7 +21,7 @@ namespace bposd_host {
 constexpr int kClassVPT = 2;
 
 template <int DCLO, int DC, int DVLO, int DVHI, int MP, int MINW, int METHOD, bool UPRIOR>
-static int launch_bp_class_t(bposd_handle* h, const BpClassParams& C) {
+static int launch_bp_class_t(bposd_handle* h, const DecodeCall& call, const BpClassParams& C) {
     auto k = bp_class_kernel<DCLO, DC, DVLO, DVHI, 1, kClassVPT, MP, MP, MINW, METHOD, UPRIOR>;
     const int nt = h->class_nt;
     const size_t lds = bp_class_lds_bytes(DC, MP, MP);
@@ -36,7 +36,7 @@ static int launch_bp_class_t(bposd_handle* h, const BpClassParams& C) {
     int rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n);
     if (rc) return rc;
     BpClassParams Cq = C;
-    Cq.llr_tmp = (double*)h->cur->bpl_llr.p;
+    Cq.llr_tmp = (double*)call.lane->bpl_llr.p;
     // syndromes per queue atomic: (what is left) / (2 x grid), at most eight, one at the end (guided self-scheduling)
     // -- for codes of up to 160 checks only, where the queue atomic is the bound (surface code d = 5: 0.93 -> 0.61 ms per
     // 65536 syndromes); larger codes lose 4-6 % to the coarser tail (tools/bp_iteration_cost.py, A/B in one run)
@@ -45,20 +45,20 @@ static int launch_bp_class_t(bposd_handle* h, const BpClassParams& C) {
     while ((1ll << Cq.queue_shift) < grid * 2) Cq.queue_shift++;
     if (const char* e = getenv("BPOSD_CLASS_QUEUE_BATCH")) Cq.queue_batch = std::max(1, std::min(64, atoi(e)));
     note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_CLASS, DCLO, DC, DVHI, MP, Cq.packed_io != 0);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, h->cur->stream, Cq);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, call.lane->stream, Cq);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
 
 template <int DCLO, int DC, int DVLO, int DVHI, int MINW_MS, int MINW_PS>
-static int launch_bp_class_shape(bposd_handle* h, const BpClassParams& C, bool uprior) {
+static int launch_bp_class_shape(bposd_handle* h, const DecodeCall& call, const BpClassParams& C, bool uprior) {
     const bool ms = h->cfg.bp_method == BPOSD_BP_MIN_SUM;
 #define BPOSD_CLASS_MP(MPV)                                                                                              \
     if (h->class_mp == MPV) {                                                                                            \
-        if (ms) return uprior ? launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_MS, 1, true>(h, C) : launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_MS, 1, false>(h, C); \
+        if (ms) return uprior ? launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_MS, 1, true>(h, call, C) : launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_MS, 1, false>(h, call, C); \
         if (h->cfg.ps_math_form) /* product-sum, two divisions per edge */                                               \
-            return uprior ? launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 0, true>(h, C) : launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 0, false>(h, C); \
-        return uprior ? launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 2, true>(h, C) : launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 2, false>(h, C); \
+            return uprior ? launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 0, true>(h, call, C) : launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 0, false>(h, call, C); \
+        return uprior ? launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 2, true>(h, call, C) : launch_bp_class_t<DCLO, DC, DVLO, DVHI, MPV, MINW_PS, 2, false>(h, call, C); \
     }
     BPOSD_CLASS_MP(256)
     BPOSD_CLASS_MP(512)
@@ -74,7 +74,7 @@ bool class_preferred(const bposd_handle* h) {
     return !(h->cfg.bp_method != BPOSD_BP_MIN_SUM && is_reg63(h) && h->class_mp == 1024);
 }
 
-int launch_bp_class(bposd_handle* h, const BpParams& P) {
+int launch_bp_class(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
     BpClassParams C{};
     C.m = P.m; C.n = P.n; C.B = P.B; C.max_iter = P.max_iter; C.ms_scaling = P.ms_scaling; C.ps_clip = P.ps_clip; C.osd_enabled = P.osd_enabled;
     C.synd = P.synd; C.llr0 = P.llr0; C.sel = P.sel; C.llr0_alt = P.llr0_alt;
@@ -82,11 +82,11 @@ int launch_bp_class(bposd_handle* h, const BpParams& P) {
     C.out_bp = P.out_bp; C.out_osd0 = P.out_osd0; C.out_osdw = P.out_osdw; C.out_conv = P.out_conv; C.out_iters = P.out_iters;
     C.out_llr = P.out_llr; C.llr_ws = P.llr_ws; C.osd_list = P.osd_list; C.counters = P.counters; C.iter_total = P.iter_total; C.tail_flag = P.tail_flag; C.packed_io = P.packed_io;
     const bool uprior = h->probs_uniform && P.sel == nullptr && h->probs[0] > 0.0 && h->probs[0] < 0.5;
-    if (h->class_dc == 7) return launch_bp_class_shape<7, 7, 3, 4, BPOSD_CLASS7_MINW, BPOSD_CLASS7_MINW_PS>(h, C, uprior);
-    if (h->class_dc == 6) return launch_bp_class_shape<6, 6, 3, 3, 8, BPOSD_CLASS6_MINW_PS>(h, C, uprior);
-    if (h->class_dc == 4 && h->class_dclo == 4) return launch_bp_class_shape<4, 4, 2, 2, 8, 7>(h, C, uprior);
-    if (h->class_dc == 4 && h->class_dclo == 3) return launch_bp_class_shape<3, 4, 1, 2, 8, 7>(h, C, uprior);
-    if (h->class_dc == 8) return launch_bp_class_shape<8, 8, 4, 4, 7, 6>(h, C, uprior);
+    if (h->class_dc == 7) return launch_bp_class_shape<7, 7, 3, 4, BPOSD_CLASS7_MINW, BPOSD_CLASS7_MINW_PS>(h, call, C, uprior);
+    if (h->class_dc == 6) return launch_bp_class_shape<6, 6, 3, 3, 8, BPOSD_CLASS6_MINW_PS>(h, call, C, uprior);
+    if (h->class_dc == 4 && h->class_dclo == 4) return launch_bp_class_shape<4, 4, 2, 2, 8, 7>(h, call, C, uprior);
+    if (h->class_dc == 4 && h->class_dclo == 3) return launch_bp_class_shape<3, 4, 1, 2, 8, 7>(h, call, C, uprior);
+    if (h->class_dc == 8) return launch_bp_class_shape<8, 8, 4, 4, 7, 6>(h, call, C, uprior);
     return fail(h, BPOSD_ERR_UNSUPPORTED, "no class BP kernel for check degree %d", h->class_dc);
 }
 }  // namespace bposd_host

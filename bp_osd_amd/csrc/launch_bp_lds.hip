@@ -9,7 +9,7 @@ using namespace bposd_host;
 
 namespace bposd_host {
 template <int DC, int DV, int CPT, int VPT, int MAXNT, int MINW, bool REG, int MPT>
-static int launch_bp_t(bposd_handle* h, const BpParams& P, int NT) {
+static int launch_bp_t(bposd_handle* h, const DecodeCall& call, const BpParams& P, int NT) {
     const size_t lds = bp_lds_bytes(DC, P.mp);
     int wg_per_cu = (int)std::min<size_t>(h->lds_per_cu / lds, (size_t)(2048 / NT));
     wg_per_cu = std::max(1, std::min(wg_per_cu, 8));
@@ -19,15 +19,15 @@ static int launch_bp_t(bposd_handle* h, const BpParams& P, int NT) {
     if (h->cfg.bp_method == BPOSD_BP_MIN_SUM) {
         auto k = bp_kernel<DC, DV, CPT, VPT, MAXNT, MINW, REG, 1, MPT>;
         { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; }
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, h->cur->stream, P);
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, call.lane->stream, P);
     } else if (h->cfg.ps_math_form) {  // product-sum, two divisions per edge
         auto k = bp_kernel<DC, DV, CPT, VPT, MAXNT, MINW, REG, 0, MPT>;
         { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; }
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, h->cur->stream, P);
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, call.lane->stream, P);
     } else {                            // product-sum in the reference's operation order (the default)
         auto k = bp_kernel<DC, DV, CPT, VPT, MAXNT, MINW, REG, 2, MPT>;
         { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; }
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, h->cur->stream, P);
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NT), lds, call.lane->stream, P);
     }
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -69,23 +69,23 @@ int pick_shape(const bposd_handle* h) {
 }
 
 template <int DC, int DV, bool REG>
-static int launch_bp_shape(bposd_handle* h, const BpParams& P, int shape, int NT) {
+static int launch_bp_shape(bposd_handle* h, const DecodeCall& call, const BpParams& P, int shape, int NT) {
     // occupancy targets: LDS admits 3 workgroups per CU for H1922 (46 KB each); the regular
     // (6,3) kernels are register-capped for that (2 x 1024, 3 x 512 or 3 x 256 threads per CU)
-    if (shape == 1) return launch_bp_t<DC, DV, 1, 2, 1024, (REG ? 8 : 4), REG, (REG ? 1024 : 0)>(h, P, NT);
+    if (shape == 1) return launch_bp_t<DC, DV, 1, 2, 1024, (REG ? 8 : 4), REG, (REG ? 1024 : 0)>(h, call, P, NT);
 #ifndef BPOSD_SHAPE2_MINW
 #define BPOSD_SHAPE2_MINW 6
 #endif
-    if (shape == 2) return launch_bp_t<DC, DV, 2, 4, 512, (REG ? BPOSD_SHAPE2_MINW : 2), REG, (REG ? 1024 : 0)>(h, P, NT);
+    if (shape == 2) return launch_bp_t<DC, DV, 2, 4, 512, (REG ? BPOSD_SHAPE2_MINW : 2), REG, (REG ? 1024 : 0)>(h, call, P, NT);
     if constexpr (REG) {
-        if (shape == 4) return launch_bp_t<DC, DV, 4, 8, 256, 3, REG, 1024>(h, P, NT);
+        if (shape == 4) return launch_bp_t<DC, DV, 4, 8, 256, 3, REG, 1024>(h, call, P, NT);
     } else {
-        if (shape == 8) return launch_bp_t<DC, DV, 2, 4, 1024, 4, false, 0>(h, P, NT);
+        if (shape == 8) return launch_bp_t<DC, DV, 2, 4, 1024, 4, false, 0>(h, call, P, NT);
     }
     return fail(h, BPOSD_ERR_UNSUPPORTED, "no BP kernel shape %d for this code", shape);
 }
 
-int launch_bp(bposd_handle* h, BpParams& P) {
+int launch_bp(bposd_handle* h, const DecodeCall& call, BpParams& P) {
     int shape = pick_shape(h);
     if (!shape) return fail(h, BPOSD_ERR_UNSUPPORTED, "code too large for the LDS-resident BP kernel (m=%d n=%d)", h->m, h->n);
     const int NT = shape_threads(h, shape);
@@ -104,13 +104,13 @@ int launch_bp(bposd_handle* h, BpParams& P) {
     P.np = NPOS;
     if (bp_lds_bytes(h->tab_dc, MP) > h->lds_per_cu)
         return fail(h, BPOSD_ERR_UNSUPPORTED, "BP messages (%zu B) exceed one CU's LDS", bp_lds_bytes(h->tab_dc, MP));
-    if (is_reg63(h) && MP == 1024) return launch_bp_shape<6, 3, true>(h, P, shape, NT);
+    if (is_reg63(h) && MP == 1024) return launch_bp_shape<6, 3, true>(h, call, P, shape, NT);
     switch (h->tab_dc) {
-        case 4: return launch_bp_shape<4, 2, false>(h, P, shape, NT);
-        case 6: return launch_bp_shape<6, 3, false>(h, P, shape, NT);
-        case 8: return launch_bp_shape<8, 4, false>(h, P, shape, NT);
-        case 12: return launch_bp_shape<12, 6, false>(h, P, shape, NT);
-        case 16: return launch_bp_shape<16, 8, false>(h, P, shape, NT);
+        case 4: return launch_bp_shape<4, 2, false>(h, call, P, shape, NT);
+        case 6: return launch_bp_shape<6, 3, false>(h, call, P, shape, NT);
+        case 8: return launch_bp_shape<8, 4, false>(h, call, P, shape, NT);
+        case 12: return launch_bp_shape<12, 6, false>(h, call, P, shape, NT);
+        case 16: return launch_bp_shape<16, 8, false>(h, call, P, shape, NT);
     }
     return fail(h, BPOSD_ERR_UNSUPPORTED, "no BP kernel for check degree %d / bit degree %d", h->dc_max, h->dv_max);
 }

@@ -9,7 +9,7 @@
 namespace bposd_host {
 
 template <int CPT, int MP, int MINW, bool EARLY, bool UPRIOR, bool PACKED, int PAIRKEY = -1>
-static int launch_bp_local_tp(bposd_handle* h, const bposd::BpLocalParams& L) {
+static int launch_bp_local_tp(bposd_handle* h, const DecodeCall& call, const bposd::BpLocalParams& L) {
     using namespace bposd;
     auto k = bp_local_kernel<CPT, MP, MINW, EARLY, UPRIOR, PACKED, PAIRKEY>;
     const int nt = MP / CPT;
@@ -24,10 +24,10 @@ static int launch_bp_local_tp(bposd_handle* h, const bposd::BpLocalParams& L) {
     int rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n);
     if (rc) return rc;
     BpLocalParams Lq = L;
-    Lq.llr_tmp = (double*)h->cur->bpl_llr.p;
+    Lq.llr_tmp = (double*)call.lane->bpl_llr.p;
     note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LOCAL, CPT, MP, MINW, EARLY, PACKED);
     h->last_bp_pair_key = PAIRKEY;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, h->cur->stream, Lq);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, call.lane->stream, Lq);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -36,6 +36,6 @@ static int launch_bp_local_tp(bposd_handle* h, const bposd::BpLocalParams& L) {
 enum BplPairShape { kBplPair1024x8U = 0, kBplPair1024x6 = 1, kBplPair2048x4 = 2 };  // <2,1024,8,false,true> <2,1024,6,false,false> <2,2048,4,false,false>
 // defined in launch_bp_local_pair_k<KEY>.hip for the six uniform keys of local_keys.h
 template <int KEY>
-int launch_bp_local_pair(bposd_handle* h, const bposd::BpLocalParams& L, int shape);
+int launch_bp_local_pair(bposd_handle* h, const DecodeCall& call, const bposd::BpLocalParams& L, int shape);
 
 }  // namespace bposd_host

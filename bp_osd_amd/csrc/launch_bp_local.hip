@@ -8,30 +8,30 @@ using namespace bposd_host;
 namespace bposd_host {
 // the packed-I/O form exists for the instances auto-selection takes (internal.h: native_packed() asks for bp_variant == 0)
 template <int CPT, int MP, int MINW, bool EARLY, bool UPRIOR = false>
-static int launch_bp_local_t(bposd_handle* h, const BpLocalParams& L) {
+static int launch_bp_local_t(bposd_handle* h, const DecodeCall& call, const BpLocalParams& L) {
     constexpr bool has_packed = !EARLY && ((CPT == 1 && MP == 1024 && MINW == 8) || (CPT == 2 && MP == 1024 && (MINW == 8 || MINW == 6)) || MP == 2048);
     if constexpr (has_packed) {
-        if (L.packed_io) return launch_bp_local_tp<CPT, MP, MINW, EARLY, UPRIOR, true>(h, L);
+        if (L.packed_io) return launch_bp_local_tp<CPT, MP, MINW, EARLY, UPRIOR, true>(h, call, L);
     } else {
         if (L.packed_io) return fail(h, BPOSD_ERR_UNSUPPORTED, "this BP kernel variant has no packed-I/O form");
     }
-    return launch_bp_local_tp<CPT, MP, MINW, EARLY, UPRIOR, false>(h, L);
+    return launch_bp_local_tp<CPT, MP, MINW, EARLY, UPRIOR, false>(h, call, L);
 }
 
 // the instance whose pair body serves this layout's (uniform key, mixed) wave, for the shapes auto-selection takes
-static int launch_bp_local_pair_any(bposd_handle* h, const BpLocalParams& L, int shape) {
+static int launch_bp_local_pair_any(bposd_handle* h, const DecodeCall& call, const BpLocalParams& L, int shape) {
     switch (h->local_pair_key) {
-        case 0: return launch_bp_local_pair<0>(h, L, shape);
-        case 1: return launch_bp_local_pair<1>(h, L, shape);
-        case 2: return launch_bp_local_pair<2>(h, L, shape);
-        case 5: return launch_bp_local_pair<5>(h, L, shape);
-        case 6: return launch_bp_local_pair<6>(h, L, shape);
-        case 10: return launch_bp_local_pair<10>(h, L, shape);
+        case 0: return launch_bp_local_pair<0>(h, call, L, shape);
+        case 1: return launch_bp_local_pair<1>(h, call, L, shape);
+        case 2: return launch_bp_local_pair<2>(h, call, L, shape);
+        case 5: return launch_bp_local_pair<5>(h, call, L, shape);
+        case 6: return launch_bp_local_pair<6>(h, call, L, shape);
+        case 10: return launch_bp_local_pair<10>(h, call, L, shape);
     }
     return fail(h, BPOSD_ERR_UNSUPPORTED, "no bp_local_kernel instance with a pair body for key %d", h->local_pair_key);
 }
 
-int launch_bp_local(bposd_handle* h, const BpParams& P) {
+int launch_bp_local(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
     BpLocalParams L{};
     L.m = P.m; L.n = P.n; L.B = P.B; L.max_iter = P.max_iter; L.ms_scaling = P.ms_scaling; L.osd_enabled = P.osd_enabled;
     L.mp = h->local_mp;
@@ -43,27 +43,27 @@ int launch_bp_local(bposd_handle* h, const BpParams& P) {
     // auto-selection launches the instance that has a body for the layout's (uniform key, mixed) wave, if it has one; a
     // variant asked for by number is the plain instance (generic body for that wave)
     const bool pair = h->bp_variant == 0 && h->local_pair_key >= 0;
-    if (h->local_mp == 2048) return pair ? launch_bp_local_pair_any(h, L, kBplPair2048x4) : launch_bp_local_t<2, 2048, 4, false>(h, L);  // 1024 threads, one workgroup per CU
-    if (h->bp_variant == 17) return launch_bp_local_t<2, 1024, 8, false>(h, L);   // 512 threads, <= 64 VGPRs: 4 workgroups per CU
-    if (h->bp_variant == 18) return launch_bp_local_t<1, 1024, 8, false>(h, L);   // 1024 threads, <= 64 VGPRs: 2 workgroups per CU
-    if (h->bp_variant == 19) return launch_bp_local_t<4, 1024, 4, true>(h, L);    // 256 threads, <= 128 VGPRs: 4 workgroups per CU
-    if (h->bp_variant == 20) return launch_bp_local_t<2, 1024, 6, true>(h, L);    // as the default with early check-pass loads
-    if (h->bp_variant == 21) return launch_bp_local_t<4, 1024, 3, true>(h, L);    // 256 threads, <= 168 VGPRs: 3 workgroups per CU
+    if (h->local_mp == 2048) return pair ? launch_bp_local_pair_any(h, call, L, kBplPair2048x4) : launch_bp_local_t<2, 2048, 4, false>(h, call, L);  // 1024 threads, one workgroup per CU
+    if (h->bp_variant == 17) return launch_bp_local_t<2, 1024, 8, false>(h, call, L);   // 512 threads, <= 64 VGPRs: 4 workgroups per CU
+    if (h->bp_variant == 18) return launch_bp_local_t<1, 1024, 8, false>(h, call, L);   // 1024 threads, <= 64 VGPRs: 2 workgroups per CU
+    if (h->bp_variant == 19) return launch_bp_local_t<4, 1024, 4, true>(h, call, L);    // 256 threads, <= 128 VGPRs: 4 workgroups per CU
+    if (h->bp_variant == 20) return launch_bp_local_t<2, 1024, 6, true>(h, call, L);    // as the default with early check-pass loads
+    if (h->bp_variant == 21) return launch_bp_local_t<4, 1024, 3, true>(h, call, L);    // 256 threads, <= 168 VGPRs: 3 workgroups per CU
     // one finite positive prior for every bit: it can live in scalar registers (positive: the padding positions share it)
     const bool uprior = h->probs_uniform && !L.sel && h->probs[0] > 0.0 && h->probs[0] < 0.5;
     // Small calls are latency-bound (a max_iter straggler runs ~2000 dependent iterations, a lone syndrome ~60): one check
     // per thread (16 waves per syndrome) iterates 25-30 % faster per syndrome, two checks per thread (4 workgroups per
     // CU) have the higher throughput.  Measured crossover on the [[1922,50]] code: 32768 syndromes per call (2048: 2.5
     // against 3.3 ms, 8192: 4.1 / 5.1, 32768: 9.6 / 10.0, 131072: 31.0 / 28.2).  A chunked host call counts as a whole.
-    const long long work = h->batch_hint > 0 ? h->batch_hint : L.B;
+    const long long work = call.batch_hint > 0 ? call.batch_hint : L.B;
     const bool small_call = h->bp_variant == 0 && work <= 40000;
-    if (small_call) return uprior ? launch_bp_local_t<1, 1024, 8, false, true>(h, L) : launch_bp_local_t<1, 1024, 8, false>(h, L);
-    if (pair) return launch_bp_local_pair_any(h, L, uprior ? kBplPair1024x8U : kBplPair1024x6);
-    if ((h->bp_variant == 22 || h->bp_variant == 0) && uprior) return launch_bp_local_t<2, 1024, 8, false, true>(h, L);  // <= 64 VGPRs: 4 workgroups per CU
-    if (h->bp_variant == 23 && uprior) return launch_bp_local_t<2, 1024, 6, true, true>(h, L);
-    if (h->bp_variant == 24 && uprior) return launch_bp_local_t<2, 1024, 6, false, true>(h, L);
-    if (h->bp_variant == 25 && uprior) return launch_bp_local_t<2, 1024, 8, true, true>(h, L);   // 22 with early check-pass loads
-    if (h->bp_variant == 26 && uprior) return launch_bp_local_t<1, 1024, 8, false, true>(h, L);  // 18 with the scalar prior
-    return launch_bp_local_t<2, 1024, 6, false>(h, L);                            // 512 threads, <= 80 VGPRs: 3 workgroups per CU
+    if (small_call) return uprior ? launch_bp_local_t<1, 1024, 8, false, true>(h, call, L) : launch_bp_local_t<1, 1024, 8, false>(h, call, L);
+    if (pair) return launch_bp_local_pair_any(h, call, L, uprior ? kBplPair1024x8U : kBplPair1024x6);
+    if ((h->bp_variant == 22 || h->bp_variant == 0) && uprior) return launch_bp_local_t<2, 1024, 8, false, true>(h, call, L);  // <= 64 VGPRs: 4 workgroups per CU
+    if (h->bp_variant == 23 && uprior) return launch_bp_local_t<2, 1024, 6, true, true>(h, call, L);
+    if (h->bp_variant == 24 && uprior) return launch_bp_local_t<2, 1024, 6, false, true>(h, call, L);
+    if (h->bp_variant == 25 && uprior) return launch_bp_local_t<2, 1024, 8, true, true>(h, call, L);   // 22 with early check-pass loads
+    if (h->bp_variant == 26 && uprior) return launch_bp_local_t<1, 1024, 8, false, true>(h, call, L);  // 18 with the scalar prior
+    return launch_bp_local_t<2, 1024, 6, false>(h, call, L);                            // 512 threads, <= 80 VGPRs: 3 workgroups per CU
 }
 }  // namespace bposd_host

@@ -11,7 +11,7 @@ using namespace bposd_host;
 
 namespace bposd_host {
 template <int DC, int DV, int METHOD>
-static int launch_bp_large_tm(bposd_handle* h, BpLargeParams& P) {
+static int launch_bp_large_tm(bposd_handle* h, const DecodeCall& call, BpLargeParams& P) {
     h->large_form = METHOD;
     const size_t lds = bp_large_lds_bytes(h->m, h->n, METHOD == 2, DC);
     auto k = bp_large_kernel<DC, DV, METHOD>;
@@ -30,23 +30,23 @@ static int launch_bp_large_tm(bposd_handle* h, BpLargeParams& P) {
     int rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_msg, sizeof(double) * (size_t)grid * SLOTS * P.mp))) return rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n))) return rc;
-    P.msg_ws = (double*)h->cur->bpl_msg.p;
-    P.llr_tmp = (double*)h->cur->bpl_llr.p;
+    P.msg_ws = (double*)call.lane->bpl_msg.p;
+    P.llr_tmp = (double*)call.lane->bpl_llr.p;
     note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LARGE, DC, DV, METHOD, 0, P.packed_io != 0);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(bp_large_threads(METHOD)), lds, h->cur->stream, P);
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(bp_large_threads(METHOD)), lds, call.lane->stream, P);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
 
 template <int DC, int DV>
-static int launch_bp_large_t(bposd_handle* h, BpLargeParams& P) {
-    if (h->cfg.bp_method != BPOSD_BP_MIN_SUM) return launch_bp_large_tm<DC, DV, 0>(h, P);
+static int launch_bp_large_t(bposd_handle* h, const DecodeCall& call, BpLargeParams& P) {
+    if (h->cfg.bp_method != BPOSD_BP_MIN_SUM) return launch_bp_large_tm<DC, DV, 0>(h, call, P);
     // min-sum: a1 and the flags of every check in LDS where they fit (bp_variant 63 forces the form with whole records in the workspace)
     const bool a1_in_lds = bp_large_lds_bytes(h->m, h->n, true, DC) <= h->lds_per_cu && h->bp_variant != 63;
-    return a1_in_lds ? launch_bp_large_tm<DC, DV, 2>(h, P) : launch_bp_large_tm<DC, DV, 1>(h, P);
+    return a1_in_lds ? launch_bp_large_tm<DC, DV, 2>(h, call, P) : launch_bp_large_tm<DC, DV, 1>(h, call, P);
 }
 
-int launch_bp_large(bposd_handle* h, const BpParams& G) {
+int launch_bp_large(bposd_handle* h, const DecodeCall& call, const BpParams& G) {
     BpLargeParams P{};
     P.m = G.m; P.n = G.n; P.B = G.B; P.max_iter = G.max_iter; P.ms_scaling = G.ms_scaling; P.ps_clip = G.ps_clip; P.ps_form = h->cfg.ps_math_form;
     P.osd_enabled = G.osd_enabled; P.mp = h->tab_mp;
@@ -55,12 +55,12 @@ int launch_bp_large(bposd_handle* h, const BpParams& G) {
     P.out_bp = G.out_bp; P.out_osd0 = G.out_osd0; P.out_osdw = G.out_osdw; P.out_conv = G.out_conv;
     P.out_iters = G.out_iters; P.out_llr = G.out_llr; P.llr_ws = G.llr_ws; P.osd_list = G.osd_list;
     P.counters = G.counters; P.iter_total = G.iter_total; P.tail_flag = G.tail_flag; P.packed_io = G.packed_io;
-    if (h->dc_max <= 12 && h->dv_max <= 6) return launch_bp_large_t<12, 6>(h, P);
-    if (h->dc_max <= 16 && h->dv_max <= 8) return launch_bp_large_t<16, 8>(h, P);
+    if (h->dc_max <= 12 && h->dv_max <= 6) return launch_bp_large_t<12, 6>(h, call, P);
+    if (h->dc_max <= 16 && h->dv_max <= 8) return launch_bp_large_t<16, 8>(h, call, P);
     return fail(h, BPOSD_ERR_UNSUPPORTED, "check degree %d / bit degree %d exceed the built kernels (16 / 8)", h->dc_max, h->dv_max);
 }
 
-int launch_bp_serial(bposd_handle* h, const BpParams& P) {
+int launch_bp_serial(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
     BpSerialParams S{};
     S.m = P.m; S.n = P.n; S.E = h->E; S.B = P.B; S.max_iter = P.max_iter; S.bp_method = h->cfg.bp_method;
     S.ms_scaling = P.ms_scaling; S.ps_clip = P.ps_clip; S.ps_form = h->cfg.ps_math_form; S.osd_enabled = P.osd_enabled; S.nlevels = h->nlevels;
@@ -75,17 +75,17 @@ int launch_bp_serial(bposd_handle* h, const BpParams& P) {
     int rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_msg, sizeof(double) * (size_t)grid * h->E))) return rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n))) return rc;
-    S.msg_ws = (double*)h->cur->bpl_msg.p;
-    S.llr_tmp = (double*)h->cur->bpl_llr.p;
+    S.msg_ws = (double*)call.lane->bpl_msg.p;
+    S.llr_tmp = (double*)call.lane->bpl_llr.p;
     { int rc_lds = set_max_lds(h, (const void*)bp_serial_kernel, lds); if (rc_lds) return rc_lds; }
     note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_SERIAL, 0, 0, 0, 0, false);
-    hipLaunchKernelGGL(bp_serial_kernel, dim3((unsigned)grid), dim3(BPS_NT), lds, h->cur->stream, S);
+    hipLaunchKernelGGL(bp_serial_kernel, dim3((unsigned)grid), dim3(BPS_NT), lds, call.lane->stream, S);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
 
 // ------------------------------------------------------------------ any-degree BP (check degree > 16 or bit degree > 8)
-int launch_bp_any(bposd_handle* h, const BpParams& P) {
+int launch_bp_any(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
     BpAnyParams A{};
     A.m = P.m; A.n = P.n; A.E = h->E; A.B = P.B; A.max_iter = P.max_iter; A.bp_method = h->cfg.bp_method;
     A.ms_scaling = P.ms_scaling; A.ps_clip = P.ps_clip; A.ps_form = h->cfg.ps_math_form; A.osd_enabled = P.osd_enabled;
@@ -100,11 +100,11 @@ int launch_bp_any(bposd_handle* h, const BpParams& P) {
     int rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_msg, sizeof(double) * (size_t)grid * 3 * h->E))) return rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n))) return rc;
-    A.msg_ws = (double*)h->cur->bpl_msg.p;
-    A.llr_tmp = (double*)h->cur->bpl_llr.p;
+    A.msg_ws = (double*)call.lane->bpl_msg.p;
+    A.llr_tmp = (double*)call.lane->bpl_llr.p;
     { int rc_lds = set_max_lds(h, (const void*)bp_anydeg_kernel, lds); if (rc_lds) return rc_lds; }
     note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_ANYDEG, 0, 0, 0, 0, false);
-    hipLaunchKernelGGL(bp_anydeg_kernel, dim3((unsigned)grid), dim3(BPA_NT), lds, h->cur->stream, A);
+    hipLaunchKernelGGL(bp_anydeg_kernel, dim3((unsigned)grid), dim3(BPA_NT), lds, call.lane->stream, A);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }

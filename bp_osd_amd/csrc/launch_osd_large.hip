@@ -14,7 +14,7 @@ static int osdl_rpt(int m) {
     return 0;
 }
 
-int launch_osd_large(bposd_handle* h, const OsdParams& P, long long B, int* d_rank_out) {
+int launch_osd_large(bposd_handle* h, const DecodeCall& call, const OsdParams& P, long long B, int* d_rank_out) {
     const int RPT = osdl_rpt(h->m);
     if (!RPT) return fail(h, BPOSD_ERR_UNSUPPORTED, "m=%d beyond the HBM-resident OSD kernel (16384)", h->m);
     OsdLargeParams Q{};
@@ -84,7 +84,7 @@ int launch_osd_large(bposd_handle* h, const OsdParams& P, long long B, int* d_ra
     if (rc) return rc;
     unsigned char* ptrs[20];
     {
-        unsigned char* base = (unsigned char*)h->cur->osdl_ws.p;
+        unsigned char* base = (unsigned char*)call.lane->osdl_ws.p;
         for (int i = 0; i < 20; ++i) { ptrs[i] = base; base += a256(sizes[i]); }
     }
     Q.alist = (int*)ptrs[13];
@@ -114,7 +114,7 @@ int launch_osd_large(bposd_handle* h, const OsdParams& P, long long B, int* d_ra
         auto k = osd_large_kernel<R>;                                                                       \
         { int rc_lds = set_max_lds(h, (const void*)k, lds); if (rc_lds) return rc_lds; } \
         note_instance(h->last_osd_inst, 3, R, 0, 0, 0, Q.packed_io != 0);                                 \
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(OSDL_NT), lds, h->osd_now ? h->osd_now : h->cur->osd_stream, Q); \
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(OSDL_NT), lds, call.osd_stream, Q); \
     } break;
     switch (RPT) {
         OSDL_LAUNCH(2)

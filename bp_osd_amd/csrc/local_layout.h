@@ -1,6 +1,6 @@
 // local_layout.h -- host-side layout search for the local-edge BP kernel (bp_local_kernel.hip.h): which check owns which
 // two of its six bits, and which position (thread slot) every check gets.  Pure C++ (no HIP): included by
-// bposd_capi.hip and by tools/layout_probe.cpp, which runs the search on the CPU alone.
+// host_tables.hip and by tools/layout_probe.cpp, which runs the search on the CPU alone.
 #pragma once
 #include <algorithm>
 #include <cmath>
