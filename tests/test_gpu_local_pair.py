@@ -27,15 +27,10 @@ def _code(name):
 
 
 def _wave_table(lib, H):
-    import scipy.sparse as sp
+    from tests.local_codes import wave_tables
 
-    H = sp.csr_matrix(H)
-    H.sort_indices()
-    m, n = H.shape
-    ip, ix = np.ascontiguousarray(H.indptr, dtype=np.int32), np.ascontiguousarray(H.indices, dtype=np.int32)
-    body, info = np.full(16, -7, np.int32), np.zeros(4, np.int64)
-    assert lib.bposd_debug_local_waves(ip.ctypes.data, ix.ctypes.data, m, n, body.ctypes.data, info.ctypes.data) == 0
-    return [int(b) for b in body[: int(info[0]) // 128]], int(info[1]), int(info[2])
+    t = wave_tables(lib, H)
+    return t["body"], t["pairkey"], t["generic"]
 
 
 def _syndromes(H, q, nb, seed):
