@@ -67,6 +67,7 @@ DEBUG_SYMBOLS = (
     "bposd_debug_last_pair_key",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
+    "bposd_debug_portable_math",
 )
 
 
@@ -187,6 +188,8 @@ def load():
     lib.bposd_debug_class_layout.restype = C.c_int
     lib.bposd_debug_last_instance.argtypes = [vp, vp, vp]
     lib.bposd_debug_last_instance.restype = C.c_int
+    lib.bposd_debug_portable_math.argtypes = [C.c_int32, vp, vp, vp, C.c_int64]
+    lib.bposd_debug_portable_math.restype = C.c_int
     lib.bposd_set_osd_variant.argtypes = [vp, C.c_int32]
     lib.bposd_set_osd_variant.restype = C.c_int
     lib.bposd_last_osd_kernel.argtypes = [vp]

@@ -113,3 +113,50 @@ int bp_serial_max_dv() { return BPS_MAXDV; }
 size_t bp_large_lds_need(int m, int n) { return bp_large_lds_bytes(m, n); }
 
 }  // namespace bposd_host
+
+// ------------------------------------------------------------------ portable_math.h on the device (diagnostic)
+// One thread per element; the routines are the ones the product-sum kernels of this library inline.
+__global__ void __launch_bounds__(256) portable_math_kernel(int which, const double* __restrict__ a, const double* __restrict__ b,
+                                                            double* __restrict__ y, long long count) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const double x = a[i];
+    double r;
+    switch (which) {
+        case 0: r = pm_tanh(x); break;
+        case 1: r = pm_log(x); break;
+        case 2: r = pm_expm1(x); break;
+        case 3: r = pm_tanh_half(x); break;
+        case 4: r = pm_log_quot(x, b[i]); break;
+        case 5: r = pm_ps_tanh_half(x, 0); break;
+        case 6: r = pm_ps_tanh_half(x, 1); break;
+        case 7: r = pm_ps_log_ratio(x, 0); break;
+        default: r = pm_ps_log_ratio(x, 1); break;
+    }
+    y[i] = r;
+}
+
+extern "C" int bposd_debug_portable_math(int32_t which, const double* a, const double* b, double* y, int64_t count) {
+    if (which < 0 || which > 8 || count < 0 || (count > 0 && (!a || !y || (which == 4 && !b)))) return BPOSD_ERR_INVALID;
+    if (count > (int64_t)1 << 28) return BPOSD_ERR_UNSUPPORTED;  // 2 GiB per array: a diagnostic, not a bulk interface
+    if (count == 0) return BPOSD_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BPOSD_ERR_NO_DEVICE;
+    const size_t bytes = sizeof(double) * (size_t)count;
+    double *d_a = nullptr, *d_b = nullptr, *d_y = nullptr;
+    hipError_t e = hipMalloc((void**)&d_a, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_y, bytes);
+    if (e == hipSuccess && which == 4) e = hipMalloc((void**)&d_b, bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && which == 4) e = hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)((count + 255) / 256);  // <= 2^20 blocks
+        hipLaunchKernelGGL(portable_math_kernel, dim3(grid), dim3(256), 0, 0, (int)which, d_a, d_b, d_y, (long long)count);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(y, d_y, bytes, hipMemcpyDeviceToHost);  // (synchronises with the kernel on the null stream)
+    (void)hipFree(d_a);
+    (void)hipFree(d_b);
+    (void)hipFree(d_y);
+    return e == hipSuccess ? BPOSD_OK : BPOSD_ERR_HIP;
+}

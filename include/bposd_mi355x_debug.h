@@ -80,6 +80,14 @@ int bposd_debug_last_pair_key(bposd_handle *h, int32_t *pair_key);
 int bposd_debug_class_layout(const int32_t *csr_indptr, const int32_t *csr_indices, int32_t m, int32_t n, int32_t *pos_chk,
                              int32_t *pos_bit, int32_t *bit_slot, int32_t *grp_deg, int32_t *grp_cdeg, int64_t *info);
 
+/* Diagnostics: csrc/portable_math.h evaluated ON THE DEVICE, one thread per element -- the routines the product-sum kernels
+ * inline, so that a test can compare the gfx950 compile of that header with a host compile bit for bit.  a, b, y are host
+ * pointers to `count` doubles (count <= 2^28; b is read by which = 4 only and may be NULL otherwise).  y[i] =
+ *   0 pm_tanh(a)   1 pm_log(a)   2 pm_expm1(a)   3 pm_tanh_half(a)   4 pm_log_quot(a, b)
+ *   5 / 6 pm_ps_tanh_half(a, 0 / 1)   7 / 8 pm_ps_log_ratio(a, 0 / 1)
+ * Runs on the current device; needs no handle. */
+int bposd_debug_portable_math(int32_t which, const double *a, const double *b, double *y, int64_t count);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -576,6 +576,13 @@ void oracle_portable_tanh_half(const double *x, double *y, int64_t count) {
 void oracle_portable_log_quot(const double *a, const double *b, double *y, int64_t count) {
     for (int64_t i = 0; i < count; i++) y[i] = pm_log_quot(a[i], b[i]);
 }
+/* the two entry points of the check update: tanh(v / 2) and log((1 + x) / (1 - x)) in evaluation order `form` (0 / 1) */
+void oracle_portable_ps_tanh_half(const double *x, int32_t form, double *y, int64_t count) {
+    for (int64_t i = 0; i < count; i++) y[i] = pm_ps_tanh_half(x[i], form);
+}
+void oracle_portable_ps_log_ratio(const double *x, int32_t form, double *y, int64_t count) {
+    for (int64_t i = 0; i < count; i++) y[i] = pm_ps_log_ratio(x[i], form);
+}
 
 int oracle_decode_batch_diag(oracle_decoder *d, const uint8_t *syndromes, int64_t B, uint8_t *osdw,
                              uint8_t *osd0, uint8_t *bp, uint8_t *converged, int32_t *iters, double *llr,

@@ -75,6 +75,9 @@ int oracle_decode_batch(oracle_decoder *d, const uint8_t *syndromes, int64_t B, 
 void oracle_portable_math(int32_t which, const double *x, double *y, int64_t count);
 void oracle_portable_tanh_half(const double *x, double *y, int64_t count);
 void oracle_portable_log_quot(const double *a, const double *b, double *y, int64_t count);
+/* pm_ps_tanh_half(x, form) / pm_ps_log_ratio(x, form): what the check update calls, in either evaluation order */
+void oracle_portable_ps_tanh_half(const double *x, int32_t form, double *y, int64_t count);
+void oracle_portable_ps_log_ratio(const double *x, int32_t form, double *y, int64_t count);
 
 /* oracle_decode_batch plus per-shot BP diagnostics (see oracle_last_bp_diag); the three arrays are nullable. */
 int oracle_decode_batch_diag(oracle_decoder *d, const uint8_t *syndromes, int64_t B, uint8_t *osdw,

@@ -108,6 +108,26 @@ def portable_log_quot(a, b):
     return y
 
 
+def _portable_ps(name, x, form):
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(x)
+    f = getattr(_load(), name)
+    f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    f.restype = None
+    f(x.ctypes.data, int(form), y.ctypes.data, x.size)
+    return y
+
+
+def portable_ps_tanh_half(x, form):
+    """tanh(x / 2) of the check update in evaluation order ``form`` (portable_math.h: pm_ps_tanh_half)."""
+    return _portable_ps("oracle_portable_ps_tanh_half", x, form)
+
+
+def portable_ps_log_ratio(x, form):
+    """log((1 + x) / (1 - x)) of the check update in evaluation order ``form`` (portable_math.h: pm_ps_log_ratio)."""
+    return _portable_ps("oracle_portable_ps_log_ratio", x, form)
+
+
 class OracleDecoder:
     def __init__(self, pcm, error_rate=None, channel_probs=None, max_iter=0, bp_method="ms",
                  ms_scaling_factor=1.0, osd_method="osd0", osd_order=0, sort_tie_policy=0, weight_fn=0,

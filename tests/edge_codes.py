@@ -352,3 +352,177 @@ def kprime(case):
 
 def order_of(case):
     return kprime(case) if case["order"] == "kprime" else case["order"]
+
+
+# ----------------------------------------------------------------------------------- the product-sum table (PS_EDGES)
+# Every BP kernel family is compiled three times per instance (METHOD 1 min-sum, 2 product-sum in the reference's operation
+# order, 0 product-sum with two divisions per edge) or switches on ps_form at run time; EDGES runs min-sum only.  One row
+# here per BP instance that product-sum must reach (tests/test_gpu_ps_edges.py; tests/test_ps_edges_cpu.py keeps the table
+# honest without a GPU).  Keys: id; edge (the id of the EDGES row whose matrix and expected instance the row reuses) or code
+# (a construction of PS_CODES); bp (the instance last_instance() must report; bp_large_kernel runs its METHOD 0 for either
+# product-sum form); bp_variant / schedule; seed and shots as in EDGES (48 syndromes by default, 11 where m > 1024 or the
+# EDGES row has as few); deg1 / deg2 (the number of checks of degree 1 and 2: a degree-1 check sends log(2 / 0) = +-inf
+# without a clip); sat12 (the unclipped max_iter = 12 runs must saturate at least one shot to +-inf: every generic matrix);
+# extras (the further runs of the row: "channel" per-bit probabilities, "select" the per-shot two-valued channel, "packed"
+# the packed host API); stride (class rows: the LDS stride the layout search settles on).
+EDGE_BY_ID = {c["id"]: c for c in EDGES}
+PS_SHOTS = (38, 8)  # + the all-zero and the all-ones syndrome: 48
+PS_ERROR_RATE = 0.08
+PS_EXCLUDED_CAP = 1.0 / 8.0  # share of a case's shots whose LLRs may mix numbers and NaN (no defined OSD order)
+PS_EDGES = []
+
+
+def _ps(id=None, edge=None, **kw):
+    if edge is not None:
+        e = EDGE_BY_ID[edge]
+        kw.setdefault("bp", e["bp"] if e["bp"][0] != "bp_large_kernel" else ("bp_large_kernel", e["bp"][1][:2] + (0,)))
+        kw.setdefault("seed", e["seed"])
+        kw.setdefault("shots", e.get("shots") or PS_SHOTS)
+        for k in ("bp_variant", "schedule"):
+            if k in e:
+                kw.setdefault(k, e[k])
+        kw.setdefault("sat12", True)
+    kw.setdefault("seed", len(PS_EDGES) + 1)
+    kw.setdefault("shots", PS_SHOTS)
+    kw.setdefault("sat12", False)
+    kw.setdefault("extras", ())
+    kw.setdefault("deg1", 0)
+    kw.setdefault("deg2", 0)
+    PS_EDGES.append(dict(id=id or edge, edge=edge, **kw))
+
+
+def _golden(name):
+    import os
+
+    return np.loadtxt(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name)).astype(np.uint8)
+
+
+def _code(name):
+    from bp_osd_amd.codes import h1922, hgp, regular_ldpc_seed, ring_code
+
+    if name == "h1922_hz":  # (3,6)-regular, 961 x 1922: the REG instances of bp_kernel
+        return h1922(compute_logicals=False).hz
+    if name == "hgp400_hz":  # the reference's example code: check degree 7, bit degrees 3..4
+        return hgp(_golden("mkmn_16_4_6.txt"), compute_logicals=False).hz
+    if name == "reg36_m120":  # (3,6)-regular, small: the (6; 3) class below stride 1024
+        return sp.csr_matrix(regular_ldpc_seed(120, 240, 3, 6, seed=11))
+    if name == "toric12_hx":  # (4; 2)
+        return hgp(ring_code(12), compute_logicals=False).hx
+    if name == "reg44_hx":  # (8; 4)
+        return hgp(regular_ldpc_seed(12, 12, 4, 4, seed=3), compute_logicals=False).hx
+    raise KeyError(name)
+
+
+def ps_pcm(row):
+    """The matrix of one PS_EDGES row (scipy CSR, uint8, sorted indices)."""
+    H = pcm_for(EDGE_BY_ID[row["edge"]]) if row["edge"] else _code(row["code"])
+    H = sp.csr_matrix(H, dtype=np.uint8)
+    H.sort_indices()
+    return H
+
+
+# bp_kernel shape 1: every degree pair, and the largest matrix of the shape
+_ps(edge="bp_pair_4_2", deg1=1, deg2=57, extras=("channel",))
+_ps(edge="bp_pair_6_3", deg1=16, deg2=74)
+_ps(edge="bp_pair_8_4", deg2=15, extras=("channel", "select", "packed"))
+_ps(edge="bp_pair_12_6", deg2=3)
+_ps(edge="bp_pair_16_8", deg2=1)
+_ps(edge="bp_shape1_m1024_n2048_dc16", deg2=1)
+# shape 2 (on request) and shape 8
+_ps(edge="bp_shape2_m1024_n2048_variant2", deg1=12, deg2=95)
+_ps(edge="bp_shape8_m1025_dc6", deg1=59, deg2=284)
+_ps(edge="bp_shape8_m1025_dc8", deg1=22, deg2=97, extras=("channel", "packed"))
+_ps(edge="bp_shape8_m2048_dc6", deg1=917, deg2=780)
+# bp_kernel<6, 3, REG> at shapes 1, 2 and 4: product-sum on a (3,6)-regular code of stride 1024 stays on bp_kernel
+for v_, t_ in ((1, (1, 1024)), (0, (2, 512)), (4, (4, 256))):
+    _ps(id=f"bp_reg63_h1922_variant{v_}", code="h1922_hz", bp=("bp_kernel", (6, 3) + t_), bp_variant=v_, seed=20 + v_,
+        shots=(20, 2), sat12=True, extras=("channel", "select", "packed") if v_ == 0 else ())
+# bp_class_kernel: the surface-code class at its three strides, then one code per other degree class
+_ps(edge="bp_class_mp256_m170", stride=256, sat12=False)
+_ps(edge="bp_class_mp512_m180", stride=512, sat12=False, extras=("channel", "select", "packed"))
+_ps(edge="bp_class_mp1024_m400", stride=1024, sat12=False)
+_ps(id="bp_class_7_hgp400", code="hgp400_hz", bp=("bp_class_kernel", (7, 7, 4, 256)), stride=256, seed=31, sat12=True, extras=("channel",))
+_ps(id="bp_class_6_reg36_m120", code="reg36_m120", bp=("bp_class_kernel", (6, 6, 3, 256)), stride=256, seed=32)
+_ps(id="bp_class_4_toric12", code="toric12_hx", bp=("bp_class_kernel", (4, 4, 2, 256)), stride=256, seed=33)
+_ps(id="bp_class_8_reg44", code="reg44_hx", bp=("bp_class_kernel", (8, 8, 4, 256)), stride=256, seed=34, sat12=True)
+# bp_large_kernel<12, 6, 0> and <16, 8, 0>
+_ps(edge="bp_hbm_m1025_dc9", deg1=20, deg2=132, extras=("channel", "select", "packed"))
+_ps(edge="bp_hbm_m2049_dv6", deg1=292, deg2=436)
+_ps(edge="bp_hbm_m1024_n2049_dc16", deg1=1, deg2=1)
+_ps(edge="bp_hbm_m2049_dv7", deg1=201, deg2=379, extras=("channel", "packed"))
+# the kernels that switch on ps_form at run time
+_ps(edge="bp_serial_dv8", deg2=1, extras=("channel", "select"))
+_ps(edge="bp_anydeg_dc17", deg2=1, extras=("channel", "select"))
+_ps(edge="bp_anydeg_dv9", deg2=1)
+
+
+def ps_cases(row):
+    """The runs of one row: dicts with form (ps_math_form; the oracle's ps_math is 2 - form), clip, max_iter, kind ("uniform",
+    "channel", "select", "packed").  Uniform channel: both forms x {no clip, one finite clip} x {a short max_iter, so that
+    most shots reach OSD; 12, so that saturation shows}.  The extras: both forms at (clip, 12) and (no clip, short)."""
+    clip = (8.0, 20.0, 37.0)[row["seed"] % 3]
+    short = 1 + row["seed"] % 3
+    out = [dict(form=f, clip=c, max_iter=it, kind="uniform") for f in (0, 1) for c in (0.0, clip) for it in (short, 12)]
+    for kind in row["extras"]:
+        out += [dict(form=f, clip=c, max_iter=it, kind=kind) for f in (0, 1) for c, it in ((clip, 12), (0.0, short))]
+    return out
+
+
+def ps_case_id(case):
+    return f"{case['kind']}-form{case['form']}-clip{case['clip']:g}-it{case['max_iter']}"
+
+
+def ps_settings(row, case, n):
+    """Decoder keywords of one run (without ps_math_form / ps_math, which differ between the library and the oracle) and the
+    per-shot channel (select, alt) of a "select" run, else (None, None)."""
+    kw = dict(max_iter=case["max_iter"], bp_method="ps", ps_clip=case["clip"], osd_method="osd_cs", osd_order=6)
+    rng = np.random.default_rng(7000 + row["seed"])
+    if case["kind"] == "channel":
+        kw["channel_probs"] = rng.uniform(0.03, 0.15, size=n)
+    else:
+        kw["error_rate"] = PS_ERROR_RATE
+    if row.get("schedule"):
+        kw["schedule"] = row["schedule"]
+    return kw
+
+
+def ps_select(row, B, n):
+    """The per-shot two-valued channel of a "select" run: (prior_select [B, n], alt_channel_probs [n])."""
+    rng = np.random.default_rng(8000 + row["seed"])
+    return (rng.random((B, n)) < 0.2).astype(np.uint8), rng.uniform(0.02, 0.3, size=n)
+
+
+def ps_oracle_select(o, syn, sel, alt):
+    """The oracle with a per-shot two-valued channel: update_channel_probs, then decode, shot by shot (what the reference
+    harness does, css_decode_sim.py:207-248)."""
+    base = o._probs.copy()
+    outs = []
+    for b in range(len(syn)):
+        o.update_channel_probs(np.where(sel[b] != 0, alt, base))
+        outs.append(o.decode_batch(syn[b:b + 1]))
+    o.update_channel_probs(base)
+    return {k: np.concatenate([r[k] for r in outs]) for k in outs[0]}
+
+
+def ps_oracle_conditions(row, case, ref, syn):
+    """What the ORACLE's output of one run must show for the run to test anything (asserted with and without a GPU, so a
+    drift of the inputs fails here): the share of shots whose LLRs mix numbers and NaN stays within PS_EXCLUDED_CAP (none
+    with a clip); with a clip every LLR is finite; without one, a matrix with a degree-1 check has +-inf in every shot BP
+    ran on and the max_iter = 12 runs of the generic matrices in at least one; a short max_iter leaves more than half the
+    shots unconverged.  Returns the mask of the excluded shots."""
+    llr = ref["llr"]
+    nan = np.isnan(llr)
+    mixed = nan.any(axis=1) & ~nan.all(axis=1)
+    assert mixed.mean() <= PS_EXCLUDED_CAP, f"{mixed.sum()} of {len(mixed)} shots mix numbers and NaN"
+    if case["clip"] > 0:
+        assert not mixed.any() and np.isfinite(llr).all(), "a clipped run is not finite"
+    else:
+        inf = np.isinf(llr).any(axis=1)
+        ran = syn.any(axis=1)  # (BP does not run on the zero syndrome)
+        if row["deg1"]:
+            assert inf[ran].all(), "a degree-1 check did not saturate every shot"
+        if row["sat12"] and case["max_iter"] == 12:
+            assert inf.any(), "no shot saturated"
+    if case["max_iter"] < 12:
+        assert (np.asarray(ref["converged"]) == 0).mean() > 0.5, "most shots converged"
+    return mixed
