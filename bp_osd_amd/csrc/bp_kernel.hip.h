@@ -38,13 +38,8 @@ namespace bposd {
 
 // LDS message array type: volatile LDS-address-space accesses stop hipcc from fusing pairs into
 // ds_read2st64_b64 / ds_write2st64_b64 (half the LDS rate of two ds_read_b64 on gfx950,
-// MI355X_MICROARCH.md §LDS; measured here: BP kernel 38.8 -> 35.2 ms).  -DBPOSD_LDS_MERGED restores
-// the fused form for A/B runs.
-#ifndef BPOSD_LDS_MERGED
+// MI355X_MICROARCH.md §LDS; measured here: BP kernel 38.8 -> 35.2 ms).
 typedef volatile __attribute__((address_space(3))) double* msg_ptr;
-#else
-typedef double* msg_ptr;
-#endif
 
 struct BpParams {
     int m, n;

@@ -113,17 +113,16 @@ static int launch_osd_mw_tp(bposd_handle* h, const DecodeCall& call, const OsdPa
 
 // 0 = not this kernel.  Shapes: 1 = 2 waves x 4 rows x 15 words (m <= 512, n <= 959: [[900,36,10]], surface codes d = 19 ... 21),
 // 2 = 4 waves x 3 rows x 20 words (m <= 768, n <= 1279: surface d = 23 ... 25), 3 = 8 waves x 2 rows x 31 words (m <= 1024,
-// n <= 1983: H1922 -- only when asked for with variant 2), 11 = shape 1 as 4 waves x 2 rows (A/B: BPOSD_OSD_MW_4X2=1)
+// n <= 1983: H1922 -- only when asked for with variant 2)
 static int osd_mw_shape(const bposd_handle* h, const DecodeCall& call, const OsdParams& P, long long B) {
     static const bool on = !(getenv("BPOSD_OSD_MW") && getenv("BPOSD_OSD_MW")[0] == '0');
-    static const bool alt = getenv("BPOSD_OSD_MW_4X2") && getenv("BPOSD_OSD_MW_4X2")[0] == '1';
     static const long long min_batch = getenv("BPOSD_OSD_MW_MIN_BATCH") ? atoll(getenv("BPOSD_OSD_MW_MIN_BATCH")) : 2048;
     if (!on || h->osd_variant == 1 || P.cost != nullptr || P.dbg != nullptr) return 0;  // switched off; fp64 weights; diagnostics
     if (h->osd_variant == 0 && std::max<long long>(B, call.batch_hint) < min_batch) return 0;
     if (P.osd_method == BPOSD_OSD_E && P.osd_order > OSDW_MAX_E) return 0;
     const int m = h->m, n1 = h->n + 1;
     if (m <= 320 && n1 <= 640) return 0;  // the one-wave kernel's
-    if (m <= 512 && n1 <= 960) return alt ? 11 : 1;
+    if (m <= 512 && n1 <= 960) return 1;
     if (m <= 768 && n1 <= 1280) return h->osd_variant == 2 ? 2 : 0;  // (measured slower than osd_kernel<24>: surface code d = 25)
     if (m <= 1024 && n1 <= 1984) return h->osd_variant == 2 ? 3 : 0;
     return 0;
@@ -134,7 +133,6 @@ int launch_osd(bposd_handle* h, const DecodeCall& call, const OsdParams& P, long
         h->last_osd_kernel = 4;
         switch (shp) {
             case 1: return launch_osd_mw_t<2, 4, 15, 3>(h, call, P, B);
-            case 11: return launch_osd_mw_t<4, 2, 15, 4>(h, call, P, B);
             case 2: return launch_osd_mw_t<4, 3, 20, 2>(h, call, P, B);
             case 3: return launch_osd_mw_t<8, 2, 31, 2>(h, call, P, B);
         }

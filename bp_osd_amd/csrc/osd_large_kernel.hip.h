@@ -63,24 +63,35 @@ constexpr int OSDL_CW = 8;             // chunk width (words) of the apply pass
 #endif
 constexpr int OSDL_K = OSDL_K_OPEN;    // open (lazily applied) pivot groups
 constexpr int OSDL_G5 = 13;            // 5-bit fields of a 64-bit pivot mask in the apply pass (12 x 5 + 4)
-#ifndef OSDL_E3_X
-#define OSDL_E3_X 0   // timing experiments (wrong results): 1 no store of the materialised rows, 2 no reads of the older groups' rows
-#endif
 #ifndef OSDL_E3D
 #define OSDL_E3D 2   // words in flight per wave in E3 beyond the one being processed.  Round 3 measured 3 and 4 SLOWER (42 -> 57 / 60 M
                      // cycles per elimination) -- with FLAT loads, whose waits also waited for every prefetch (see osdl_e3_materialise);
                      // with global loads: 1 / 2 / 4 words give 8.09 / 8.16 / 8.07 k syndromes/s on l29k_ms_e15 (same box)
 #endif
-constexpr size_t OSDL_E3_LDS_OFF = 57344;   // bytes from the start of the phase union: behind the E1 tables and the panel lists (54920 B)
+constexpr int OSDL_E2C_CAP = 2048;   // longest panel list (rows); beyond it the all-rows form runs (4096: measured, no gain)
+// E3 gives each of the OSDL_K - 1 older groups sixteen table-building lanes of a wave (and holds their masks in mrow[OSDL_K - 1]);
+// the apply pass builds its 2 * OSDL_K * OSDL_G5 * OSDL_CW half-tables in one round of the workgroup's threads
+static_assert(OSDL_K >= 2 && OSDL_K - 1 <= 64 / 16 && 2 * OSDL_K * OSDL_G5 * OSDL_CW <= OSDL_NT, "OSDL_K_OPEN: 2 .. 4 open groups");
+// ---- LDS map of the panel phase: byte offsets from U, the start of the phase union.  The one place that lays the region out --
+// osdl_e2_compact_wave and the kernel body take their pointers from here (osdl_e1c_list is handed U, Lpw and Lid by the body).  E3's wave tables start behind it: E3 of one group runs
+// beside the next panel's one-wave pivot search on these lists.
+constexpr size_t OSDL_L_E1 = 0;                                             // E1 nibble tables, u64 [OSDL_K * 256]
+constexpr size_t OSDL_L_LPW = OSDL_L_E1 + (size_t)OSDL_K * 256 * 8;         // Lpw u64 [CAP]: the listed rows' panel words
+constexpr size_t OSDL_L_LT = OSDL_L_LPW + (size_t)OSDL_E2C_CAP * 8;         // Lt u64 [CAP]: their combination masks
+constexpr size_t OSDL_L_LID = OSDL_L_LT + (size_t)OSDL_E2C_CAP * 8;         // Lid u32 [CAP]: row | used << 31
+constexpr size_t OSDL_L_LPIV = OSDL_L_LID + (size_t)OSDL_E2C_CAP * 4;       // Lpiv u32 [128]: list position of pivot q, then its column
+constexpr size_t OSDL_L_LNEW = OSDL_L_LPIV + 128 * 4;                       // Lnew u16 [1024]: bit k of entry t: row t + 1024 k became a pivot row
+constexpr size_t OSDL_L_PFW = OSDL_L_LNEW + 1024 * 2;                       // PFW u64 [64] by column: final panel word of the pivot there
+constexpr size_t OSDL_L_TF = OSDL_L_PFW + 64 * 8;                           // TF u64 [64] by column: its mask, own bit included
+constexpr size_t OSDL_L_PCM = OSDL_L_TF + 64 * 8;                           // pcm u32 [2]: pivot columns of this panel
+constexpr size_t OSDL_L_LANY = OSDL_L_PCM + 2 * 4;                          // Lany u16 [1024]: bit k of entry t: row t + 1024 k got a non-zero mask in the new group
+constexpr size_t OSDL_L_PKEY = OSDL_L_LANY + 1024 * 2;                      // pkey u32 [2][OSDL_NW]: the waves' lightest candidates (sixteen-wave search)
+constexpr size_t OSDL_L_END = OSDL_L_PKEY + (size_t)2 * OSDL_NW * 4;        // 54920 with OSDL_K = 4
+constexpr size_t OSDL_E3_LDS_OFF = (OSDL_L_END + 4095) / 4096 * 4096;       // E3's wave tables (57344)
+static_assert(OSDL_L_END <= OSDL_E3_LDS_OFF && OSDL_L_PFW % 8 == 0, "E3's tables start behind the panel lists; the u64 fields are aligned");
 constexpr size_t OSDL_PCZ_LDS_OFF = OSDL_E3_LDS_OFF + (size_t)OSDL_NW * (OSDL_K - 1) * 256 * 8;   // [64] chunk maps of the new pivot rows
-#ifndef OSDL_BACKSUB_V2
-#define OSDL_BACKSUB_V2 1   // back-substitution with everything requested a step ahead and the pivots of a word solved for all right-hand sides at once (round 5)
-#endif
 #ifndef OSDL_BS_XL
 #define OSDL_BS_XL 28
-#endif
-#ifndef OSDL_OVERLAP_E3
-#define OSDL_OVERLAP_E3 1   // E3 of a group on waves 1-15 beside the NEXT panel's one-wave pivot search (round 5)
 #endif
 constexpr int OSDL_MAXSPAN = 16;       // max osd_e order, and max osd_cs order with fp64 (non-uniform channel) weights
 constexpr int OSDL_MAXSPAN_CS = 64;    // max osd_cs order with integer weights (uniform channel): as on the small path; the
@@ -181,24 +192,32 @@ __device__ __forceinline__ unsigned int osdl_opaque(unsigned int v) {
     asm volatile("" : "+v"(v));
     return v;
 }
-#ifndef BPOSD_LDS_MERGED
-typedef const volatile __attribute__((address_space(3))) unsigned long long* osdl_lds_ptr;
-#else
-typedef const unsigned long long* osdl_lds_ptr;
-#endif
+// Named address spaces give global_load / ds_read with counters of their own (generic pointers give FLAT accesses, see
+// osdl_e3_materialise).  LDS comes in two forms ON PURPOSE: the volatile one keeps look-ups as single ds_read_b64 (hipcc pairs plain
+// ones into ds_read2_b64, half rate on gfx950) -- which form a site uses is part of its generated code.
+typedef __attribute__((address_space(1))) unsigned long long osdl_g_u64;
+typedef __attribute__((address_space(1))) int osdl_g_i32;
+typedef __attribute__((address_space(1))) uint8_t osdl_g_u8;
+typedef __attribute__((address_space(1))) char osdl_g_char;
+typedef __attribute__((address_space(3))) unsigned long long osdl_l_u64;
+typedef __attribute__((address_space(3))) unsigned int osdl_l_u32;
+typedef __attribute__((address_space(3))) int osdl_l_i32;
+typedef volatile __attribute__((address_space(3))) unsigned long long osdl_lv_u64;
+typedef volatile __attribute__((address_space(3))) unsigned int osdl_lv_u32;
+typedef osdl_lv_u64* osdl_lds_w64;
+typedef osdl_lv_u32* osdl_lds_w32;
+typedef const osdl_lv_u64* osdl_lds_ptr;
+// The arguments of a non-inlined function arrive in VECTOR registers: moved to scalar registers once, a global base is an SGPR
+// pair (accesses take the base + 32-bit offset form) and an LDS address a uniform 32-bit value.
+__device__ __forceinline__ unsigned long long osdl_uni(const void* p_) {
+    const unsigned long long a = (unsigned long long)p_;
+    return ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(a >> 32)) << 32) |
+           (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)a);
+}
+__device__ __forceinline__ unsigned int osdl_lds(const void* p_) {
+    return (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(const __attribute__((address_space(3))) char*)p_);
+}
 #define OSDL_AT(type, base, byteoff) (*(type*)((char*)(base) + (size_t)(unsigned int)(byteoff)))
-// matrix words of the apply pass: streamed once per pass (60 MB per workgroup, no reuse any cache could catch) -- non-temporal,
-// so that what IS re-read (the rows' combination masks, once per 8-word chunk) stays in the L2 / Infinity Cache
-#ifndef OSDL_NT_ROWS
-#define OSDL_NT_ROWS 0  // measured (tools/ab_libs_l29k.sh): 179.8 vs 180.5 ms per 252 eliminations -- no effect, off
-#endif
-#if OSDL_NT_ROWS
-#define OSDL_ROW_LD(base, byteoff) __builtin_nontemporal_load((const unsigned long long*)((const char*)(base) + (size_t)(unsigned int)(byteoff)))
-#define OSDL_ROW_ST(base, byteoff, val) __builtin_nontemporal_store((unsigned long long)(val), (unsigned long long*)((char*)(base) + (size_t)(unsigned int)(byteoff)))
-#else
-#define OSDL_ROW_LD(base, byteoff) OSDL_AT(unsigned long long, base, byteoff)
-#define OSDL_ROW_ST(base, byteoff, val) (OSDL_AT(unsigned long long, base, byteoff) = (val))
-#endif
 
 // ---- E2c: the panel phase on a compacted list (Gaussian mode: every unfrozen row with a non-zero panel word; Gauss-Jordan:
 // the unused ones, see the Jordan fix-up at the call site).  A row whose panel word is zero after E1 stays zero for
@@ -208,11 +227,7 @@ typedef const unsigned long long* osdl_lds_ptr;
 // barrier and no LDS round trip per pivot (~400 / ~900 cycles per pivot for CR = 4 / 16 against ~10000 for the all-rows
 // form, which remains for denser panels).  A separate, non-inlined function: its registers are
 // allocated on their own, the caller holds no 16-row window when it runs.
-// LDS (offsets from lpw): words [CAP] u64, masks [CAP] u64, ids [CAP] u32 (row | used << 31), pivots [128] u32
-// (list position of pivot q, then its column), new-pivot bits [1024] u16 (bit k of entry t: row t + 1024 k).
-typedef volatile __attribute__((address_space(3))) unsigned long long* osdl_lds_w64;
-typedef volatile __attribute__((address_space(3))) unsigned int* osdl_lds_w32;
-constexpr int OSDL_E2C_CAP = 2048;   // longest panel list (rows); beyond it the all-rows form runs (4096: measured, no gain)
+// LDS: the lists of the panel-phase map (OSDL_L_LPW .. OSDL_L_LPIV above); lpw_addr is the LDS address of Lpw.
 #ifndef OSDL_MW_MIN
 #define OSDL_MW_MIN 1024  // lists longer than this are searched by all sixteen waves (512 / 256: measured 6 % slower in round 4; 512 again in round 5, when
                           // the sixteen-entries-per-lane instance of the one-wave loop had begun to spill 63 dwords under the lightest-row keys:
@@ -227,12 +242,6 @@ constexpr int OSDL_E2C_CAP = 2048;   // longest panel list (rows); beyond it the
 // >= 0), plus popcount(mask so far) inside the panel.  CPU model of L29k eliminations (tools/fillin_sim.c, policy 6 against 0):
 // row additions 348 k -> 205 k and 190 k -> 174 k, changed row-words 22.3 M -> 7.7 M and 9.9 M -> 5.4 M, longest panel list
 // 1199 -> 669 -- within 15 % of choosing by the exact remaining row weight (policy 1), which the lazy elimination cannot know.
-#ifndef OSDL_PIVOT_LIGHT
-#define OSDL_PIVOT_LIGHT 1
-#endif
-#ifndef OSDL_E2C_SKIP
-#define OSDL_E2C_SKIP OSDL_PIVOT_LIGHT  // one-wave pivot search: register slots without a one in the column are skipped (round 5)
-#endif
 constexpr unsigned int OSDL_CNT_MAX = 16383u - 64u;  // stored counts saturate here: count + popcount(mask) stays below 2^14
 
 // GAUSS (OSD-0 / OSD-E, round 5): plain Gaussian elimination -- a pivot row takes no further row additions once it is chosen
@@ -245,18 +254,15 @@ constexpr unsigned int OSDL_CNT_MAX = 16383u - 64u;  // stored counts saturate h
 template <int CR, bool GAUSS>
 __device__ __attribute__((noinline)) void osdl_e2_compact_wave(unsigned int lpw_addr, unsigned int misc_addr, int nnz,
                                                               unsigned long long vmask, int rank, int nrank, int done_in, int* rowpos_) {
-    constexpr int CAP = OSDL_E2C_CAP;
     const int lane = threadIdx.x & 63;
     osdl_lds_w64 Lpw = (osdl_lds_w64)(size_t)lpw_addr;
-    osdl_lds_w64 Lt = Lpw + CAP;
-    osdl_lds_w32 Lid = (osdl_lds_w32)(Lt + CAP);
-    osdl_lds_w32 Lpiv = Lid + CAP;
+    osdl_lds_w64 Lt = Lpw + (OSDL_L_LT - OSDL_L_LPW) / 8;
+    osdl_lds_w32 Lid = (osdl_lds_w32)(Lpw + (OSDL_L_LID - OSDL_L_LPW) / 8);
+    osdl_lds_w32 Lpiv = (osdl_lds_w32)(Lpw + (OSDL_L_LPIV - OSDL_L_LPW) / 8);
     osdl_lds_w32 misc = (osdl_lds_w32)(size_t)misc_addr;
-    typedef __attribute__((address_space(1))) int g_i32;
-    g_i32* rowpos = (g_i32*)rowpos_;
+    osdl_g_i32* rowpos = (osdl_g_i32*)rowpos_;
     unsigned long long cp[CR], ct[CR];
     unsigned int cu = 0u;  // bit s: my s-th entry is a pivot row
-#if OSDL_PIVOT_LIGHT
     unsigned int key0[CR];  // (pivot rows absorbed in earlier panels << 14) | row
 #pragma unroll
     for (int s2 = 0; s2 < CR; ++s2) {
@@ -270,7 +276,6 @@ __device__ __attribute__((noinline)) void osdl_e2_compact_wave(unsigned int lpw_
 #pragma unroll
         for (int s2 = 0; s2 < CR; ++s2) key0[s2] |= (rp[s2] < 0 ? (unsigned int)(-1 - rp[s2]) : 0u) << 14;
     }
-#endif
 #pragma unroll
     for (int s2 = 0; s2 < CR; ++s2) {
         const int pos = s2 * 64 + lane;
@@ -294,7 +299,6 @@ __device__ __attribute__((noinline)) void osdl_e2_compact_wave(unsigned int lpw_
         // every lane picks "its" entry with a one in the column (only the winning lane's pick is read)
         int kb = 0;
         unsigned long long a = 0ull, c = 0ull;
-#if OSDL_E2C_SKIP
         // Round 5: a column of the panel has a handful of ones among the list's rows, so most of the CR register slots hold no
         // row with a one there in ANY lane: a slot is tested by one wave-uniform branch (4 instructions) and only the slots that
         // pass run the key comparison (12) and, below, the row addition (7) -- as first written every slot ran both (~20) per pivot.
@@ -339,45 +343,6 @@ __device__ __attribute__((noinline)) void osdl_e2_compact_wave(unsigned int lpw_
                 ct[s2] = ((unsigned long long)thi << 32) | tlo;
             }
         }
-#else
-#if OSDL_PIVOT_LIGHT
-        unsigned int bk = ~0u;  // the lane's lightest candidate: fewest absorbed pivot rows, then lowest row
-#pragma unroll
-        for (int s2 = CR - 1; s2 >= 0; --s2) {
-            const bool hit = (((cp[s2] >> col) & 1ull) != 0ull) && (GAUSS || ((cu >> s2) & 1u) == 0u);
-            const unsigned int key = key0[s2] + ((unsigned int)__popcll(ct[s2]) << 14);
-            const bool better = hit && key < bk;
-            bk = better ? key : bk;
-            kb = better ? s2 : kb;
-            a = better ? cp[s2] : a;
-            c = better ? ct[s2] : c;
-        }
-        const unsigned int wmin = osd_wave_min_u32(bk);  // (some lane has a hit: the column was proposed)
-        const int first = (int)__builtin_ctzll(__ballot(bk == wmin));
-#else
-        const int first = (int)(wk & 63u);
-#pragma unroll
-        for (int s2 = CR - 1; s2 >= 0; --s2) {
-            const bool hit = (((cp[s2] >> col) & 1ull) != 0ull) && (GAUSS || ((cu >> s2) & 1u) == 0u);
-            kb = hit ? s2 : kb;
-            a = hit ? cp[s2] : a;
-            c = hit ? ct[s2] : c;
-        }
-#endif
-        const unsigned long long pw_p =
-            ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(a >> 32), first) << 32) |
-            (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)a, first);
-        const unsigned long long t_p =
-            ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(c >> 32), first) << 32) |
-            (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)c, first);
-        const unsigned long long tq = t_p ^ (1ull << cnp);
-#pragma unroll
-        for (int s2 = 0; s2 < CR; ++s2) {
-            const unsigned long long mm = (unsigned long long)((long long)(cp[s2] << (63 - col)) >> 63);
-            cp[s2] ^= pw_p & mm;
-            ct[s2] ^= tq & mm;
-        }
-#endif
         if (lane == first) {
             if (GAUSS) {  // the pivot row is final: to the list, out of the registers
                 Lpw[kb * 64 + lane] = pw_p;
@@ -399,13 +364,11 @@ __device__ __attribute__((noinline)) void osdl_e2_compact_wave(unsigned int lpw_
         if (pos < nnz && !(GAUSS && ((cu >> s2) & 1u))) {
             Lpw[pos] = cp[s2];
             Lt[pos] = ct[s2];
-#if OSDL_PIVOT_LIGHT
             // the pivot rows this (still unused) row absorbed in the panel join its count
             if (ct[s2] != 0ull && ((cu >> s2) & 1u) == 0u) {
                 const unsigned int cnt = (key0[s2] >> 14) + (unsigned int)__popcll(ct[s2]);
                 rowpos[key0[s2] & 0x3fffu] = -1 - (int)(cnt < OSDL_CNT_MAX ? cnt : OSDL_CNT_MAX);
             }
-#endif
         }
     }
     if (lane == 0) { misc[4] = (unsigned int)cnp; misc[5] = (unsigned int)cnr; misc[6] = cdone ? 1u : 0u; }
@@ -418,17 +381,13 @@ __device__ __attribute__((noinline)) void osdl_e2_compact_wave(unsigned int lpw_
 // spaces, registers of its own): inlined, the same code left the sort faster and the apply pass's row walk 50 % slower -- the
 // kernel sits at its 128-VGPR cap and every change of its body moves the allocation of the hot loop.
 __device__ __attribute__((noinline)) void osdl_sort(unsigned long long* keys_, int* kidx_, unsigned int lds_addr, int NS) {
-    typedef __attribute__((address_space(1))) unsigned long long g_u64;
-    typedef __attribute__((address_space(1))) int g_i32;
-    typedef __attribute__((address_space(3))) unsigned long long l_u64;
-    typedef __attribute__((address_space(3))) int l_i32;
-    g_u64* keys = (g_u64*)keys_;
-    g_i32* kidx = (g_i32*)kidx_;
+    osdl_g_u64* keys = (osdl_g_u64*)keys_;
+    osdl_g_i32* kidx = (osdl_g_i32*)kidx_;
     const int tid = threadIdx.x;
     constexpr int NT = OSDL_NT;
     const int BS = NS < 8192 ? NS : 8192;
-    l_u64* lk = (l_u64*)(size_t)lds_addr;                 // [BS]
-    l_i32* li = (l_i32*)(size_t)(lds_addr + 8192u * 8u);  // [BS]
+    osdl_l_u64* lk = (osdl_l_u64*)(size_t)lds_addr;                 // [BS]
+    osdl_l_i32* li = (osdl_l_i32*)(size_t)(lds_addr + 8192u * 8u);  // [BS]
     auto lds_passes = [&](int base, int k, int jstart) {
         for (int j = jstart; j > 0; j >>= 1) {
             for (int t = tid; t < (BS >> 1); t += NT) {
@@ -503,14 +462,11 @@ __device__ __attribute__((noinline)) void osdl_sort(unsigned long long* keys_, i
 template <int RPT>
 __device__ __attribute__((noinline)) void osdl_build_rows(unsigned long long* M_, const int* rp_, const int* ci_, const int* inv_, const uint8_t* synd_,
                                                           long long s, int m, int W, int MRL, int packed, unsigned long long* cnz_) {
-    typedef __attribute__((address_space(1))) unsigned long long g_u64;
-    typedef __attribute__((address_space(1))) int g_i32;
-    typedef __attribute__((address_space(1))) uint8_t g_u8;
-    g_u64* M = (g_u64*)M_;
-    const g_i32* rp = (const g_i32*)rp_;
-    const g_i32* ci = (const g_i32*)ci_;
-    const g_i32* inv = (const g_i32*)inv_;
-    const g_u8* synd = (const g_u8*)synd_;
+    osdl_g_u64* M = (osdl_g_u64*)M_;
+    const osdl_g_i32* rp = (const osdl_g_i32*)rp_;
+    const osdl_g_i32* ci = (const osdl_g_i32*)ci_;
+    const osdl_g_i32* inv = (const osdl_g_i32*)inv_;
+    const osdl_g_u8* synd = (const osdl_g_u8*)synd_;
     const int tid = threadIdx.x;
     constexpr int NT = OSDL_NT;
 #pragma clang loop unroll(disable)
@@ -520,7 +476,7 @@ __device__ __attribute__((noinline)) void osdl_build_rows(unsigned long long* M_
             constexpr int CH = 12;  // edges per batch (the degree of a check of the codes this path serves; more: further batches)
             const int e0 = rp[r], e1 = rp[r + 1];
             unsigned long long cz = 0ull;  // the row's chunk map: bit (word >> 3)
-            const bool sb = packed ? ((((const __attribute__((address_space(1))) unsigned long long*)synd)[(size_t)s * (size_t)((m + 63) >> 6) + (r >> 6)] >> (r & 63)) & 1ull) != 0ull
+            const bool sb = packed ? ((((const osdl_g_u64*)synd)[(size_t)s * (size_t)((m + 63) >> 6) + (r >> 6)] >> (r & 63)) & 1ull) != 0ull
                                    : (synd[(size_t)s * m + r] & 1) != 0;
             for (int eb = e0; eb < e1 || eb == e0; eb += CH) {
                 int jj[CH + 1];
@@ -544,16 +500,16 @@ __device__ __attribute__((noinline)) void osdl_build_rows(unsigned long long* M_
                         if (same && i2 < i) first = false;
                     }
                     if (first) {
-                        g_u64* dst = M + (size_t)(jj[i] >> 6) * MRL + r;  // only the owner touches row r
+                        osdl_g_u64* dst = M + (size_t)(jj[i] >> 6) * MRL + r;  // only the owner touches row r
                         if (eb == e0) *dst = word;    // (the matrix is zero: no read)
                         else *dst |= word;            // a later batch may meet a word of an earlier one
                     }
                 }
                 if (e1 == e0) break;
             }
-            ((__attribute__((address_space(1))) unsigned long long*)cnz_)[r] = cz;
+            ((osdl_g_u64*)cnz_)[r] = cz;
         } else if (r < MRL) {
-            ((__attribute__((address_space(1))) unsigned long long*)cnz_)[r] = 0ull;
+            ((osdl_g_u64*)cnz_)[r] = 0ull;
         }
     }
 }
@@ -574,23 +530,20 @@ __device__ __attribute__((noinline)) void osdl_e3_materialise(unsigned long long
     // LDS counter: the wait before a stage's first table write then waits for every row word requested for the LATER stages too,
     // and the OSDL_E3D-deep prefetch is no prefetch (E3 34 -> 31 M cycles per elimination with the spaces named).  Named address spaces
     // give global_load / ds_read with their own counters.
-    typedef __attribute__((address_space(1))) unsigned long long g_u64;
-    typedef __attribute__((address_space(3))) int l_i32;
-    const g_u64* TmO = (const g_u64*)TmO_;
-    g_u64* PRO = (g_u64*)PRO_;
-    const g_u64* M = (const g_u64*)M_;
-    const l_i32* grow = (const l_i32*)grow_;
-    const l_i32* gnp = (const l_i32*)gnp_;
-    const l_i32* gbo = (const l_i32*)gbo_;
+    const osdl_g_u64* TmO = (const osdl_g_u64*)TmO_;
+    osdl_g_u64* PRO = (osdl_g_u64*)PRO_;
+    const osdl_g_u64* M = (const osdl_g_u64*)M_;
+    const osdl_l_i32* grow = (const osdl_l_i32*)grow_;
+    const osdl_l_i32* gnp = (const osdl_l_i32*)gnp_;
+    const osdl_l_i32* gbo = (const osdl_l_i32*)gbo_;
 
-                        typedef volatile __attribute__((address_space(3))) unsigned long long* lds_rw;
-                        lds_rw tw = (lds_rw)(U + OSDL_E3_LDS_OFF / 8 + (size_t)wave * (OSDL_K - 1) * 256);
+                        osdl_lds_w64 tw = (osdl_lds_w64)(U + OSDL_E3_LDS_OFF / 8 + (size_t)wave * (OSDL_K - 1) * 256);
                         const int row = (lane < npiv) ? grow[ng * 64 + lane] : 0;
                         // Round 5: the row's chunk map (bit c: its STORED words 8c .. 8c+7 may be non-zero; kept conservatively by the
                         // build and the apply passes).  The lightest-row choice makes pivot rows of rows that absorbed little, so most of
                         // their stored words are zero -- and this phase is bound by its gather of 64 scattered row words per word.  A
                         // lane whose map clears the chunk reads the start of the matrix instead (one line for all such lanes).
-                        const unsigned long long mycz = (lane < npiv) ? ((const g_u64*)cnz_)[row] : 0ull;
+                        const unsigned long long mycz = (lane < npiv) ? ((const osdl_g_u64*)cnz_)[row] : 0ull;
                         unsigned long long pmap = 0ull;  // chunks in which my pivot row's START state is non-zero
                         unsigned long long mrow[OSDL_K - 1];
     #pragma unroll
@@ -607,20 +560,12 @@ __device__ __attribute__((noinline)) void osdl_e3_materialise(unsigned long long
                         unsigned long long prq[OSDL_E3D][4], mvq[OSDL_E3D];
                         auto issue = [&](int d, int xx) {
                             if (xx < x_end) {
-                                const g_u64* src = PRO + ((long long)gbo[builder ? tg : 0] + xx) * 64 + q0;
+                                const osdl_g_u64* src = PRO + ((long long)gbo[builder ? tg : 0] + xx) * 64 + q0;
     #pragma unroll
-#if OSDL_E3_X != 2 && OSDL_E3_X != 3
                                 for (int kk = 0; kk < 4; ++kk) prq[d][kk] = src[kk];
-#else
-                                for (int kk = 0; kk < 4; ++kk) prq[d][kk] = (unsigned long long)(size_t)src + kk;
-#endif
                                 unsigned long long ma = (unsigned long long)(((mycz >> (xx >> 3)) & 1ull) ? M + (size_t)xx * MRL + row : M);
                                 asm volatile("" : "+v"(ma));  // (an opaque address: the request count stays a constant, nothing waits early)
-#if OSDL_E3_X != 3
-                                mvq[d] = *(const g_u64*)ma;
-#else
-                                mvq[d] = ma;
-#endif
+                                mvq[d] = *(const osdl_g_u64*)ma;
                             }
                         };
                         auto process = [&](int d, int x) {
@@ -635,7 +580,7 @@ __device__ __attribute__((noinline)) void osdl_e3_materialise(unsigned long long
     #pragma unroll
                                 for (int kk = 0; kk < 4; ++kk)
                                     if ((idx >> kk) & 1u) tv ^= pr[kk];
-                                lds_rw tp = tw + lane * 16;
+                                osdl_lds_w64 tp = tw + lane * 16;
                                 tp[idx] = tv;
     #pragma unroll
                                 for (int i = 1; i < 16; ++i) {
@@ -654,11 +599,7 @@ __device__ __attribute__((noinline)) void osdl_e3_materialise(unsigned long long
                                         v ^= tw[(g * 16 + grp) * 16 + (int)((mrow[g] >> (4 * grp)) & 15ull)];
                                 }
                             }
-#if OSDL_E3_X != 1 && OSDL_E3_X != 3
                             PRO[((long long)gbo[ng] + x) * 64 + lane] = v;
-#else
-                            if (v == 0x123456789abcdefull) PRO[((long long)gbo[ng] + x) * 64 + lane] = v;
-#endif
                             pmap |= (v != 0ull) ? (1ull << (x >> 3)) : 0ull;
                             __builtin_amdgcn_wave_barrier();
                         };
@@ -693,23 +634,13 @@ __device__ __attribute__((noinline)) void osdl_e3_materialise(unsigned long long
 __device__ __attribute__((noinline)) int osdl_backsub(unsigned long long* zv_, unsigned long long* resw_, const int* tpos_, const int* pivrow_,
                                                        const unsigned long long* M_, const unsigned long long* pmask_, const unsigned long long* PRO_,
                                                        int W, int MRL, int wlast, int ntc_g) {
-    typedef __attribute__((address_space(1))) unsigned long long g_u64;
-    typedef __attribute__((address_space(1))) int g_i32;
-    typedef volatile __attribute__((address_space(3))) unsigned long long l_u64;
-    typedef __attribute__((address_space(3))) int l_i32;
-    auto uni = [](const void* p_) {
-        const unsigned long long a = (unsigned long long)p_;
-        return ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(a >> 32)) << 32) |
-               (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)a);
-    };
-    auto lds = [](const void* p_) { return (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(const __attribute__((address_space(3))) char*)p_); };
-    l_u64* zv = (l_u64*)(size_t)lds(zv_);
-    l_u64* resw = (l_u64*)(size_t)lds(resw_);
-    const l_i32* tpos = (const l_i32*)(size_t)lds(tpos_);
-    const g_i32* pivrow = (const g_i32*)uni(pivrow_);
-    const g_u64* M = (const g_u64*)uni(M_);
-    const g_u64* pmask = (const g_u64*)uni(pmask_);
-    const g_u64* PRO = (const g_u64*)uni(PRO_);
+    osdl_lv_u64* zv = (osdl_lv_u64*)(size_t)osdl_lds(zv_);
+    osdl_lv_u64* resw = (osdl_lv_u64*)(size_t)osdl_lds(resw_);
+    const osdl_l_i32* tpos = (const osdl_l_i32*)(size_t)osdl_lds(tpos_);
+    const osdl_g_i32* pivrow = (const osdl_g_i32*)osdl_uni(pivrow_);
+    const osdl_g_u64* M = (const osdl_g_u64*)osdl_uni(M_);
+    const osdl_g_u64* pmask = (const osdl_g_u64*)osdl_uni(pmask_);
+    const osdl_g_u64* PRO = (const osdl_g_u64*)osdl_uni(PRO_);
     W = __builtin_amdgcn_readfirstlane(W);
     MRL = __builtin_amdgcn_readfirstlane(MRL);
     wlast = __builtin_amdgcn_readfirstlane(wlast);
@@ -722,14 +653,14 @@ __device__ __attribute__((noinline)) int osdl_backsub(unsigned long long* zv_, u
     const int xt = ntc_g > 0 ? (tpos[ntc_g - 1] >> 6) : -1;
     if (tid < NR) resw[NR + tid] = 0ull;  // resw: [2][NR] by step parity
     __syncthreads();
-    l_u64* zsyn = zv + (size_t)SYN * W;
+    osdl_lv_u64* zsyn = zv + (size_t)SYN * W;
     unsigned long long vx[XL];
 #pragma unroll
     for (int i = 0; i < XL; ++i) vx[i] = 0ull;
     // my first word of step w_ in which the syndrome's vector alone is non-zero
     auto first_alone = [&](int w_) { return (w_ > xt ? w_ : xt) + 1 + wave; };
     auto request = [&](int w_) {
-        const g_u64* gq = PRO + osd_large_pro_base(W, w_) * 64 + lane;
+        const osdl_g_u64* gq = PRO + osd_large_pro_base(W, w_) * 64 + lane;
         const int xb = first_alone(w_);
 #pragma unroll
         for (int i4 = 0; i4 < XL / 4; ++i4) {
@@ -758,10 +689,10 @@ __device__ __attribute__((noinline)) int osdl_backsub(unsigned long long* zv_, u
         const int prow = prow0;
         const unsigned long long pv = __ballot(prow >= 0);  // (the same in every wave)
         const int np = __popcll(pv);  // = the group's pivots: slots 0 .. np - 1 of its rows in PRO
-        l_u64* rw = resw + (w & 1) * NR;
+        osdl_lv_u64* rw = resw + (w & 1) * NR;
         unsigned long long asyn = 0ull;  // the syndrome's sum of this step, my words
         if (pv != 0ull) {  // uniform
-            const g_u64* gp = PRO + osd_large_pro_base(W, w) * 64 + lane;
+            const osdl_g_u64* gp = PRO + osd_large_pro_base(W, w) * 64 + lane;
             const int xb = first_alone(w);
             unsigned int alo = 0u, ahi = 0u;
 #pragma unroll
@@ -792,7 +723,7 @@ __device__ __attribute__((noinline)) int osdl_backsub(unsigned long long* zv_, u
             // the words up to the last search column's: every right-hand side, in two halves (seventeen sums and seventeen solution
             // words at once took this function to 128 VGPRs -- and a callee that clobbers the registers the KERNEL keeps its spilled
             // SGPRs in doubled the kernel's own scratch reloads, 536 -> 1164 in the ISA, l29k_ms_e15 11.0 k -> 10.6 k syndromes/s)
-            const g_u64* gp = PRO + osd_large_pro_base(W, w) * 64 + lane;
+            const osdl_g_u64* gp = PRO + osd_large_pro_base(W, w) * 64 + lane;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 constexpr int HN = 9;
@@ -896,23 +827,13 @@ template <int RPT>
 __device__ __attribute__((noinline)) unsigned int osdl_e1c_list(const unsigned long long* Mw_, const unsigned long long* TmO_, const unsigned long long* U_,
                                                                 unsigned long long* Lpw_, unsigned int* Lid_, int* cnt_, const int* gnp_, int MRL, int ng,
                                                                 unsigned int skipmask, unsigned int anymask, unsigned int usedmask) {
-    typedef __attribute__((address_space(1))) unsigned long long g_u64;
-    typedef volatile __attribute__((address_space(3))) unsigned long long l_u64;
-    typedef volatile __attribute__((address_space(3))) unsigned int l_u32;
-    typedef __attribute__((address_space(3))) int l_i32;
-    auto uni = [](const void* p_) {
-        const unsigned long long a = (unsigned long long)p_;
-        return ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(a >> 32)) << 32) |
-               (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)a);
-    };
-    auto lds = [](const void* p_) { return (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(const __attribute__((address_space(3))) char*)p_); };
-    const g_u64* Mw = (const g_u64*)uni(Mw_);
-    const g_u64* TmO = (const g_u64*)uni(TmO_);
-    l_u64* U = (l_u64*)(size_t)lds(U_);
-    l_u64* Lpw = (l_u64*)(size_t)lds(Lpw_);
-    l_u32* Lid = (l_u32*)(size_t)lds(Lid_);
-    l_i32* cnt = (l_i32*)(size_t)lds(cnt_);
-    const l_i32* gnp = (const l_i32*)(size_t)lds(gnp_);
+    const osdl_g_u64* Mw = (const osdl_g_u64*)osdl_uni(Mw_);
+    const osdl_g_u64* TmO = (const osdl_g_u64*)osdl_uni(TmO_);
+    osdl_lv_u64* U = (osdl_lv_u64*)(size_t)osdl_lds(U_);
+    osdl_lv_u64* Lpw = (osdl_lv_u64*)(size_t)osdl_lds(Lpw_);
+    osdl_lv_u32* Lid = (osdl_lv_u32*)(size_t)osdl_lds(Lid_);
+    osdl_l_i32* cnt = (osdl_l_i32*)(size_t)osdl_lds(cnt_);
+    const osdl_l_i32* gnp = (const osdl_l_i32*)(size_t)osdl_lds(gnp_);
     MRL = __builtin_amdgcn_readfirstlane(MRL);
     ng = __builtin_amdgcn_readfirstlane(ng);
     constexpr int NT = OSDL_NT;
@@ -933,8 +854,8 @@ __device__ __attribute__((noinline)) unsigned int osdl_e1c_list(const unsigned l
         unsigned long long a0 = (unsigned long long)((g < ng && s0 >= 0) ? TmO + (size_t)g * MRL + tid + s0 * NT : Mw + tid);
         unsigned long long a1 = (unsigned long long)((g < ng && s1 >= 0) ? TmO + (size_t)g * MRL + tid + s1 * NT : Mw + tid);
         asm volatile("" : "+v"(a0), "+v"(a1));
-        m0[g] = *(const g_u64*)a0;
-        m1[g] = *(const g_u64*)a1;
+        m0[g] = *(const osdl_g_u64*)a0;
+        m1[g] = *(const osdl_g_u64*)a1;
     }
     // the nibble tables: U[(g * 16 + grp) * 16 + nibble]
     auto delta = [&](const unsigned long long (&mm)[OSDL_K]) {
@@ -1016,31 +937,20 @@ __device__ __attribute__((noinline)) unsigned int osdl_e1c_list(const unsigned l
 __device__ __attribute__((noinline)) int osdl_apply_sparse(unsigned long long* U_, const int* alist_, const unsigned long long* TmO_,
                                                             const unsigned long long* PRO_, unsigned long long* M_, const int* gnp_, const int* gbo_,
                                                             int MRL, int W, int xlo, int ng, int nact, unsigned long long* cnz_, const unsigned long long* gcnz_) {
-    typedef __attribute__((address_space(1))) unsigned long long g_u64;
-    typedef __attribute__((address_space(1))) int g_i32;
-    typedef __attribute__((address_space(1))) char g_char;
-    typedef __attribute__((address_space(3))) unsigned long long l_u64;
-    typedef __attribute__((address_space(3))) int l_i32;
-    typedef __attribute__((address_space(3))) unsigned int l_u32;
     // The arguments of a non-inlined function arrive in VECTOR registers: left so, every address below is 64-bit vector
     // arithmetic on values the compiler must take for divergent (128 VGPRs and spills inside the loop in the first build).  Moved
-    // to scalar registers once, the bases are SGPR pairs and the accesses take the base + 32-bit offset form.
-    auto uni = [](const void* p_) {
-        const unsigned long long a = (unsigned long long)p_;
-        return ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(a >> 32)) << 32) |
-               (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)a);
-    };
+    // to scalar registers once (osdl_uni), the bases are SGPR pairs and the accesses take the base + 32-bit offset form.
     MRL = __builtin_amdgcn_readfirstlane(MRL); W = __builtin_amdgcn_readfirstlane(W); xlo = __builtin_amdgcn_readfirstlane(xlo);
     ng = __builtin_amdgcn_readfirstlane(ng); nact = __builtin_amdgcn_readfirstlane(nact);
-    const g_i32* alist = (const g_i32*)uni(alist_);
-    const g_u64* TmO = (const g_u64*)uni(TmO_);
-    const g_u64* PRO = (const g_u64*)uni(PRO_);
-    g_u64* M = (g_u64*)uni(M_);
-    g_u64* cnz = (g_u64*)uni(cnz_);
-    const g_u64* gcnz = (const g_u64*)uni(gcnz_);
-    const l_i32* gnp = (const l_i32*)(size_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(const l_i32*)gnp_);
-    const l_i32* gbo = (const l_i32*)(size_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(const l_i32*)gbo_);
-    l_u64* PRW = (l_u64*)(size_t)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(size_t)(l_u64*)U_);  // [2][OSDL_K][OSDL_CW][64]
+    const osdl_g_i32* alist = (const osdl_g_i32*)osdl_uni(alist_);
+    const osdl_g_u64* TmO = (const osdl_g_u64*)osdl_uni(TmO_);
+    const osdl_g_u64* PRO = (const osdl_g_u64*)osdl_uni(PRO_);
+    osdl_g_u64* M = (osdl_g_u64*)osdl_uni(M_);
+    osdl_g_u64* cnz = (osdl_g_u64*)osdl_uni(cnz_);
+    const osdl_g_u64* gcnz = (const osdl_g_u64*)osdl_uni(gcnz_);
+    const osdl_l_i32* gnp = (const osdl_l_i32*)(size_t)osdl_lds(gnp_);
+    const osdl_l_i32* gbo = (const osdl_l_i32*)(size_t)osdl_lds(gbo_);
+    osdl_l_u64* PRW = (osdl_l_u64*)(size_t)osdl_lds(U_);  // [2][OSDL_K][OSDL_CW][64]
     constexpr int NT = OSDL_NT;
     constexpr int BUF = OSDL_K * 64 * OSDL_CW;
     constexpr int NSW = 4;                       // staging waves
@@ -1052,8 +962,8 @@ __device__ __attribute__((noinline)) int osdl_apply_sparse(unsigned long long* U
     static_assert(OSDL_SPARSE_LIST % NWT == 0, "whole entries per walking thread");
     const int tid = threadIdx.x;
     const int nch = (W - xlo + OSDL_CW - 1) / OSDL_CW;
-    l_u32* ELIST = (l_u32*)(PRW + 2 * BUF);      // [OSDL_SPARSE_LIST] the pass's (row, group, pivot) entries
-    l_i32* ecount = (l_i32*)(ELIST + OSDL_SPARSE_LIST);
+    osdl_l_u32* ELIST = (osdl_l_u32*)(PRW + 2 * BUF);      // [OSDL_SPARSE_LIST] the pass's (row, group, pivot) entries
+    osdl_l_i32* ecount = (osdl_l_i32*)(ELIST + OSDL_SPARSE_LIST);
     // ---- The work list of the pass: one entry per SET BIT of a listed row's masks -- (row, group, pivot), i.e. "row absorbs that
     // pivot row" -- packed as  row * 8 | (group * 512 + pivot) << 17.  A lane walks ENTRIES, not rows: a row's mask over the
     // start states of a group's pivot rows has 1-2 bits as a rule but 30-100 for one row in twelve (a pivot row that absorbed
@@ -1167,7 +1077,7 @@ __device__ __attribute__((noinline)) int osdl_apply_sparse(unsigned long long* U
             OSDL_STEP_BARRIER();
             const int x0 = xlo + c * OSDL_CW;
             const int cw = (W - x0) < OSDL_CW ? (W - x0) : OSDL_CW;
-            const l_u64* blk = PRW + (c & 1) * BUF;
+            const osdl_l_u64* blk = PRW + (c & 1) * BUF;
 #pragma unroll
             for (int j = 0; j < EPW; ++j) {
                 if (j >= nj) break;  // uniform
@@ -1176,7 +1086,7 @@ __device__ __attribute__((noinline)) int osdl_apply_sparse(unsigned long long* U
                     // collide when their pivots are 32 apart.  ([group][pivot][8 words] with 128-bit reads put all 64 lanes on 16
                     // banks: 16-way conflicts.)  Volatile: single ds_read_b64 with immediate offsets, not the half-rate
                     // ds_read2st64_b64 pairs (same finding as in the table walk).
-                    const volatile l_u64* src = (const volatile l_u64*)(blk + (ent[j] >> 17));
+                    const osdl_lv_u64* src = (const osdl_lv_u64*)(blk + (ent[j] >> 17));
                     const unsigned int ro = ent[j] & 0x1ffffu;
                     unsigned long long v[OSDL_CW];
 #pragma unroll
@@ -1184,7 +1094,7 @@ __device__ __attribute__((noinline)) int osdl_apply_sparse(unsigned long long* U
 #pragma unroll
                     for (int xx = 0; xx < OSDL_CW; ++xx)
                         if (xx < cw && v[xx] != 0ull)
-                            __hip_atomic_fetch_xor((g_u64*)((g_char*)(M + (size_t)(x0 + xx) * MRL) + ro), v[xx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            __hip_atomic_fetch_xor((osdl_g_u64*)((osdl_g_char*)(M + (size_t)(x0 + xx) * MRL) + ro), v[xx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
         }
@@ -1534,7 +1444,7 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
 #pragma unroll
                     for (int xx = 0; xx < OSDL_CW; ++xx) {
                         cur[xx] = 0ull;
-                        if (xx < cw && live && v[xx] != 0ull) cur[xx] = OSDL_ROW_LD(M + (size_t)(x0 + xx) * MRL, ro);
+                        if (xx < cw && live && v[xx] != 0ull) cur[xx] = OSDL_AT(unsigned long long, M + (size_t)(x0 + xx) * MRL, ro);
                     }
                     // The new words are formed for all eight positions in one straight-line block (the positions that do not change
                     // hold 0 ^ 0) and pinned there: with the XOR inside each store's own branch the compiler waits vmcnt(0) before
@@ -1546,7 +1456,7 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                     asm volatile("" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]), "+v"(cur[6]), "+v"(cur[7]));
 #pragma unroll
                     for (int xx = 0; xx < OSDL_CW; ++xx)
-                        if (xx < cw && live && v[xx] != 0ull) OSDL_ROW_ST(M + (size_t)(x0 + xx) * MRL, ro, cur[xx]);
+                        if (xx < cw && live && v[xx] != 0ull) OSDL_AT(unsigned long long, M + (size_t)(x0 + xx) * MRL, ro) = cur[xx];
                 }
             }
             if (threadIdx.x == 0) misc[8] = 0;
@@ -1590,15 +1500,16 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
             const bool jordan = !gauss;
             {
                 constexpr int CAP = OSDL_E2C_CAP;
-                unsigned long long* Lpw = U + OSDL_K * 256;          // behind the E1 tables
-                unsigned long long* Lt = Lpw + CAP;
-                unsigned int* Lid = (unsigned int*)(Lt + CAP);
-                unsigned int* Lpiv = Lid + CAP;                      // [128]
-                unsigned short* Lnew = (unsigned short*)(Lpiv + 128);  // [1024] bit k: row tid + 1024 k became a pivot row
-                unsigned long long* PFW = (unsigned long long*)(Lnew + 1024);  // [64] by column: final panel word of the pivot there
-                unsigned long long* TF = PFW + 64;                             // [64] by column: its mask, own bit included
-                unsigned int* pcm = (unsigned int*)(TF + 64);                  // [2] pivot columns of this panel
-                unsigned short* Lany = (unsigned short*)(pcm + 2);             // [1024] bit k: row tid + 1024 k got a non-zero mask in the new group
+                unsigned char* const Ub = (unsigned char*)U;  // the panel-phase map (OSDL_L_*)
+                unsigned long long* Lpw = (unsigned long long*)(Ub + OSDL_L_LPW);
+                unsigned long long* Lt = (unsigned long long*)(Ub + OSDL_L_LT);
+                unsigned int* Lid = (unsigned int*)(Ub + OSDL_L_LID);
+                unsigned int* Lpiv = (unsigned int*)(Ub + OSDL_L_LPIV);
+                unsigned short* Lnew = (unsigned short*)(Ub + OSDL_L_LNEW);
+                unsigned long long* PFW = (unsigned long long*)(Ub + OSDL_L_PFW);
+                unsigned long long* TF = (unsigned long long*)(Ub + OSDL_L_TF);
+                unsigned int* pcm = (unsigned int*)(Ub + OSDL_L_PCM);
+                unsigned short* Lany = (unsigned short*)(Ub + OSDL_L_LANY);
                 if (tid == 0) { misc[7] = 0; pcm[0] = 0u; pcm[1] = 0u; }
                 Lnew[threadIdx.x] = 0;
                 Lany[threadIdx.x] = 0;
@@ -1619,23 +1530,20 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                         // parity; the lowest column, lowest wave wins).  ~60 instructions and a barrier per pivot against ~450 from
                         // one wave walking the list in LDS (rounds 2-3's form: 90 M cycles in the slowest elimination of an L29k batch).
                         constexpr int MWR = OSDL_E2C_CAP / OSDL_NT;  // entries per lane
+                        static_assert(OSDL_E2C_CAP % OSDL_NT == 0, "the sixteen-wave search holds whole entries per lane");
                         unsigned long long cp[MWR], ct[MWR];
                         unsigned int cu = 0u;
-#if OSDL_PIVOT_LIGHT
                         unsigned int key0[MWR];  // (pivot rows absorbed in earlier panels << 14) | row, see osdl_e2_compact_wave
-                        unsigned int* pkey = (unsigned int*)(Lany + 1024);  // [2][NW] the waves' lightest candidates, behind the lists
-#endif
+                        unsigned int* pkey = (unsigned int*)(Ub + OSDL_L_PKEY);  // [2][NW] the waves' lightest candidates
 #pragma unroll
                         for (int s2 = 0; s2 < MWR; ++s2) {
                             const int pos = s2 * NT + (int)threadIdx.x;
                             cp[s2] = pos < nnz ? Lpw[pos] : 0ull;
                             ct[s2] = 0ull;
                             if (pos < nnz && (Lid[pos] >> 31)) cu |= 1u << s2;
-#if OSDL_PIVOT_LIGHT
                             key0[s2] = pos < nnz ? (Lid[pos] & 0x3fffu) : 0u;
                             const int rpv = rowpos[key0[s2]];
                             key0[s2] |= (rpv < 0 ? (unsigned int)(-1 - rpv) : 0u) << 14;
-#endif
                         }
                         int cnp = 0, cnr = nrank;
                         bool cdone = done;
@@ -1651,7 +1559,6 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                             const int colw = (int)(wk >> 6);
                             int kb = 0;
                             unsigned long long a = 0ull, c = 0ull;
-#if OSDL_PIVOT_LIGHT
                             unsigned int bk = ~0u;
 #pragma unroll
                             for (int s2 = MWR - 1; s2 >= 0; --s2) {
@@ -1666,16 +1573,6 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                             const unsigned int wmin = osd_wave_min_u32(bk);
                             const int firstl = colw < 64 ? (int)__builtin_ctzll(__ballot(bk == wmin)) : 0;
                             if (lane == firstl) pkey[par * OSDL_NW + wave] = wmin;
-#else
-                            const int firstl = (int)(wk & 63u);
-#pragma unroll
-                            for (int s2 = MWR - 1; s2 >= 0; --s2) {
-                                const bool hit = (((cp[s2] >> (colw & 63)) & 1ull) != 0ull) && (((cu >> s2) & 1u) == 0u);
-                                kb = hit ? s2 : kb;
-                                a = hit ? cp[s2] : a;
-                                c = hit ? ct[s2] : c;
-                            }
-#endif
                             if (lane == firstl) {
                                 pcol[par * OSDL_NW + wave] = (unsigned int)(colw < 64 ? colw : 64);
                                 pbuf[(size_t)(par * OSDL_NW + wave) * 2 + 0] = a;
@@ -1683,7 +1580,6 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                             }
                             __syncthreads();
                             int mincol = 64, wv = 0;
-#if OSDL_PIVOT_LIGHT
                             unsigned int minkey = ~0u;  // lowest column, then the lightest row among the waves that propose it
 #pragma unroll
                             for (int q = OSDL_NW - 1; q >= 0; --q) {
@@ -1691,13 +1587,6 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                                 const unsigned int pk = pkey[par * OSDL_NW + q];
                                 if (pc < mincol || (pc == mincol && pk <= minkey)) { mincol = pc; minkey = pk; wv = q; }
                             }
-#else
-#pragma unroll
-                            for (int q = OSDL_NW - 1; q >= 0; --q) {
-                                const int pc = (int)pcol[par * OSDL_NW + q];
-                                if (pc <= mincol) { mincol = pc; wv = q; }
-                            }
-#endif
                             if (mincol >= 64) { par ^= 1; break; }
                             const unsigned long long pw_p = pbuf[(size_t)(par * OSDL_NW + wv) * 2 + 0];
                             const unsigned long long t_p = pbuf[(size_t)(par * OSDL_NW + wv) * 2 + 1];
@@ -1730,12 +1619,10 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                             if (pos < nnz && !(gauss && ((cu >> s2) & 1u))) {
                                 Lpw[pos] = cp[s2];
                                 Lt[pos] = ct[s2];
-#if OSDL_PIVOT_LIGHT
                                 if (ct[s2] != 0ull && ((cu >> s2) & 1u) == 0u) {
                                     const unsigned int cnt = (key0[s2] >> 14) + (unsigned int)__popcll(ct[s2]);
                                     rowpos[key0[s2] & 0x3fffu] = -1 - (int)(cnt < OSDL_CNT_MAX ? cnt : OSDL_CNT_MAX);
                                 }
-#endif
                             }
                         }
                         if (tid == 0) { misc[4] = cnp; misc[5] = cnr; misc[6] = cdone ? 1 : 0; }
@@ -1994,7 +1881,6 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                             if (((frozenmask >> k) & 1u) == 0u) mybits += __popcll(t[k]);
                         if (mybits) atomicAdd(&misc[8], mybits);
                     }
-#if OSDL_PIVOT_LIGHT
                     // (this form takes whichever candidate row comes first, but keeps the rows' absorbed-pivot counts for the
                     // compact panels that follow: rowpos = -1 - count for an unused row)
 #pragma unroll
@@ -2003,7 +1889,6 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                             const int rp = OSDL_AT(int, rowpos, (ro >> 1) + k * NT * 4) - __popcll(t[k]);
                             OSDL_AT(int, rowpos, (ro >> 1) + k * NT * 4) = rp > -1 - (int)OSDL_CNT_MAX ? rp : -1 - (int)OSDL_CNT_MAX;
                         }
-#endif
                 }
             }
             if (gauss) frozenmask |= usedmask;  // Gaussian: a pivot row takes no more updates
@@ -2038,7 +1923,7 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                 if (w + 1 < W) {
                     // Round 5: where no apply pass follows at once, only word w + 1 -- which the next panel's E1 tables need -- is
                     // materialised here (wave 0); the rest of the group runs on waves 1-15 beside that panel's one-wave pivot search.
-                    const bool defer = OSDL_OVERLAP_E3 && ng + 1 < OSDL_K && w + 2 < W;
+                    const bool defer = ng + 1 < OSDL_K && w + 2 < W;
                     if (defer) {
                         osdl_e3_materialise(U, grow, gnp, TmO, PRO, gbo, M, (int)MRL, W, w, ng, npiv, cnz, pcz, w + 1, w + 2, 0, 1);
                         e3p = true; e3p_g = ng; e3p_w = w; e3p_npiv = npiv;
@@ -2111,120 +1996,10 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
             // path).  Pivot row p ended as XOR of start_l over l in S_p (pmask: the pivots of its own group it absorbed, and
             // itself), so <row_p, z> over the words right of the panel = parity(popcount(S_p & A)) with A_l = <start_l, z>;
             // the panel's own word is final in M and is read from there (one gather per step).
-#if !OSDL_BACKSUB_V2
-            unsigned long long* resb = resw + NR;  // [NR] the own-word part, by column lane (behind resw: R has room for NR + 1 vectors' tails)
-            if (tid < NR) resb[tid] = 0ull;
+            const int xt_ = osdl_backsub(zv, resw, tpos, pivrow, M, pmask, PRO, W, (int)MRL, wlast, ntc_g);
+            OSDL_ADD(27, xt_);
+            (void)xt_;
             __syncthreads();
-            // Round 5: a unit right-hand side e_t is zero to the right of t, and so is its solution (a pivot row has no entry to the
-            // left of its pivot column): beyond the word of the LAST search column only the syndrome's vector is non-zero, and a word there
-            // takes one look-up and two bit operations instead of seventeen and thirty-four.  The search columns are the first non-pivot
-            // columns in sorted order, a few words into the matrix; the loop below was bound by those look-ups (each a 512-byte LDS
-            // broadcast: ~16 k of a step's ~25-30 k cycles, 14 M cycles per L29k elimination).  xt = -1 without search columns (OSD-0).
-            const int xt = ntc_g > 0 ? (tpos[ntc_g - 1] >> 6) : -1;
-            OSDL_ADD(27, xt);
-#pragma clang loop unroll(disable)
-            for (int w = wlast; w >= 0; --w) {
-                const int prow = pivrow[w * 64 + lane];  // lane q: the pivot at sorted position 64 w + q, if any
-                const unsigned long long pv = __ballot(prow >= 0);
-                if (pv == 0ull) continue;  // (uniform: no pivot in this word)
-                const int np = __popcll(pv);  // = the group's pivots: slots 0 .. np - 1 of its rows in PRO
-                unsigned long long acc[NR];
-#pragma unroll
-                for (int c = 0; c < NR; ++c) acc[c] = 0ull;
-                const unsigned long long* gp = PRO + osd_large_pro_base(W, w) * 64 + lane;
-                // the 16 waves split the words to the right; a wave keeps XB of its words in flight (the loads are coalesced now,
-                // so that is XB requests, not XB x 64), and the NR solution words of a position are read from LDS together
-                // before they are used: as first written the loop waited for every load and every LDS read on its own
-                // (47 k cycles per step, 20 M per elimination)
-                constexpr int XB = 8;
-                for (int x0 = w + 1 + wave; x0 < W; x0 += OSDL_NW * XB) {
-                    unsigned long long vx[XB];
-#pragma unroll
-                    for (int i = 0; i < XB; ++i) {
-                        const int x = x0 + i * OSDL_NW;
-                        vx[i] = gp[(size_t)(x < W ? x : W - 1) * 64];
-                    }
-#pragma unroll
-                    for (int i = 0; i < XB; ++i) {
-                        const int x = x0 + i * OSDL_NW;
-                        if (x > xt && x < W) {  // uniform: the syndrome's vector alone
-                            const unsigned long long zs = zv[(size_t)OSDL_MAXSPAN * W + x];
-                            const unsigned int lo = __builtin_amdgcn_bitop3_b32((unsigned int)acc[OSDL_MAXSPAN], (unsigned int)vx[i], (unsigned int)zs, 0x78);
-                            const unsigned int hi = __builtin_amdgcn_bitop3_b32((unsigned int)(acc[OSDL_MAXSPAN] >> 32), (unsigned int)(vx[i] >> 32), (unsigned int)(zs >> 32), 0x78);
-                            acc[OSDL_MAXSPAN] = ((unsigned long long)hi << 32) | lo;
-                        } else if (x < W) {  // uniform
-                            unsigned long long zz[NR];
-#pragma unroll
-                            for (int c = 0; c < NR; ++c) zz[c] = zv[(size_t)c * W + x];
-                            static_assert(NR == 17, "the statement below names every element");
-                            asm volatile("" : "+v"(zz[0]), "+v"(zz[1]), "+v"(zz[2]), "+v"(zz[3]), "+v"(zz[4]), "+v"(zz[5]), "+v"(zz[6]), "+v"(zz[7]),
-                                         "+v"(zz[8]), "+v"(zz[9]), "+v"(zz[10]), "+v"(zz[11]), "+v"(zz[12]), "+v"(zz[13]), "+v"(zz[14]), "+v"(zz[15]),
-                                         "+v"(zz[16]));
-                            const unsigned int vlo = (unsigned int)vx[i], vhi = (unsigned int)(vx[i] >> 32);
-#pragma unroll
-                            for (int c = 0; c < NR; ++c) {  // acc ^= v & z: one v_bitop3 per half (0x78 = a ^ (b & c))
-                                const unsigned int lo = __builtin_amdgcn_bitop3_b32((unsigned int)acc[c], vlo, (unsigned int)zz[c], 0x78);
-                                const unsigned int hi = __builtin_amdgcn_bitop3_b32((unsigned int)(acc[c] >> 32), vhi, (unsigned int)(zz[c] >> 32), 0x78);
-                                acc[c] = ((unsigned long long)hi << 32) | lo;
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < NR; ++c) {
-                    if (c < ntc_g || c == OSDL_MAXSPAN) {  // uniform
-                        const unsigned long long bits = __ballot(lane < np && (__popcll(acc[c]) & 1));
-                        if (lane == 0 && bits) atomicXor(&resw[c], bits);
-                    }
-                }
-                // Round 5: the pivot rows of a word are no longer reduced against each other (plain Gaussian elimination, see
-                // osdl_e2_compact_wave), so pivot row q has entries at the columns of the word's LATER pivots and the word is solved
-                // from its last pivot column to its first: x[j] = parity(S_j & A) ^ <own word of row j, z[w]>, z[w] |= x[j] << j.
-                // One wave, right-hand side c on lane c, the row's own word broadcast by v_readlane: <= 64 short dependent steps
-                // per word (~1.5 M cycles per elimination) for the Jordan steps the panel phase and the apply passes no longer do.
-                unsigned long long vb = 0ull, S = 0ull;
-                if (wave == 0 && prow >= 0) {  // (requested before the barrier)
-                    vb = M[(size_t)w * MRL + prow];
-                    S = pmask[w * 64 + lane];
-                }
-                __syncthreads();
-                if (wave == 0) {
-#pragma unroll
-                    for (int c = 0; c < NR; ++c) {
-                        if (c < ntc_g || c == OSDL_MAXSPAN) {  // bit j: parity(S_j & A_c), the part from the words to the right
-                            const unsigned long long pa = __ballot(prow >= 0 && (__popcll(S & resw[c]) & 1) != 0);
-                            if (lane == 0) resb[c] = pa;
-                        }
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    const bool mine = lane < NR && (lane < ntc_g || lane == OSDL_MAXSPAN);
-                    unsigned long long z = mine ? zv[(size_t)lane * W + w] : 0ull;
-                    const unsigned long long pa = mine ? resb[lane] : 0ull;
-                    unsigned long long pvm = pv;  // wave-uniform
-                    while (pvm) {
-                        const int j = 63 - __builtin_clzll(pvm);
-                        pvm &= ~(1ull << j);
-                        const unsigned long long vbj =
-                            ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(vb >> 32), j) << 32) |
-                            (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)vb, j);
-                        const unsigned long long bit = ((pa >> j) ^ (unsigned long long)__popcll(vbj & z)) & 1ull;
-                        z |= bit << j;  // (no right-hand side has a bit of its own at a pivot column)
-                    }
-                    if (mine) {
-                        zv[(size_t)lane * W + w] = z;
-                        resw[lane] = 0ull;
-                    }
-                }
-                __syncthreads();
-            }
-#else
-            {
-                const int xt_ = osdl_backsub(zv, resw, tpos, pivrow, M, pmask, PRO, W, (int)MRL, wlast, ntc_g);
-                OSDL_ADD(27, xt_);
-                (void)xt_;
-            }
-            __syncthreads();
-#endif
             OSDL_TICK(13);
             // reduced columns and reduced syndrome as bit vectors over the pivot ROWS (the layout the sweep below uses)
 #pragma unroll
