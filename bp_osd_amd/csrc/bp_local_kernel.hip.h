@@ -23,7 +23,10 @@
 // are instruction immediates.
 //
 // Everything else -- persistent workgroups on an atomic queue, in-place messages, incremental convergence
-// bitmap with a speculative check pass, outputs, OSD hand-off -- is the scheme of bp_kernel.hip.h (rows a3-a7).
+// bitmap, outputs, OSD hand-off -- is the scheme of bp_kernel.hip.h (rows a3-a7), except the convergence test itself:
+// bp_kernel's waves each look at their own bitmap words and agree through flag words and a barrier (which makes its
+// check pass speculative); here every wave reads the WHOLE bitmap (MP/64 b64 words, one per lane, one ds_read_b64) at
+// the top of an iteration and decides for itself -- no flag word, no aggregation, no check pass whose result is dropped.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -159,9 +162,10 @@ __host__ __device__ constexpr bool bpl_specialised(int cpt, int mpt, int minw, b
 template <int CPT, int MPT, int MINW, bool EARLY, bool UPRIOR, bool PACKED = false, int PAIRKEY = -1>
 __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocalParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // (a PAIRKEY instance reads m and n where they are used, like the other per-syndrome arguments: held next to B as one
-    // four-dword load, the byte form's register allocation left a dead 16-byte spill slot behind -- a private segment)
-    const int m = PAIRKEY >= 0 ? bpl_args()->m : P.m, n = PAIRKEY >= 0 ? bpl_args()->n : P.n;
+    // (m and n are read where they are used, like the other per-syndrome arguments: held next to B as one four-dword load,
+    // the register allocation left a dead 16-byte spill slot behind -- a private segment -- first in the PAIRKEY instances'
+    // byte form, then in the plain headline instance as well)
+    const int m = bpl_args()->m, n = bpl_args()->n;
 #ifdef BPOSD_DEBUG
     if (blockIdx.x == 0 && threadIdx.x == 0 && (bpl_args()->m != P.m || bpl_args()->counters != P.counters)) __builtin_trap();
 #endif
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
     double* msg_plain = reinterpret_cast<double*>(smem);
     msg_ptr msg = (msg_ptr)msg_plain;
     unsigned int* diffw = reinterpret_cast<unsigned int*>(msg_plain + (size_t)4 * MP + 2);
-    int* sh = reinterpret_cast<int*>(diffw + (MP / 32 + 2));
+    int* sh = reinterpret_cast<int*>(diffw + (MP / 32 + 2));  // control words: [2] the queue ticket, [3] the OSD slot ([0], [1] unused)
     const unsigned int diffw_base = (unsigned int)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)diffw;
 
     // ---- per-thread graph tables
@@ -243,14 +247,22 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
         asm volatile("" : "+s"(w));
         return w != 0;
     };
+    // The whole mismatch bitmap in one LDS read: lane l gets b64 word l mod MP/64 (the lanes past MP/64 read the same words
+    // again -- a broadcast -- so no lane needs a mask or a select), and it is zero iff no lane holds a set bit.  Every wave
+    // reads the same words after the same barrier, so every wave takes the same exit without further synchronisation.
+    // The address is formed where it is used (no register live across the loop).
+    static_assert(MP % 64 == 0 && MP / 64 <= 64 && ((MP / 64) & (MP / 64 - 1)) == 0, "one bitmap word per lane");
+    auto bitmap_word = [&]() -> unsigned long long {
+        unsigned int a = (unsigned int)tid;
+        asm volatile("" : "+v"(a));
+        return *(const volatile __attribute__((address_space(3))) unsigned long long*)(uintptr_t)(diffw_base + ((a & (unsigned int)(MP / 64 - 1)) << 3));
+    };
+    auto bitmap_is_zero = [&](unsigned long long w) -> bool {
+        asm volatile("" : "+v"(w));  // (waited for here, behind whatever was issued after the read)
+        return __ballot(w != 0ull) == 0ull;
+    };
     for (;;) {
-        if (tid == 0) {
-            int zero = 0;
-            asm volatile("" : "+v"(zero));  // (formed here: as a loop-invariant register pair it went to scratch)
-            sh[0] = zero;
-            sh[1] = zero;
-            sh[2] = atomicAdd(&bpl_args()->counters[0], 1);
-        }
+        if (tid == 0) sh[2] = atomicAdd(&bpl_args()->counters[0], 1);
         __syncthreads();
         const long long s = __builtin_amdgcn_readfirstlane(sh[2]);
         if (s >= P.B) {
@@ -270,7 +282,6 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                 const int w0 = ((wave << 6) + j * NT) >> 5;
                 diffw[w0] = (unsigned int)bal;
                 diffw[w0 + 1] = (unsigned int)(bal >> 32);
-                if (bal) sh[0] = 1;
             }
         }
         if (!UPRIOR && bpl_args()->sel) {
@@ -306,13 +317,17 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
         __syncthreads();
 
         int it_done = 0;
-        int conv = __builtin_amdgcn_readfirstlane(sh[0]) == 0 ? 1 : 0;  // (an int in one scalar register, not a lane mask)
+        int conv = bitmap_is_zero(bitmap_word()) ? 1 : 0;  // the zero syndrome (an int in one scalar register, not a lane mask)
         // The iteration loop, as a body per (KEY, LLR).  KEY >= 0: every group of the wave has this key (local_keys.h) and the
         // bit pass is straight-line code (a pair key: group 0 has the uniform key, group 1 the mixed one); KEY < 0: the generic
         // body, one switch per group on its key.  LLR: the body that
         // stores the posterior LLRs (every iteration if out_llr is set, else the last one only); the body without them runs
-        // iterations it0 .. max_iter - 1 and holds no test of it.  Returns 1 once conv / it_done are final.  The control
-        // words are read through readfirstlane (every lane reads the same LDS word), so the exits are scalar branches.
+        // iterations it0 .. max_iter - 1 and holds no test of it.  Returns 1 once conv / it_done are final.
+        // Convergence: the bitmap is final at the barrier that ends a bit pass, and the top of iteration `it` tests all of it
+        // (bitmap_word): zero means the decisions of iteration it - 1 satisfy the syndrome.  The test is a ballot, so the exit
+        // is a scalar branch, and it is the same in every wave.  Nobody writes the bitmap between that barrier and the next
+        // barrier a wave that stays in the loop passes (the one after the check pass), and a wave that leaves passes the two
+        // barriers of the result section before the next syndrome's bits are written: the slowest wave has read by then.
         auto iterate = [&](auto key_c, auto llr_c, const int it0) __attribute__((always_inline)) -> int {
             constexpr int KEY = decltype(key_c)::value;
             constexpr bool LLR = decltype(llr_c)::value;
@@ -320,39 +335,32 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
 #pragma clang loop unroll(disable)
             for (int it = it0; LLR || it < max_iter; ++it) {
                 asm volatile("; bpl_body key=%0 llr=%1" ::"n"(KEY), "n"((int)LLR));  // names the loop in the ISA listing (tools/isa_loop_count.py)
-                const int fi = it & 1;
-                {
-                    // the wave's 64 positions of group j are one aligned pair of bitmap words: one broadcast read per group
-                    // from a wave-uniform address (no per-lane address or mask registers live across the loop)
-                    unsigned long long mis = 0ull;
+                // the bitmap read, then the first check's message loads (all checks' if EARLY), then the test: its LDS round
+                // trip overlaps the loads, which a converged syndrome discards (LDS accesses are volatile: issued in this order)
+                const unsigned long long bw = bitmap_word();
+                double vl[EARLY ? CPT : 1][4];
 #pragma unroll
-                    for (int j = 0; j < CPT; ++j)
-                        mis |= *(const volatile __attribute__((address_space(3))) unsigned long long*)(uintptr_t)(
-                            diffw_base + (unsigned int)(((wave << 6) + j * NT) >> 3));  // (padding positions never raise their bits)
-                    if (lane == 0 && mis) sh[fi] = 1;
+                for (int j = 0; j < (EARLY ? CPT : 1); ++j)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) vl[j][k] = msg[(tid + j * NT) + k * MP];
+                if (bitmap_is_zero(bw)) {  // converged by the decisions of iteration it - 1
+                    conv = 1;
+                    it_done = it - 1;
+                    return 1;
                 }
-                if (LLR && it > max_iter) {
-                    __syncthreads();
-                    conv = __builtin_amdgcn_readfirstlane(sh[fi]) == 0 ? 1 : 0;
+                if (LLR && it > max_iter) {  // the test after the last bit pass has failed
                     it_done = max_iter;
                     return 1;
                 }
-                // =================== check -> bit pass (a4), speculative for it >= 2 ===========
+                // =================== check -> bit pass (a4) ===========
                 const unsigned long long alpha_u = alpha_bits_for_iteration(P.ms_scaling, it);  // scalar instructions
                 const int alpha_lo = (int)(unsigned int)alpha_u, alpha_hi = (int)(unsigned int)(alpha_u >> 32), nalpha_hi = alpha_hi ^ (int)0x80000000;
-                double vl[EARLY ? CPT : 1][4];
-                if (EARLY) {
-#pragma unroll
-                    for (int j = 0; j < CPT; ++j)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) vl[j][k] = msg[(tid + j * NT) + k * MP];
-                }
 #pragma unroll
                 for (int j = 0; j < CPT; ++j) {
                     msg_ptr mc = msg + (tid + j * NT);
                     double v[6];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = EARLY ? vl[j][k] : mc[k * MP];
+                    for (int k = 0; k < 4; ++k) v[k] = (EARLY || j == 0) ? vl[EARLY ? j : 0][k] : mc[k * MP];
                     v[4] = loc[2 * j];
                     v[5] = loc[2 * j + 1];
                     double pre[6], suf[6];
@@ -382,12 +390,6 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                     }
                 }
                 __syncthreads();
-                if (__builtin_amdgcn_readfirstlane(sh[fi]) == 0) {
-                    conv = 1;
-                    it_done = it - 1;
-                    return 1;
-                }
-                if (tid == 0) sh[fi ^ 1] = 0;
                 // ============ bit pass: posterior, decision, bit -> check (a6 / a7) ============
                 // the two LDS messages of every owned bit: all of them up front (latency hidden inside the thread), or,
                 // for the register-capped high-occupancy variant, one group (two bits) at a time
