@@ -32,6 +32,9 @@ EXPORTED_SYMBOLS = (
     "bposd_decode_batch_device_packed",
     "bposd_decode_batch_select",
     "bposd_decode_batch_select_device",
+    "bposd_channel_tables",
+    "bposd_decode_batch_rows",
+    "bposd_decode_batch_rows_device",
     "bposd_pack_rows_device",
     "bposd_pack_rows_device_lane",
     "bposd_synchronize",
@@ -145,6 +148,12 @@ def load():
     lib.bposd_decode_batch_select.restype = C.c_int
     lib.bposd_decode_batch_select_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.bposd_decode_batch_select_device.restype = C.c_int
+    lib.bposd_channel_tables.argtypes = [vp, C.c_int64, vp, vp]
+    lib.bposd_channel_tables.restype = C.c_int
+    lib.bposd_decode_batch_rows.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+    lib.bposd_decode_batch_rows.restype = C.c_int
+    lib.bposd_decode_batch_rows_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.bposd_decode_batch_rows_device.restype = C.c_int
     lib.bposd_pack_rows_device.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
     lib.bposd_pack_rows_device.restype = C.c_int
     lib.bposd_synchronize.argtypes = [vp]

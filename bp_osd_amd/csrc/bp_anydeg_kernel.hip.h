@@ -37,6 +37,7 @@ struct BpAnyParams {
     const double* __restrict__ llr0;      // [n]
     const uint8_t* __restrict__ sel;      // [B, n] nullable
     const double* __restrict__ llr0_alt;  // [n]
+    const double* __restrict__ llr0_rows; // [B, n] nullable: this shot's own priors (wins over sel)
     const int* __restrict__ rp;           // CSR indptr [m + 1]
     const int* __restrict__ ci;           // CSR indices [E]
     const int* __restrict__ cp;           // CSC indptr [n + 1]
@@ -82,8 +83,7 @@ __global__ __launch_bounds__(BPA_NT) void bp_anydeg_kernel(const BpAnyParams P) 
         for (int c = tid; c < m; c += BPA_NT) nz |= (syn[c] & 1) != 0;
         // a3: every edge's bit->check message starts at the prior; decisions = 0
         for (int i = tid; i < n; i += BPA_NT) {
-            double l0 = P.llr0[i];
-            if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+            const double l0 = bp_shot_prior(P, s, n, i);
             for (int k = P.cp[i]; k < P.cp[i + 1]; ++k) msg[P.ce[k]] = l0;
             dec[i] = 0;
             llrt[i] = l0;
@@ -163,8 +163,7 @@ __global__ __launch_bounds__(BPA_NT) void bp_anydeg_kernel(const BpAnyParams P) 
                 }
                 // ---------------- bit pass: posterior, decision, bit -> check (a6 / a7)
                 for (int i = tid; i < n; i += BPA_NT) {
-                    double l0 = P.llr0[i];
-                    if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+                    const double l0 = bp_shot_prior(P, s, n, i);
                     const int k0 = P.cp[i], k1 = P.cp[i + 1];
                     double t = l0;
                     for (int k = k0; k < k1; ++k) {

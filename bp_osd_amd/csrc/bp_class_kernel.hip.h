@@ -67,6 +67,7 @@ struct BpClassParams {
                                   // atomic -- big batches first, single syndromes at the end (2^queue_shift ~ 2 x the grid).  With codes
                                   // of a few hundred bits the chip retires a syndrome every ~25 ns, which is what one same-address
                                   // atomic per syndrome costs.
+    const double* __restrict__ llr0_rows;  // [B, n] nullable: this shot's own priors (wins over sel); last, so that no other argument moves
 };
 
 __host__ __device__ inline size_t bp_class_lds_bytes(int DC, int mp, int ntmax) {
@@ -304,7 +305,13 @@ __global__ __launch_bounds__(NTMAX, MINW) void bp_class_kernel(const BpClassPara
                 if (bal) sh[0] = 1;
             }
         }
-        if (!UPRIOR && bpc_args()->sel) {
+        if (!UPRIOR && bpc_args()->llr0_rows) {  // a channel of its own for every shot: row s of the caller's priors
+#pragma unroll
+            for (int r = 0; r < VPT; ++r) {
+                const int i = BPC_BIT(r);
+                if (i >= 0) l0[r] = bpc_args()->llr0_rows[(size_t)s * n + i];
+            }
+        } else if (!UPRIOR && bpc_args()->sel) {
 #pragma unroll
             for (int r = 0; r < VPT; ++r) {
                 const int i = BPC_BIT(r);

@@ -53,6 +53,7 @@ struct BpParams {
     const double* __restrict__ llr0;    // [n]
     const uint8_t* __restrict__ sel;    // [B, n] nullable: per-syndrome choice between llr0 and llr0_alt
     const double* __restrict__ llr0_alt;  // [n] priors of the alternative channel (used where sel != 0)
+    const double* __restrict__ llr0_rows; // [B, n] nullable: a channel of its own for every syndrome, row s = its priors (wins over sel)
     const int* __restrict__ chk_deg;    // [m]
     int np;             // bit positions = blockDim.x * VPT; position p is owned by thread p % blockDim.x
     const int* __restrict__ pos_bit;    // [np] bit handled at position p, -1 = padding.  The order is chosen by
@@ -78,6 +79,16 @@ struct BpParams {
 __device__ __forceinline__ bool bp_synd_bit(const uint8_t* synd, int packed, long long s, int m, int c) {
     if (packed) return (((const unsigned long long*)synd)[(size_t)s * (size_t)((m + 63) >> 6) + (c >> 6)] >> (c & 63)) & 1ull;
     return (synd[(size_t)s * m + c] & 1) != 0;
+}
+
+// prior LLR of bit i for syndrome s in the kernels that index by bit (bp_large, bp_anydeg, bp_serial): the shot's own row
+// where the call brought rows, else the two-valued choice, else the handle's table
+template <class Params>
+__device__ __forceinline__ double bp_shot_prior(const Params& P, long long s, int n, int i) {
+    if (P.llr0_rows) return P.llr0_rows[(size_t)s * n + i];
+    double l0 = P.llr0[i];
+    if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+    return l0;
 }
 
 // Packed result rows of one syndrome: the workgroup's hard decisions (thread-owned bits, any layout) meet in an LDS bitmap
@@ -224,7 +235,13 @@ __global__ __launch_bounds__(MAXNT, MINW) void bp_kernel(const BpParams P) {
             }
         }
         // ---- per-syndrome two-valued channel (css_decode_sim.py:207-248): pick this shot's priors
-        if (P.sel) {
+        if (P.llr0_rows) {  // ... or a channel of its own for every shot: row s of the caller's priors
+#pragma unroll
+            for (int r = 0; r < VPT; ++r) {
+                const int i = P.pos_bit[tid + r * NT];
+                if (i >= 0) l0[r] = P.llr0_rows[(size_t)s * n + i];
+            }
+        } else if (P.sel) {
 #pragma unroll
             for (int r = 0; r < VPT; ++r) {
                 const int i = P.pos_bit[tid + r * NT];

@@ -54,6 +54,7 @@ struct BpLargeParams {
     const double* __restrict__ llr0;     // [n]
     const uint8_t* __restrict__ sel;     // [B, n] nullable
     const double* __restrict__ llr0_alt; // [n]
+    const double* __restrict__ llr0_rows; // [B, n] nullable: this shot's own priors (wins over sel)
     const int* __restrict__ chk_deg;     // [m]
     const int* __restrict__ var_deg;     // [n]
     const int* __restrict__ var_pos;     // [DV * n], entry d*n+i = k*mp + c
@@ -140,8 +141,7 @@ __global__ __launch_bounds__(bp_large_threads(METHOD)) void bp_large_kernel(cons
             }
         }
         for (int i = tid; i < n; i += NT) {
-            double l0 = P.llr0[i];
-            if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+            const double l0 = bp_shot_prior(P, s, n, i);
             const int deg = P.var_deg[i];
             if (REC || RLDS) {
                 for (int d = 0; d < deg; ++d) {
@@ -273,8 +273,7 @@ __global__ __launch_bounds__(bp_large_threads(METHOD)) void bp_large_kernel(cons
 #pragma clang loop unroll(disable)
                 for (int i = tid; i < n; i += NT) {
                     const int deg = P.var_deg[i];
-                    double l0 = P.llr0[i];
-                    if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+                    const double l0 = bp_shot_prior(P, s, n, i);
                     int pos[DV];
                     double cm[DV], pre[DV];
                     if (RLDS) {

@@ -67,6 +67,7 @@ struct BpLocalParams {
     unsigned long long* __restrict__ iter_total;
     int* __restrict__ tail_flag;  // nullable, host-visible: set to 1 by the workgroup that finds the queue empty (the tail begins)
     int packed_io;  // 1: packed syndromes in, packed result rows out (bp_kernel.hip.h: BpParams::packed_io)
+    const double* __restrict__ llr0_rows;  // [B, n] nullable: this shot's own priors (wins over sel); last, so that no other argument moves
 };
 
 __host__ __device__ inline size_t bp_local_lds_bytes(int mp) {
@@ -284,7 +285,15 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                 diffw[w0 + 1] = (unsigned int)(bal >> 32);
             }
         }
-        if (!UPRIOR && bpl_args()->sel) {
+        if (!UPRIOR && bpl_args()->llr0_rows) {  // a channel of its own for every shot: row s of the caller's priors
+#pragma unroll
+            for (int j = 0; j < CPT; ++j)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    const int i = BPL_BIT(2 * j + b);
+                    if (i >= 0) l0[2 * j + b] = bpl_args()->llr0_rows[(size_t)s * n + i];
+                }
+        } else if (!UPRIOR && bpl_args()->sel) {
 #pragma unroll
             for (int j = 0; j < CPT; ++j)
 #pragma unroll

@@ -39,6 +39,7 @@ struct BpSerialParams {
     const double* __restrict__ llr0;      // [n]
     const uint8_t* __restrict__ sel;      // [B, n] nullable
     const double* __restrict__ llr0_alt;  // [n]
+    const double* __restrict__ llr0_rows; // [B, n] nullable: this shot's own priors (wins over sel)
     const int* __restrict__ rp;           // CSR indptr [m + 1]
     const int* __restrict__ ci;           // CSR indices [E]
     const int* __restrict__ cp;           // CSC indptr [n + 1]
@@ -80,8 +81,7 @@ __global__ __launch_bounds__(BPS_NT) void bp_serial_kernel(const BpSerialParams 
         bool nz = false;
         for (int c = tid; c < m; c += BPS_NT) nz |= (syn[c] & 1) != 0;
         for (int i = tid; i < n; i += BPS_NT) {
-            double l0 = P.llr0[i];
-            if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+            const double l0 = bp_shot_prior(P, s, n, i);
             for (int k = P.cp[i]; k < P.cp[i + 1]; ++k) b2c[P.ce[k]] = l0;
             dec[i] = 0;
             llrt[i] = l0;
@@ -98,8 +98,7 @@ __global__ __launch_bounds__(BPS_NT) void bp_serial_kernel(const BpSerialParams 
                     const int lo = P.lvl_ptr[lv], hi = P.lvl_ptr[lv + 1];
                     for (int q = lo + tid; q < hi; q += BPS_NT) {
                         const int i = P.lvl_bits[q];
-                        double l0 = P.llr0[i];
-                        if (P.sel && P.sel[(size_t)s * n + i]) l0 = P.llr0_alt[i];
+                        const double l0 = bp_shot_prior(P, s, n, i);
                         double llr = l0;
                         double c2b[BPS_MAXDV];
                         const int k0 = P.cp[i], deg = P.cp[i + 1] - k0;

@@ -190,6 +190,18 @@ int launch_unpack(bposd_handle* h, hipStream_t st, const unsigned long long* d_w
 
 }  // namespace
 
+// [0, count) cut into equal slices for at most min(16, hardware threads) host threads (one below 64 K items); f(lo, hi)
+template <class F>
+static void parallel_slices(size_t count, F f) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const size_t nt = std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)(hw ? hw : 1), count / 65536 + 1}));
+    if (nt == 1) { f((size_t)0, count); return; }
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < nt; ++t) pool.emplace_back(f, count * t / nt, count * (t + 1) / nt);
+    f((size_t)0, count / nt);
+    for (auto& th : pool) th.join();
+}
+
 // ================================================================================ C-ABI
 extern "C" {
 
@@ -213,7 +225,7 @@ void bposd_destroy(bposd_handle* h) {
         if (l.copy_stream) (void)hipStreamDestroy(l.copy_stream);
         for (DevBuf* b : {&l.io_cmp0, &l.io_cmpw, &l.io_psynd, &l.io_posdw, &l.io_posd0, &l.io_pbp, &l.io_pcmp}) release(*b);
         for (DevBuf* b : {&l.bpl_msg, &l.bpl_llr, &l.osdl_ws, &l.io_sel, &l.osd_rows_ws, &l.llr_ws, &l.osd_list, &l.io_synd, &l.io_osdw,
-                          &l.io_osd0, &l.io_bp, &l.io_conv, &l.io_iters, &l.io_llr})
+                          &l.io_osd0, &l.io_bp, &l.io_conv, &l.io_iters, &l.io_llr, &l.io_l0rows, &l.io_costrows})
             release(*b);
         for (void* p : {(void*)l.d_counters, (void*)l.d_osd_dbg})  // (d_iter_total lives inside the d_counters block)
             if (p) (void)hipFree(p);
@@ -222,6 +234,7 @@ void bposd_destroy(bposd_handle* h) {
         if (l.h_tail) (void)hipHostFree(l.h_tail);
         if (l.d_alt) (void)hipFree(l.d_alt);
         if (l.h_alt) (void)hipHostFree(l.h_alt);
+        if (l.h_rows) (void)hipHostFree(l.h_rows);
         if (l.ev_alt) (void)hipEventDestroy(l.ev_alt);
         if (l.ev_bp) (void)hipEventDestroy(l.ev_bp);
         if (l.ev_osd) (void)hipEventDestroy(l.ev_osd);
@@ -584,7 +597,16 @@ struct IoPtrs {
     uint8_t *osdw = nullptr, *osd0 = nullptr, *bp = nullptr, *conv = nullptr;
     int32_t* iters = nullptr;
     double* llr = nullptr;
+    // a channel of its own for every syndrome (bposd_decode_batch_rows*): rows [B, n] of prior LLRs and of OSD-W weights
+    // as bposd_channel_tables makes them; cost_rows is null where OSD does not weigh candidates
+    const double* llr0_rows = nullptr;
+    const double* cost_rows = nullptr;
 };
+
+// Does this handle's OSD stage rank candidates by the channel's weights (else per-shot weight rows are never read)?
+static bool osd_weighs_candidates(const bposd_handle* h) {
+    return h->cfg.osd_method >= BPOSD_OSD_E && h->cfg.osd_order > 0 && h->cfg.weight_fn == 0;
+}
 
 // What every decode entry point checks before anything is enqueued (B == 0 is a valid call that does nothing).
 static int check_batch(bposd_handle* h, int64_t B, const void* synd, const void* osdw) {
@@ -637,6 +659,7 @@ static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoP
     P.llr0 = h->d_llr0;
     P.sel = io.sel;
     P.llr0_alt = call.lane_alt ? L.d_alt : h->d_llr0_alt;
+    P.llr0_rows = io.llr0_rows;
     P.chk_deg = h->d_chk_deg;
     P.var_deg = h->d_var_deg;
     P.var_pos = h->d_var_pos;
@@ -714,7 +737,8 @@ static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoP
         Q.cmp_osdw = call.cmp_osdw;
         Q.dbg = nullptr;
         Q.packed_io = call.packed ? 1 : 0;
-        Q.cost = (h->fp_weights || (io.sel && h->cfg.weight_fn == 0)) ? h->d_cost : nullptr;
+        Q.cost = (h->fp_weights || ((io.sel || io.cost_rows) && h->cfg.weight_fn == 0)) ? h->d_cost : nullptr;  // (non-null = the fp64 weight path)
+        Q.cost_rows = h->cfg.weight_fn == 0 ? io.cost_rows : nullptr;
         Q.sel = io.sel;
         Q.cost_alt = call.lane_alt ? L.d_alt + h->n : h->d_cost_alt;
         const char* dbg_env = getenv("BPOSD_OSD_DEBUG");
@@ -812,12 +836,7 @@ static int check_alt_channel(bposd_handle* h, const double* alt) {
     return 0;
 }
 
-static void alt_channel_tables(int n, const double* alt, double* l0, double* cost) {
-    for (int i = 0; i < n; ++i) {
-        l0[i] = std::log((1 - alt[i]) / alt[i]);
-        cost[i] = std::log(1 / alt[i]);
-    }
-}
+static void alt_channel_tables(int n, const double* alt, double* l0, double* cost) { (void)channel_tables(alt, n, l0, cost); }
 
 static int upload_alt_channel(bposd_handle* h, const double* alt) {
     { int rca = check_alt_channel(h, alt); if (rca) return rca; }
@@ -859,7 +878,53 @@ int bposd_decode_batch_select_device(bposd_handle* h, const uint8_t* d_synd, int
     return decode_device_impl(h, call, IoPtrs{d_synd, d_sel, d_osdw, d_osd0, d_bp, d_conv, d_iters, d_llr}, B);
 }
 
-static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed = false, bool bp_only = false);
+static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed = false, bool bp_only = false,
+                            const double* prob_rows = nullptr);
+
+int bposd_channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost) {
+    if (count < 0 || (count > 0 && !probs)) return fail(nullptr, BPOSD_ERR_INVALID, "bposd_channel_tables: probs and a count >= 0 are required");
+    if (const int64_t bad = channel_tables(probs, count, prior_llr, cost))
+        return fail(nullptr, BPOSD_ERR_INVALID, "probs[%lld] = %g is not a probability", (long long)(bad - 1), probs[bad - 1]);
+    return BPOSD_OK;
+}
+
+/* A channel of its own for every syndrome, device-pointer form: the rows replace the handle's channel for this call only. */
+int bposd_decode_batch_rows_device(bposd_handle* h, const uint8_t* d_synd, int64_t B, const double* d_prior_llr_rows,
+                                   const double* d_cost_rows, uint8_t* d_osdw, uint8_t* d_osd0, uint8_t* d_bp,
+                                   uint8_t* d_conv, int32_t* d_iters, double* d_llr) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (!d_prior_llr_rows) return fail(h, BPOSD_ERR_INVALID, "prior_llr_rows is required");
+    const bool weighs = h->cfg.osd_method != BPOSD_OSD_OFF && osd_weighs_candidates(h);
+    if (weighs && !d_cost_rows) return fail(h, BPOSD_ERR_INVALID, "cost_rows is required: this handle's OSD stage weighs its candidates with the channel");
+    if (const int rc = check_batch(h, B, d_synd, d_osdw); rc || B == 0) return rc;
+    IoPtrs io{d_synd, nullptr, d_osdw, d_osd0, d_bp, d_conv, d_iters, d_llr};
+    io.llr0_rows = d_prior_llr_rows;
+    io.cost_rows = weighs ? d_cost_rows : nullptr;
+    return decode_device_impl(h, take_next_lane(h), io, B);
+}
+
+/* The same with host pointers: channel_probs_rows [B, n] are error probabilities, validated before anything is enqueued. */
+int bposd_decode_batch_rows(bposd_handle* h, const uint8_t* synd, int64_t B, const double* channel_probs_rows, uint8_t* osdw,
+                            uint8_t* osd0, uint8_t* bp, uint8_t* conv, int32_t* iters, double* llr) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (!channel_probs_rows) return fail(h, BPOSD_ERR_INVALID, "channel_probs_rows is required");
+    if (const int rc = check_batch(h, B, synd, osdw); rc || B == 0) return rc;
+    const size_t total = (size_t)B * (size_t)h->n;
+    std::mutex mu;
+    size_t first_bad = total;
+    parallel_slices(total, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i)
+            if (!(channel_probs_rows[i] >= 0.0 && channel_probs_rows[i] <= 1.0)) {
+                std::lock_guard<std::mutex> g(mu);
+                first_bad = std::min(first_bad, i);
+                return;
+            }
+    });
+    if (first_bad < total)
+        return fail(h, BPOSD_ERR_INVALID, "channel_probs_rows[%lld][%d] = %g is not a probability", (long long)(first_bad / h->n),
+                    (int)(first_bad % h->n), channel_probs_rows[first_bad]);
+    return decode_host_impl(h, IoPtrs{synd, nullptr, osdw, osd0, bp, conv, iters, llr}, B, false, false, channel_probs_rows);
+}
 
 int bposd_decode_batch(bposd_handle* h, const uint8_t* synd, int64_t B, uint8_t* osdw, uint8_t* osd0,
                        uint8_t* bp, uint8_t* conv, int32_t* iters, double* llr) {
@@ -947,7 +1012,14 @@ static int download_rows(bposd_handle* h, hipStream_t st, const IoPtrs& host, si
 // word i >> 6 = entry i) -- one eighth of the bytes over PCIe; the device unpacks the syndromes in front of the BP kernel and
 // packs the result rows behind it (sel and llr are not offered in this form).
 // bp_only (bposd_posterior_llr): no OSD stage, no OSD list, on the small path and on every chunk alike.
-static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed, bool bp_only) {
+// prob_rows (bposd_decode_batch_rows; validated by the caller): [B, n] error probabilities, a channel per syndrome.  Each
+// chunk's rows are converted on the host (bposd_channel_tables' routine, a few threads) into the lane's page-locked block
+// and uploaded next to the syndromes; the weight rows only where the OSD stage reads them.
+static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed, bool bp_only, const double* prob_rows) {
+    const bool rows_cost = prob_rows && !bp_only && h->cfg.osd_method != BPOSD_OSD_OFF && osd_weighs_candidates(h);
+    auto convert_rows = [&](const double* src, size_t count, double* l0, double* cost) {
+        parallel_slices(count, [&](size_t lo, size_t hi) { (void)channel_tables(src + lo, (int64_t)(hi - lo), l0 + lo, cost ? cost + lo : nullptr); });
+    };
     if (const int rc0 = check_batch(h, B, host.synd, host.osdw); rc0 || B == 0) return rc0;
     DeviceGuard dev_guard(h->device);
     HIP_TRY(h, dev_guard.err);
@@ -963,7 +1035,8 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
         const size_t o_syn = 0, o_sel = o_syn + a64(b8 * m8), o_osdw = o_sel + (host.sel ? a64(b8 * n8) : 0),
                      o_osd0 = o_osdw + a64(b8 * n8), o_bp = o_osd0 + (host.osd0 ? a64(b8 * n8) : 0),
                      o_conv = o_bp + (host.bp ? a64(b8 * n8) : 0), o_it = o_conv + a64(b8), o_llr = o_it + a64(b8 * 4),
-                     total = o_llr + (host.llr ? a64(b8 * n8 * 8) : 0);
+                     o_r0 = o_llr + (host.llr ? a64(b8 * n8 * 8) : 0), o_rc = o_r0 + (prob_rows ? a64(b8 * n8 * 8) : 0),
+                     total = o_rc + (rows_cost ? a64(b8 * n8 * 8) : 0);
         if (zero_copy && !packed && total <= (size_t)1 << 20) {
             Lane& L = h->lanes[0];
             if (L.h_stage_bytes < total) {
@@ -977,13 +1050,16 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
             unsigned char* st = (unsigned char*)L.h_stage;
             memcpy(st + o_syn, host.synd, b8 * m8);
             if (host.sel) memcpy(st + o_sel, host.sel, b8 * n8);
+            if (prob_rows) convert_rows(prob_rows, b8 * n8, (double*)(st + o_r0), rows_cost ? (double*)(st + o_rc) : nullptr);
             DecodeCall call{&L, &h->rec[0]};
             call.bp_only = bp_only;
             call.lean = !getenv("BPOSD_OSD_DEBUG");
             call.osd_stream = call.lean ? L.stream : L.osd_stream;
-            int rcz = decode_device_impl(h, call, IoPtrs{st + o_syn, host.sel ? st + o_sel : nullptr, st + o_osdw, host.osd0 ? st + o_osd0 : nullptr,
-                                                         host.bp ? st + o_bp : nullptr, st + o_conv, (int32_t*)(st + o_it),
-                                                         host.llr ? (double*)(st + o_llr) : nullptr}, B);
+            IoPtrs zio{st + o_syn, host.sel ? st + o_sel : nullptr, st + o_osdw, host.osd0 ? st + o_osd0 : nullptr,
+                       host.bp ? st + o_bp : nullptr, st + o_conv, (int32_t*)(st + o_it), host.llr ? (double*)(st + o_llr) : nullptr};
+            if (prob_rows) zio.llr0_rows = (const double*)(st + o_r0);
+            if (rows_cost) zio.cost_rows = (const double*)(st + o_rc);
+            int rcz = decode_device_impl(h, call, zio, B);
             if (rcz) { (void)sync_all_lanes(h); return rcz; }
             h->nrec = 1;
             if (!call.lean) { rcz = sync_all_lanes(h); if (rcz) return rcz; }
@@ -1001,6 +1077,8 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
     // 8 chunks 35.6 ms -- a lane's next chunk waits for the previous one's OSD kernel and download, and every chunk pays
     // its own straggler tail -- 2 chunks 33.0 ms), at most BPOSD_MAX_CHUNKS; BPOSD_HOST_CHUNK overrides the target size.
     long long target = 32768;
+    // (a channel row per shot is 16 n bytes next to the syndrome's m: chunks of ~64 MB of rows bound what a lane stages)
+    if (prob_rows) target = std::min<long long>(target, std::max<long long>(1024, ((long long)64 << 20) / (16LL * h->n)));
     if (const char* e = getenv("BPOSD_HOST_CHUNK")) target = std::max(1LL, atoll(e));
     int nchunks = (int)std::min<long long>(BPOSD_MAX_CHUNKS, std::max<long long>(1, (B + target / 2) / target));
     if (h->large) nchunks = (int)std::min<long long>(nchunks, std::max<long long>(1, B / (4LL * h->num_cu)));
@@ -1091,8 +1169,27 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
             if ((rc = ensure(h, L.io_sel, (size_t)CH * n))) return rc;
             HIP_TRY(h, hipMemcpyAsync(L.io_sel.p, host.sel + (size_t)lo * n, bn, hipMemcpyHostToDevice, L.stream));
         }
+        if (prob_rows) {  // (the lane's previous chunk has been drained above: its staging block is free)
+            const size_t cap = (size_t)CH * n, want = cap * (rows_cost ? 2 : 1);
+            if ((rc = ensure(h, L.io_l0rows, sizeof(double) * cap))) return rc;
+            if (rows_cost && (rc = ensure(h, L.io_costrows, sizeof(double) * cap))) return rc;
+            if (L.h_rows_cap < want) {
+                if (L.h_rows) (void)hipHostFree(L.h_rows);
+                L.h_rows = nullptr; L.h_rows_cap = 0;
+                HIP_TRY(h, hipHostMalloc((void**)&L.h_rows, sizeof(double) * want, hipHostMallocDefault));
+                L.h_rows_cap = want;
+            }
+            convert_rows(prob_rows + (size_t)lo * n, bn, L.h_rows, rows_cost ? L.h_rows + cap : nullptr);
+            HIP_TRY(h, hipMemcpyAsync(L.io_l0rows.p, L.h_rows, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
+            if (rows_cost) HIP_TRY(h, hipMemcpyAsync(L.io_costrows.p, L.h_rows + cap, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
+        }
         HIP_TRY(h, hipEventRecord(L.ev_up, L.stream));
-        const IoPtrs dev = lane_ptrs(L, native, host), wire = lane_ptrs(L, packed, host);
+        IoPtrs dev = lane_ptrs(L, native, host);
+        const IoPtrs wire = lane_ptrs(L, packed, host);
+        if (prob_rows) {
+            dev.llr0_rows = (const double*)L.io_l0rows.p;
+            dev.cost_rows = rows_cost ? (const double*)L.io_costrows.p : nullptr;
+        }
         if (wire.synd != dev.synd && (rc = launch_unpack(h, L.stream, (const unsigned long long*)wire.synd, cnt, (int)m, (uint8_t*)dev.synd))) return rc;
         // Chunk c's kernels are released when chunk c - 1's BP kernel has handed out its last syndrome (its tail begins; the
         // flag is written by that kernel into page-locked memory) or has ended: the chunks then run in order, each filling

@@ -56,11 +56,24 @@ bool pick_pair(int dc, int dv, DegPair* out) {
     return false;
 }
 
+// The one place that turns error probabilities into what the kernels read (bposd_channel_tables):
+// a3: prior LLR = log((1 - p) / p), a11: weight = log(1 / p), evaluated on the host in fp64 (same libm call the CPU path
+// makes) so that device arithmetic is add / compare / multiply only.  The handle's channel, the alternative channel and
+// the per-shot rows all come from here, which is what makes a row equal update_channel_probs with that row bit for bit.
+// Either output may be null.  Returns the index of the first value that is no probability + 1, 0 if there is none.
+int64_t channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost) {
+    for (int64_t i = 0; i < count; ++i)
+        if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return i + 1;
+    if (prior_llr)
+        for (int64_t i = 0; i < count; ++i) prior_llr[i] = std::log((1 - probs[i]) / probs[i]);
+    if (cost)
+        for (int64_t i = 0; i < count; ++i) cost[i] = std::log(1 / probs[i]);
+    return 0;
+}
+
 int upload_priors(bposd_handle* h) {
-    // a3: prior LLR = log((1 - p) / p), evaluated on the host in fp64 (same libm call the
-    // CPU path makes) so that device arithmetic is add / compare / multiply only.
-    std::vector<double> l0(h->n);
-    for (int i = 0; i < h->n; ++i) l0[i] = std::log((1 - h->probs[i]) / h->probs[i]);
+    std::vector<double> l0(h->n), cost(h->n);
+    if (channel_tables(h->probs.data(), h->n, l0.data(), cost.data())) return fail(h, BPOSD_ERR_INVALID, "channel_probs holds a value that is not a probability");
     HIP_TRY(h, hipMemcpy(h->d_llr0, l0.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
     h->probs_uniform = true;
     for (int i = 1; i < h->n; ++i)
@@ -68,8 +81,6 @@ int upload_priors(bposd_handle* h) {
     // a11: weight(x) = sum over set bits of log(1/p_i) (ldpc v2).  For a uniform 0 < p < 1 every term is
     // the same positive number, so the sums order candidates exactly like Hamming weights (identical
     // partial sums, strictly increasing in the count) and the integer path is used.
-    std::vector<double> cost(h->n);
-    for (int i = 0; i < h->n; ++i) cost[i] = std::log(1 / h->probs[i]);
     HIP_TRY(h, hipMemcpy(h->d_cost, cost.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
     h->fp_weights = (h->cfg.weight_fn == 0) &&
                     !(h->probs_uniform && h->probs[0] > 0.0 && h->probs[0] < 1.0);

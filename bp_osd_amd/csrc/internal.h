@@ -45,6 +45,11 @@ struct Lane {
     DevBuf osdl_ws;           // large OSD workspaces (matrix, sort keys, pivots, weights) carved from one allocation
     DevBuf osd_rows_ws;       // OSD kernel's per-workgroup spill area for finished row words
     DevBuf llr_ws, osd_list, io_synd, io_osdw, io_osd0, io_bp, io_conv, io_iters, io_llr, io_sel;
+    // host-pointer calls with a channel row per shot (bposd_decode_batch_rows): the chunk's prior and weight rows, [chunk][n]
+    // doubles each, and the page-locked block the host converts the caller's probabilities into before the upload
+    DevBuf io_l0rows, io_costrows;
+    double* h_rows = nullptr;
+    size_t h_rows_cap = 0;           // doubles
     // host-pointer calls: the outputs are downloaded on a copy stream of the lane's own right after the BP kernel (event-
     // ordered), the rows the OSD kernel rewrites come from compact copies [list slot][n] once it has run
     DevBuf io_cmp0, io_cmpw;
@@ -192,6 +197,7 @@ struct DegPair { int dc, dv; };
 bool pick_pair(int dc, int dv, DegPair* out);  // the compiled bp_kernel degree pair that covers (dc, dv)
 int gf2_rank_host(int m, int n, const std::vector<int>& rp, const std::vector<int>& ci);
 int upload_priors(bposd_handle* h);
+int64_t channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost);  // bposd_channel_tables
 int probe_rank_large(bposd_handle* h, const DecodeCall& call, int* rank);
 int num_candidates(const bposd_handle* h);
 

@@ -35,7 +35,7 @@ int launch_bp_local(bposd_handle* h, const DecodeCall& call, const BpParams& P) 
     BpLocalParams L{};
     L.m = P.m; L.n = P.n; L.B = P.B; L.max_iter = P.max_iter; L.ms_scaling = P.ms_scaling; L.osd_enabled = P.osd_enabled;
     L.mp = h->local_mp;
-    L.synd = P.synd; L.llr0 = P.llr0; L.sel = P.sel; L.llr0_alt = P.llr0_alt;
+    L.synd = P.synd; L.llr0 = P.llr0; L.sel = P.sel; L.llr0_alt = P.llr0_alt; L.llr0_rows = P.llr0_rows;
     L.pos_chk = h->d_lpos_chk; L.pos_bit = h->d_lpos_bit; L.pos_alo = h->d_lpos_alo; L.pos_ahi = h->d_lpos_ahi;
     L.grp_dl = h->d_lgrp_dl; L.pos_dl = h->d_lpos_dl;
     L.out_bp = P.out_bp; L.out_osd0 = P.out_osd0; L.out_osdw = P.out_osdw; L.out_conv = P.out_conv; L.out_iters = P.out_iters;
@@ -50,7 +50,7 @@ int launch_bp_local(bposd_handle* h, const DecodeCall& call, const BpParams& P) 
     if (h->bp_variant == 20) return launch_bp_local_t<2, 1024, 6, true>(h, call, L);    // as the default with early check-pass loads
     if (h->bp_variant == 21) return launch_bp_local_t<4, 1024, 3, true>(h, call, L);    // 256 threads, <= 168 VGPRs: 3 workgroups per CU
     // one finite positive prior for every bit: it can live in scalar registers (positive: the padding positions share it)
-    const bool uprior = h->probs_uniform && !L.sel && h->probs[0] > 0.0 && h->probs[0] < 0.5;
+    const bool uprior = h->probs_uniform && !L.sel && !L.llr0_rows && h->probs[0] > 0.0 && h->probs[0] < 0.5;
     // Small calls are latency-bound (a max_iter straggler runs ~2000 dependent iterations, a lone syndrome ~60): one check
     // per thread (16 waves per syndrome) iterates 25-30 % faster per syndrome, two checks per thread (4 workgroups per
     // CU) have the higher throughput.  Measured crossover on the [[1922,50]] code: 32768 syndromes per call (2048: 2.5

@@ -27,7 +27,7 @@ int launch_osd_large(bposd_handle* h, const DecodeCall& call, const OsdParams& P
     Q.packed_io = P.packed_io; Q.out_osd0 = P.out_osd0; Q.out_osdw = P.out_osdw; Q.cmp_osd0 = P.cmp_osd0; Q.cmp_osdw = P.cmp_osdw; Q.rank_out = d_rank_out; Q.dbg = P.dbg;
     // fp64 index-order candidate weights (non-uniform channel) -- only OSD-E / OSD-CS rank candidates
     const bool fpw = P.cost != nullptr && Q.osd_method >= BPOSD_OSD_E && Q.osd_order > 0;
-    Q.cost = fpw ? P.cost : nullptr; Q.sel = fpw ? P.sel : nullptr; Q.cost_alt = P.cost_alt;
+    Q.cost = fpw ? P.cost : nullptr; Q.sel = fpw ? P.sel : nullptr; Q.cost_alt = P.cost_alt; Q.cost_rows = fpw ? P.cost_rows : nullptr;
     Q.wdn = std::max(64 * Q.W, 1 << OSDL_MAXSPAN);
     long long grid = std::min<long long>(B, h->num_cu);
     if (grid < 1) grid = 1;

@@ -86,6 +86,7 @@ struct OsdParams {
                                        // (ldpc v2 weight function with non-uniform channel_probs)
     const uint8_t* __restrict__ sel;   // [B, n] nullable: per-syndrome choice between cost and cost_alt
     const double* __restrict__ cost_alt;
+    const double* __restrict__ cost_rows;  // [B, n] nullable: log(1/p) of every syndrome's own channel (wins over sel; cost is then non-null too)
     unsigned long long* __restrict__ rows_ws;  // [gridDim.x][W][blockDim.x * RPT] finished row words
     long long* __restrict__ dbg;       // nullable: 8 phase timestamps (s_memtime) of list slot 0
     int packed_io;  // 1: synd is [B][ceil(m/64)] and out_osd0 / out_osdw / cmp_* are rows of ceil(n/64) little-endian 64-bit words
@@ -812,7 +813,9 @@ __global__ __launch_bounds__(64 * OSD_MAXW) void osd_kernel(const OsdParams P) {
                 for (int k = 0; k < RPT; ++k) am[tid + k * NT] = amask[k];
                 for (int i = tid; i < n; i += NT) {
                     double ci = P.cost[i];
-                    if (P.sel) {  // per-syndrome two-valued channel (css_decode_sim.py:207-248)
+                    if (P.cost_rows) {  // a channel of its own for every shot: row s of the caller's weights
+                        ci = P.cost_rows[(size_t)s * n + i];
+                    } else if (P.sel) {  // per-syndrome two-valued channel (css_decode_sim.py:207-248)
                         const unsigned int pick = P.sel[(size_t)s * n + i];
                         const double ca = P.cost_alt[i];
                         if (pick != 0u) ci = ca;

@@ -142,6 +142,7 @@ struct OsdLargeParams {
     const double* __restrict__ cost;        // [n] log(1/p_i), nullable
     const uint8_t* __restrict__ sel;        // [B, n] nullable: per-syndrome choice between cost and cost_alt
     const double* __restrict__ cost_alt;    // [n]
+    const double* __restrict__ cost_rows;   // [B, n] nullable: every syndrome's own weights (wins over sel; cost is then non-null too)
     double* __restrict__ costs_ws;          // [grid][n]   this syndrome's per-bit costs
     unsigned long long* __restrict__ colvec_ws;  // [grid][OSDL_MAXSPAN_CS][RPT * OSDL_NW] reduced columns when osd_cs order > 16
     double* __restrict__ wd_ws;             // [grid][wdn] weights of the single candidates / of the osd_e patterns
@@ -2096,7 +2097,9 @@ __global__ __launch_bounds__(OSDL_NT) void osd_large_kernel(const OsdLargeParams
                 OSDL_FRESH_TID();
                 for (int i = tid; i < n; i += NT) {
                     double ci = P.cost[i];
-                    if (P.sel) {  // per-syndrome two-valued channel (css_decode_sim.py:207-248)
+                    if (P.cost_rows) {  // a channel of its own for every shot: row s of the caller's weights
+                        ci = P.cost_rows[(size_t)s * n + i];
+                    } else if (P.sel) {  // per-syndrome two-valued channel (css_decode_sim.py:207-248)
                         const double ca = P.cost_alt[i];
                         if (P.sel[(size_t)s * n + i] != 0) ci = ca;
                     }

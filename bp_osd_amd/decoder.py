@@ -259,8 +259,19 @@ class BpOsdDecoder:
         self._hold(lane, s, osdw_words, osd0_words, bp_words, converged, iters)
         return lane
 
+    @staticmethod
+    def channel_tables(probs):
+        """``(prior_llr, cost)`` of error probabilities of any shape: ``log((1 - p) / p)`` and ``log(1 / p)`` as the library
+        computes them for every channel it is given (``bposd_channel_tables``; host only) -- the rows
+        :meth:`decode_batch_device` takes as ``d_prior_llr_rows`` / ``d_cost_rows``.  ValueError for a value outside [0, 1] or a NaN."""
+        p = np.ascontiguousarray(probs, dtype=np.float64)
+        llr, cost = np.empty(p.shape, np.float64), np.empty(p.shape, np.float64)
+        lib = _lib.load()
+        _lib.check(lib, None, lib.bposd_channel_tables(p.ctypes.data, p.size, llr.ctypes.data, cost.ctypes.data))
+        return llr, cost
+
     def decode_batch(self, syndromes, want_osd0=True, want_bp=True, want_llr=False, prior_select=None,
-                     alt_channel_probs=None, packed=False):
+                     alt_channel_probs=None, packed=False, channel_probs_rows=None):
         """Decode B syndromes (array [B, m], any integer dtype).  Returns the OSD-W (or BP, when BP
         converged) corrections as uint8 [B, n]; per-row ``batch_converge``, ``batch_iter`` and, if
         requested, ``batch_osd0`` / ``batch_bp`` / ``batch_llr`` are left on the object.
@@ -272,8 +283,14 @@ class BpOsdDecoder:
         ``prior_select`` (uint8 [B, n]) with ``alt_channel_probs`` (n floats) gives every shot its own
         two-valued channel: bit i of shot b uses ``alt_channel_probs[i]`` where ``prior_select[b, i]`` is
         set and the decoder's ``channel_probs[i]`` elsewhere -- the batched form of the per-shot
-        ``update_channel_probs`` of css_decode_sim.py:207-248."""
+        ``update_channel_probs`` of css_decode_sim.py:207-248.
+
+        ``channel_probs_rows`` (float64 [B, n]) gives every shot a channel of its own: shot b is decoded exactly as
+        ``update_channel_probs(channel_probs_rows[b])`` followed by ``decode(syndromes[b])`` would, in one call; the
+        decoder's own channel is untouched.  Not combinable with ``prior_select`` or ``packed``."""
         self._timing_override = None
+        if channel_probs_rows is not None and (prior_select is not None or packed):
+            raise ValueError("channel_probs_rows cannot be combined with prior_select or packed=True")
         if packed:
             if want_llr or prior_select is not None:
                 raise ValueError("packed=True offers the integer outputs only (no want_llr, no prior_select)")
@@ -324,6 +341,12 @@ class BpOsdDecoder:
             else:
                 rc = self._lib.bposd_decode_batch_select(self._h, s8.ctypes.data, B, sel.ctypes.data, alt.ctypes.data,
                                                          ptr(osdw), ptr(osd0), ptr(bp), ptr(conv), ptr(iters), ptr(llr))
+        elif channel_probs_rows is not None:
+            rows = np.ascontiguousarray(channel_probs_rows, dtype=np.float64)
+            if rows.shape != (B, self.n):
+                raise ValueError(f"channel_probs_rows must have shape ({B}, {self.n}), not {rows.shape}")
+            rc = 0 if B == 0 else self._lib.bposd_decode_batch_rows(self._h, s8.ctypes.data, B, rows.ctypes.data, ptr(osdw), ptr(osd0),
+                                                                    ptr(bp), ptr(conv), ptr(iters), ptr(llr))
         else:
             rc = self._lib.bposd_decode_batch(self._h, s8.ctypes.data, B, ptr(osdw), ptr(osd0), ptr(bp),
                                               ptr(conv), ptr(iters), ptr(llr))
@@ -462,13 +485,24 @@ class BpOsdDecoder:
         return llr[0].copy()
 
     def decode_batch_device(self, d_syndromes, B, d_osdw, d_osd0=None, d_bp=None, d_converged=None,
-                            d_iters=None, d_llr=None, d_prior_select=None, alt_channel_probs=None):
+                            d_iters=None, d_llr=None, d_prior_select=None, alt_channel_probs=None,
+                            d_prior_llr_rows=None, d_cost_rows=None):
         """Asynchronous decode on device pointers (ints, e.g. ``tensor.data_ptr()``) that live on this
         decoder's device; call :meth:`synchronize` before reading the outputs.  ``d_prior_select`` (device uint8
         [B, n]) with ``alt_channel_probs`` (host array of n floats) is the per-shot two-valued channel of
-        :meth:`decode_batch`."""
+        :meth:`decode_batch`.  ``d_prior_llr_rows`` / ``d_cost_rows`` (device float64 [B, n], the two arrays of
+        :meth:`channel_tables`) give every shot a channel of its own; ``d_cost_rows`` may be None where OSD does not weigh
+        candidates with the channel (``osd_off``, ``osd_0``, order 0, ``weight_fn=1``).  The rows stay the caller's and
+        unchanged until :meth:`synchronize`."""
         self._timing_override = None
-        if d_prior_select is not None:
+        if d_prior_llr_rows is not None:
+            if d_prior_select is not None:
+                raise ValueError("d_prior_llr_rows cannot be combined with d_prior_select")
+            rc = self._lib.bposd_decode_batch_rows_device(self._h, d_syndromes, int(B), d_prior_llr_rows, d_cost_rows, d_osdw, d_osd0,
+                                                          d_bp, d_converged, d_iters, d_llr)
+        elif d_cost_rows is not None:
+            raise ValueError("d_cost_rows needs d_prior_llr_rows")
+        elif d_prior_select is not None:
             if alt_channel_probs is None:
                 raise ValueError("alt_channel_probs is required with d_prior_select")
             alt = np.ascontiguousarray(alt_channel_probs, dtype=np.float64)

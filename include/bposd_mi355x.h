@@ -183,6 +183,36 @@ int bposd_decode_batch_select_device(bposd_handle *h, const uint8_t *d_syndromes
                                      uint8_t *d_converged, int32_t *d_iters, double *d_llr);
 
 /*
+ * What the kernels read of a channel: prior_llr[i] = log((1 - p_i) / p_i) and cost[i] = log(1 / p_i) for count
+ * probabilities, with the host's libm -- the one routine behind bposd_create, bposd_update_channel_probs, the alternative
+ * channel of the select calls and the rows of the calls below, so all of them agree bit for bit.  Host only: no handle, no
+ * device.  Either output may be NULL.  BPOSD_ERR_INVALID (text: bposd_last_error(NULL)) for a value outside [0, 1] or a NaN;
+ * nothing is written then.
+ */
+int bposd_channel_tables(const double *probs, int64_t count, double *prior_llr, double *cost);
+
+/*
+ * A channel of its own for every syndrome: syndrome b is decoded with the error probabilities
+ * channel_probs_rows[b*n .. b*n + n) (BP priors and OSD-W weights alike), exactly as
+ * `.update_channel_probs(row b)` followed by `.decode(syndrome b)` would -- soft-information readout, graded erasures,
+ * drifting noise, windowed decoding.  The rows replace the handle's channel for this call only; the handle's own tables
+ * and its alternative channel are untouched.  Host-pointer form, synchronous, same outputs as bposd_decode_batch_select.
+ * Every value is validated before anything is enqueued (the error text names the first offending shot and bit); the rows
+ * are converted chunk by chunk on a few host threads and staged per lane as fp64 prior rows plus, where the OSD stage
+ * weighs candidates with the channel (osd_e / osd_cs of order > 0 with weight_fn 0), fp64 weight rows.  Not offered
+ * together with select, nor in the bit-packed form.
+ */
+int bposd_decode_batch_rows(bposd_handle *h, const uint8_t *syndromes, int64_t B, const double *channel_probs_rows,
+                            uint8_t *osdw, uint8_t *osd0, uint8_t *bp, uint8_t *converged, int32_t *iters, double *llr);
+
+/* Device-pointer form: d_prior_llr_rows and d_cost_rows are [B, n] doubles on the device as bposd_channel_tables makes them
+ * (d_cost_rows may be NULL where the OSD stage does not weigh candidates, see above; it is required otherwise).  The caller
+ * owns the rows and keeps them unchanged until the call's lane is synchronised.  Asynchronous like bposd_decode_batch_device. */
+int bposd_decode_batch_rows_device(bposd_handle *h, const uint8_t *d_syndromes, int64_t B, const double *d_prior_llr_rows,
+                                   const double *d_cost_rows, uint8_t *d_osdw, uint8_t *d_osd0, uint8_t *d_bp,
+                                   uint8_t *d_converged, int32_t *d_iters, double *d_llr);
+
+/*
  * Bit-pack B rows of n 0/1 bytes (device) into B rows of ceil(n/64) little-endian 64-bit words (device):
  * bit (i & 63) of word (i >> 6) of row b = d_bytes[b*n + i] & 1.  Used to shrink the one exchange step of
  * the multi-GPU path (the gather of corrections) 8x.  Asynchronous on the handle's stream.
