@@ -21,6 +21,7 @@
 #include <tuple>
 #include <functional>
 #include <map>
+#include <memory>
 #include <chrono>
 #include <mutex>
 #include <thread>
@@ -50,21 +51,6 @@ int fail(bposd_handle* h, int code, const char* fmt, ...) {
     else g_create_error = buf;
     return code;
 }
-// Every entry point works on the handle's device and puts the caller's current device back on exit (a process that
-// also drives torch, or handles on other GPUs, must not find its thread's device changed by a decode call).
-struct DeviceGuard {
-    int prev = -1, dev = -1;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 int sync_all_lanes(bposd_handle* h) {
     for (auto& l : h->lanes) {
         if (l.stream) HIP_TRY(h, hipStreamSynchronize(l.stream));
@@ -107,15 +93,15 @@ int cached_occupancy(bposd_handle* h, const void* kernel, int nt, size_t lds, in
 }
 
 int ensure(bposd_handle* h, DevBuf& b, size_t bytes) {
-    if (bytes <= b.bytes && b.p) return 0;
-    if (b.p) {
-        HIP_TRY(h, hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    size_t want = std::max<size_t>(bytes, 256);
-    HIP_TRY(h, hipMalloc(&b.p, want));
-    b.bytes = want;
+    HIP_TRY(h, b.ensure(bytes));
+    return 0;
+}
+
+// The page-locked counterpart, for a block made with `flags`: nothing happens when it is large enough, else it is freed
+// and allocated anew (contents are not kept).
+int ensure_pinned(bposd_handle* h, PinnedBuf& b, size_t bytes, unsigned flags) {
+    if (bytes <= b.bytes) return 0;
+    HIP_TRY(h, b.alloc(bytes, flags));
     return 0;
 }
 
@@ -128,12 +114,6 @@ int ensure_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes) {
         if (rc) return rc;
     }
     return 0;
-}
-
-void release(DevBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
 }
 }  // namespace bposd_host
 
@@ -166,11 +146,12 @@ __global__ void unpack_rows_kernel(const unsigned long long* __restrict__ in, lo
 
 namespace {
 
-int launch_pack(bposd_handle* h, hipStream_t st, const uint8_t* d_bytes, long long B, int n, unsigned long long* d_words) {
+// wg_per_cu caps the grid: 2 inside the decode paths (few, fat workgroups: see launch_unpack), 16 for a stand-alone pack
+int launch_pack(bposd_handle* h, hipStream_t st, const uint8_t* d_bytes, long long B, int n, unsigned long long* d_words, int wg_per_cu = 2) {
     if (B <= 0) return 0;
     const int wpr = (n + 63) / 64, threads = 256;
     const long long want = ((long long)B * wpr * 64 + threads - 1) / threads;
-    const unsigned grid = (unsigned)std::min<long long>(want, (long long)h->num_cu * 2);  // few, fat workgroups: see launch_unpack
+    const unsigned grid = (unsigned)std::min<long long>(want, (long long)h->num_cu * wg_per_cu);
     hipLaunchKernelGGL(pack_rows_kernel, dim3(grid), dim3(threads), 0, st, d_bytes, B, n, wpr, d_words);
     HIP_TRY(h, hipGetLastError());
     return 0;
@@ -217,45 +198,11 @@ const char* bposd_last_error(bposd_handle* h) { return h ? h->err.c_str() : g_cr
 
 void bposd_destroy(bposd_handle* h) {
     if (!h) return;
-    DeviceGuard dev_guard(h->device);
+    DeviceGuard dev_guard(h->device);  // (outlives the delete: the members free themselves on the handle's device)
     for (auto& l : h->lanes) {
         if (l.stream) (void)hipStreamSynchronize(l.stream);
-        if (l.h_list) (void)hipHostFree(l.h_list);
-        if (l.ev_copy) (void)hipEventDestroy(l.ev_copy);
-        if (l.copy_stream) (void)hipStreamDestroy(l.copy_stream);
-        for (DevBuf* b : {&l.io_cmp0, &l.io_cmpw, &l.io_psynd, &l.io_posdw, &l.io_posd0, &l.io_pbp, &l.io_pcmp}) release(*b);
-        for (DevBuf* b : {&l.bpl_msg, &l.bpl_llr, &l.osdl_ws, &l.io_sel, &l.osd_rows_ws, &l.llr_ws, &l.osd_list, &l.io_synd, &l.io_osdw,
-                          &l.io_osd0, &l.io_bp, &l.io_conv, &l.io_iters, &l.io_llr, &l.io_l0rows, &l.io_costrows})
-            release(*b);
-        for (void* p : {(void*)l.d_counters, (void*)l.d_osd_dbg})  // (d_iter_total lives inside the d_counters block)
-            if (p) (void)hipFree(p);
         if (l.osd_stream) (void)hipStreamSynchronize(l.osd_stream);
-        if (l.h_stage) (void)hipHostFree(l.h_stage);
-        if (l.h_tail) (void)hipHostFree(l.h_tail);
-        if (l.d_alt) (void)hipFree(l.d_alt);
-        if (l.h_alt) (void)hipHostFree(l.h_alt);
-        if (l.h_rows) (void)hipHostFree(l.h_rows);
-        if (l.ev_alt) (void)hipEventDestroy(l.ev_alt);
-        if (l.ev_bp) (void)hipEventDestroy(l.ev_bp);
-        if (l.ev_osd) (void)hipEventDestroy(l.ev_osd);
-        if (l.ev_done) (void)hipEventDestroy(l.ev_done);
-        if (l.ev_up) (void)hipEventDestroy(l.ev_up);
-        if (l.osd_stream) (void)hipStreamDestroy(l.osd_stream);
-        if (l.stream) (void)hipStreamDestroy(l.stream);
     }
-    for (void* p : {(void*)h->d_rp, (void*)h->d_ci, (void*)h->d_chk_deg, (void*)h->d_var_deg,
-                    (void*)h->d_var_pos, (void*)h->d_var_ck, (void*)h->d_pos_bit, (void*)h->d_llr0, (void*)h->d_cost, (void*)h->d_llr0_alt, (void*)h->d_cost_alt,
-                    (void*)h->d_lpos_chk, (void*)h->d_lpos_bit,
-                    (void*)h->d_lpos_alo, (void*)h->d_lpos_ahi, (void*)h->d_lgrp_dl, (void*)h->d_lpos_dl,
-                    (void*)h->d_cpos_chk, (void*)h->d_cpos_bit, (void*)h->d_cbit_slot, (void*)h->d_cgrp_deg, (void*)h->d_cgrp_cdeg,
-                    (void*)h->d_cp, (void*)h->d_ce, (void*)h->d_erow, (void*)h->d_lvl_ptr, (void*)h->d_lvl_bits})
-        if (p) (void)hipFree(p);
-    for (CallRecord* rs : {h->rec, h->lane_rec})
-        for (int k = 0; k < (rs == h->rec ? BPOSD_MAX_CHUNKS : BPOSD_LANES); ++k) {
-            if (rs[k].h_counters) (void)hipHostFree(rs[k].h_counters);
-            for (auto& e : rs[k].ev)
-                if (e) (void)hipEventDestroy(e);
-        }
     delete h;
 }
 
@@ -287,16 +234,17 @@ int bposd_create(const bposd_config* cfg, const int32_t* indptr, const int32_t* 
                 return fail(nullptr, BPOSD_ERR_INVALID, "column indices must be strictly ascending within a row");
         }
     }
-    for (int i = 0; i < n; ++i)
-        if (!(channel_probs[i] >= 0.0 && channel_probs[i] <= 1.0))
-            return fail(nullptr, BPOSD_ERR_INVALID, "channel_probs[%d] = %g is not a probability", i, channel_probs[i]);
+    if (const int64_t bad = first_bad_prob(channel_probs, n))
+        return fail(nullptr, BPOSD_ERR_INVALID, "channel_probs[%d] = %g is not a probability", (int)(bad - 1), channel_probs[bad - 1]);
 
     int ndev = bposd_device_count();
     if (ndev <= 0) return fail(nullptr, BPOSD_ERR_NO_DEVICE, "no HIP device visible: the MI355X decoder has no CPU path");
     if (cfg->device < 0 || cfg->device >= ndev)
         return fail(nullptr, BPOSD_ERR_INVALID, "device %d out of range (%d visible)", cfg->device, ndev);
 
-    bposd_handle* h = new bposd_handle();
+    // Whatever the handle holds by the time a check below fails goes back with it: every failure is a plain return.
+    std::unique_ptr<bposd_handle, decltype(&bposd_destroy)> owner(new bposd_handle(), bposd_destroy);
+    bposd_handle* const h = owner.get();
     h->cfg = *cfg;
     h->device = cfg->device;
     h->m = m;
@@ -307,53 +255,38 @@ int bposd_create(const bposd_config* cfg, const int32_t* indptr, const int32_t* 
     h->probs.assign(channel_probs, channel_probs + n);
     h->max_iter = cfg->max_iter > 0 ? cfg->max_iter : n;  // A.1: 0 => block length
 
-#define CREATE_TRY(expr)                                                                        \
+    // a HIP call of the creation: a failure names it in the creation error
+#define CREATE_HIP(expr)                                                                        \
     do {                                                                                        \
         hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            fail(nullptr, BPOSD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e));        \
-            bposd_destroy(h);                                                                   \
-            return BPOSD_ERR_HIP;                                                               \
-        }                                                                                       \
+        if (_e != hipSuccess) return fail(nullptr, BPOSD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
-#define CREATE_RC(expr)                                                                         \
-    do {                                                                                        \
-        int _rc = (expr);                                                                       \
-        if (_rc) {                                                                              \
-            g_create_error = h->err;                                                            \
-            bposd_destroy(h);                                                                   \
-            return _rc;                                                                         \
-        }                                                                                       \
-    } while (0)
+    auto failed = [h](int rc) { g_create_error = h->err; return rc; };  // a step that left its message in the handle
+    int rc;
 
     DeviceGuard dev_guard(h->device);
-    CREATE_TRY(dev_guard.err);
+    CREATE_HIP(dev_guard.err);
     hipDeviceProp_t prop;
-    CREATE_TRY(hipGetDeviceProperties(&prop, h->device));
+    CREATE_HIP(hipGetDeviceProperties(&prop, h->device));
     h->num_cu = prop.multiProcessorCount;
     if (prop.maxSharedMemoryPerMultiProcessor > 0) h->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
     int prio_least = 0, prio_greatest = 0;
-    CREATE_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    CREATE_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     for (auto& l : h->lanes) {
-        CREATE_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
-        CREATE_TRY(hipStreamCreateWithPriority(&l.osd_stream, hipStreamNonBlocking, prio_greatest));
-        CREATE_TRY(hipEventCreateWithFlags(&l.ev_bp, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&l.ev_osd, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&l.ev_done, hipEventDisableTiming));
-        CREATE_TRY(hipEventCreateWithFlags(&l.ev_up, hipEventDisableTiming));
-        CREATE_TRY(hipStreamCreateWithFlags(&l.copy_stream, hipStreamNonBlocking));
-        CREATE_TRY(hipEventCreateWithFlags(&l.ev_copy, hipEventDisableTiming));
-        CREATE_TRY(hipMalloc((void**)&l.d_counters, 32));  // 4 counters + the 64-bit iteration total: one memset, one copy
-        CREATE_TRY(hipHostMalloc((void**)&l.h_tail, 64, hipHostMallocMapped));
-        *l.h_tail = 0;
+        CREATE_HIP(hipStreamCreateWithFlags(&l.stream.raw, hipStreamNonBlocking));
+        CREATE_HIP(hipStreamCreateWithPriority(&l.osd_stream.raw, hipStreamNonBlocking, prio_greatest));
+        for (Event* e : {&l.ev_bp, &l.ev_osd, &l.ev_done, &l.ev_up, &l.ev_copy}) CREATE_HIP(hipEventCreateWithFlags(&e->raw, hipEventDisableTiming));
+        CREATE_HIP(hipStreamCreateWithFlags(&l.copy_stream.raw, hipStreamNonBlocking));
+        CREATE_HIP(l.d_counters.alloc(32));  // 4 counters + the 64-bit iteration total: one memset, one copy
+        CREATE_HIP(l.h_tail.alloc(64, hipHostMallocMapped));
+        *l.h_tail.as<int>() = 0;
     }
     for (CallRecord* rs : {h->rec, h->lane_rec})
         for (int k = 0; k < (rs == h->rec ? BPOSD_MAX_CHUNKS : BPOSD_LANES); ++k) {
-            for (auto& e : rs[k].ev) CREATE_TRY(hipEventCreate(&e));
-            CREATE_TRY(hipHostMalloc((void**)&rs[k].h_counters, 32));
-            rs[k].h_iter_total = (unsigned long long*)(rs[k].h_counters + 4);
-            rs[k].h_counters[0] = rs[k].h_counters[1] = 0;
-            *rs[k].h_iter_total = 0;
+            for (auto& e : rs[k].ev) CREATE_HIP(hipEventCreate(&e.raw));
+            CREATE_HIP(rs[k].h_counters.alloc(32, hipHostMallocDefault));
+            rs[k].counters()[0] = rs[k].counters()[1] = 0;
+            *rs[k].iter_total() = 0;
         }
 
     // degrees
@@ -388,93 +321,68 @@ int bposd_create(const bposd_config* cfg, const int32_t* indptr, const int32_t* 
         // launched (l29k_ms_e15: 88 ms per step with two lanes, 82-83 with three or four -- the sum of the kernels' CU time).
         h->nlanes = h->bp_hbm ? 3 : 2;
         if (const char* e = getenv("BPOSD_LARGE_LANES")) h->nlanes = std::max(1, std::min(BPOSD_LANES, atoi(e)));
-        if (n > 32767 || m > 16384 || (h->bp_hbm && bp_large_lds_need(m, n) > h->lds_per_cu)) {
-            fail(nullptr, BPOSD_ERR_UNSUPPORTED, "code too large even for the HBM-resident kernels (m=%d n=%d; limits 16384 / 32767)", m, n);
-            bposd_destroy(h);
-            return BPOSD_ERR_UNSUPPORTED;
-        }
+        if (n > 32767 || m > 16384 || (h->bp_hbm && bp_large_lds_need(m, n) > h->lds_per_cu))
+            return fail(nullptr, BPOSD_ERR_UNSUPPORTED, "code too large even for the HBM-resident kernels (m=%d n=%d; limits 16384 / 32767)", m, n);
         const int span_cap = osd_large_maxspan(cfg->osd_method == BPOSD_OSD_CS);
-        if (cfg->osd_method >= BPOSD_OSD_E && cfg->osd_order > span_cap) {
-            fail(nullptr, BPOSD_ERR_UNSUPPORTED,
-                 "osd order %d > %d is not supported by the HBM-resident OSD kernel (m=%d n=%d)", cfg->osd_order,
-                 span_cap, m, n);
-            bposd_destroy(h);
-            return BPOSD_ERR_UNSUPPORTED;
-        }
+        if (cfg->osd_method >= BPOSD_OSD_E && cfg->osd_order > span_cap)
+            return fail(nullptr, BPOSD_ERR_UNSUPPORTED,
+                        "osd order %d > %d is not supported by the HBM-resident OSD kernel (m=%d n=%d)", cfg->osd_order,
+                        span_cap, m, n);
     }
 
     h->rank = h->large ? std::min(m, n) : gf2_rank_host(m, n, h->rp, h->ci);  // large: probed on the device below
     h->kprime = n - h->rank;
     if (cfg->osd_method != BPOSD_OSD_OFF && !h->large) {
-        if (m > 1024 || osd_words(n) == 0) {
-            fail(nullptr, BPOSD_ERR_UNSUPPORTED,
-                 "code too large for the register-resident OSD kernel (m=%d > 1024 or n=%d > 2047): large-code path not built yet",
-                 m, n);
-            bposd_destroy(h);
-            return BPOSD_ERR_UNSUPPORTED;
-        }
-        if (cfg->osd_method >= BPOSD_OSD_E && cfg->osd_order > h->kprime) {
-            fail(nullptr, BPOSD_ERR_INVALID, "osd_order %d exceeds the number of non-pivot columns n - rank = %d",
-                 cfg->osd_order, h->kprime);
-            bposd_destroy(h);
-            return BPOSD_ERR_INVALID;
-        }
-        if (cfg->osd_method == BPOSD_OSD_E && cfg->osd_order > 20) {
-            fail(nullptr, BPOSD_ERR_UNSUPPORTED, "osd_e order %d > 20 not supported", cfg->osd_order);
-            bposd_destroy(h);
-            return BPOSD_ERR_UNSUPPORTED;
-        }
-        if (cfg->osd_method == BPOSD_OSD_CS && cfg->osd_order > 64) {
-            fail(nullptr, BPOSD_ERR_UNSUPPORTED, "osd_cs order %d > 64 not supported", cfg->osd_order);
-            bposd_destroy(h);
-            return BPOSD_ERR_UNSUPPORTED;
-        }
+        if (m > 1024 || osd_words(n) == 0)
+            return fail(nullptr, BPOSD_ERR_UNSUPPORTED,
+                        "code too large for the register-resident OSD kernel (m=%d > 1024 or n=%d > 2047): large-code path not built yet",
+                        m, n);
+        if (cfg->osd_method >= BPOSD_OSD_E && cfg->osd_order > h->kprime)
+            return fail(nullptr, BPOSD_ERR_INVALID, "osd_order %d exceeds the number of non-pivot columns n - rank = %d",
+                        cfg->osd_order, h->kprime);
+        if (cfg->osd_method == BPOSD_OSD_E && cfg->osd_order > 20)
+            return fail(nullptr, BPOSD_ERR_UNSUPPORTED, "osd_e order %d > 20 not supported", cfg->osd_order);
+        if (cfg->osd_method == BPOSD_OSD_CS && cfg->osd_order > 64)
+            return fail(nullptr, BPOSD_ERR_UNSUPPORTED, "osd_cs order %d > 64 not supported", cfg->osd_order);
     }
     h->ncand = num_candidates(h);
 
-    CREATE_RC(upload_ints(h, &h->d_rp, h->rp));
-    CREATE_RC(upload_ints(h, &h->d_ci, h->ci));
-    CREATE_TRY(hipMalloc((void**)&h->d_llr0, sizeof(double) * n));
-    CREATE_TRY(hipMalloc((void**)&h->d_cost, sizeof(double) * n));
-    CREATE_TRY(hipMalloc((void**)&h->d_llr0_alt, sizeof(double) * n));
-    CREATE_TRY(hipMalloc((void**)&h->d_cost_alt, sizeof(double) * n));
-    if (h->bp_any) CREATE_RC(build_tables_serial(h));  // (its CSC edge map is what the any-degree kernel walks)
-    else if (h->bp_hbm) CREATE_RC(build_tables_large(h, h->dv_max <= 6 ? 6 : 8, (m + 63) / 64 * 64));
-    else CREATE_RC(build_tables(h, pair.dc, pair.dv, shape_threads(h, shp) * shape_cpt(shp), shape_threads(h, shp), 2 * shape_cpt(shp)));
-    if (!h->bp_any && !h->bp_hbm && cfg->bp_method == BPOSD_BP_MIN_SUM) CREATE_RC(build_tables_local(h));
-    if (!h->bp_any && !h->bp_hbm && (!(h->local_ok && cfg->bp_method == BPOSD_BP_MIN_SUM) || getenv("BPOSD_CLASS_ALWAYS"))) CREATE_RC(build_tables_class(h));
+    if ((rc = upload_ints(h, h->d_rp, h->rp))) return failed(rc);
+    if ((rc = upload_ints(h, h->d_ci, h->ci))) return failed(rc);
+    for (DevArray<double>* t : {&h->d_llr0, &h->d_cost, &h->d_llr0_alt, &h->d_cost_alt}) CREATE_HIP(t->alloc(sizeof(double) * n));
+    if (h->bp_any) rc = build_tables_serial(h);  // (its CSC edge map is what the any-degree kernel walks)
+    else if (h->bp_hbm) rc = build_tables_large(h, h->dv_max <= 6 ? 6 : 8, (m + 63) / 64 * 64);
+    else rc = build_tables(h, pair.dc, pair.dv, shape_threads(h, shp) * shape_cpt(shp), shape_threads(h, shp), 2 * shape_cpt(shp));
+    if (rc) return failed(rc);
+    if (!h->bp_any && !h->bp_hbm && cfg->bp_method == BPOSD_BP_MIN_SUM && (rc = build_tables_local(h))) return failed(rc);
+    if (!h->bp_any && !h->bp_hbm && (!(h->local_ok && cfg->bp_method == BPOSD_BP_MIN_SUM) || getenv("BPOSD_CLASS_ALWAYS")) && (rc = build_tables_class(h)))
+        return failed(rc);
     if (cfg->schedule == 1) {
-        if (h->dv_max > bp_serial_max_dv()) {
-            fail(h, BPOSD_ERR_UNSUPPORTED, "serial schedule: bit degree %d exceeds %d", h->dv_max, bp_serial_max_dv());
-            CREATE_RC(BPOSD_ERR_UNSUPPORTED);
-        }
-        if (!h->bp_any) CREATE_RC(build_tables_serial(h));
+        if (h->dv_max > bp_serial_max_dv())
+            return failed(fail(h, BPOSD_ERR_UNSUPPORTED, "serial schedule: bit degree %d exceeds %d", h->dv_max, bp_serial_max_dv()));
+        if (!h->bp_any && (rc = build_tables_serial(h))) return failed(rc);
     }
-    CREATE_RC(upload_priors(h));
+    if ((rc = upload_priors(h))) return failed(rc);
     if (h->large) {
         DecodeCall probe;
         probe.lane = &h->lanes[0];
         probe.osd_stream = probe.lane->osd_stream;
-        CREATE_RC(probe_rank_large(h, probe, &h->rank));
+        if ((rc = probe_rank_large(h, probe, &h->rank))) return failed(rc);
         h->kprime = n - h->rank;
-        if (cfg->osd_method >= BPOSD_OSD_E && cfg->osd_order > h->kprime) {
-            fail(h, BPOSD_ERR_INVALID, "osd_order %d exceeds the number of non-pivot columns n - rank = %d",
-                 cfg->osd_order, h->kprime);
-            CREATE_RC(BPOSD_ERR_INVALID);
-        }
+        if (cfg->osd_method >= BPOSD_OSD_E && cfg->osd_order > h->kprime)
+            return failed(fail(h, BPOSD_ERR_INVALID, "osd_order %d exceeds the number of non-pivot columns n - rank = %d",
+                               cfg->osd_order, h->kprime));
         h->ncand = num_candidates(h);
     }
-    *out = h;
+    *out = owner.release();
     return BPOSD_OK;
-#undef CREATE_TRY
-#undef CREATE_RC
+#undef CREATE_HIP
 }
 
 int bposd_update_channel_probs(bposd_handle* h, const double* channel_probs) {
     if (!h || !channel_probs) return fail(h, BPOSD_ERR_INVALID, "null argument");
-    for (int i = 0; i < h->n; ++i)
-        if (!(channel_probs[i] >= 0.0 && channel_probs[i] <= 1.0))
-            return fail(h, BPOSD_ERR_INVALID, "channel_probs[%d] = %g is not a probability", i, channel_probs[i]);
+    if (const int64_t bad = first_bad_prob(channel_probs, h->n))
+        return fail(h, BPOSD_ERR_INVALID, "channel_probs[%d] = %g is not a probability", (int)(bad - 1), channel_probs[bad - 1]);
     DeviceGuard dev_guard(h->device);
     HIP_TRY(h, dev_guard.err);
     { int rcs = sync_all_lanes(h); if (rcs) return rcs; }
@@ -522,16 +430,8 @@ int bposd_pack_rows_device_lane(bposd_handle* h, int32_t lane, const uint8_t* d_
     if (B == 0) return BPOSD_OK;
     DeviceGuard dev_guard(h->device);
     HIP_TRY(h, dev_guard.err);
-    const int wpr = (n + 63) / 64;
-    const long long nwords = (long long)B * wpr;
-    const int threads = 256;
-    const long long want = (nwords * 64 + threads - 1) / threads;
-    const unsigned grid = (unsigned)std::min<long long>(want, (long long)h->num_cu * 16);
     // queued behind the device-pointer decode that ran on this lane (stream order)
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(grid), dim3(threads), 0, h->lanes[lane].stream, d_bytes, (long long)B, (int)n, wpr,
-                       (unsigned long long*)d_words);
-    HIP_TRY(h, hipGetLastError());
-    return BPOSD_OK;
+    return launch_pack(h, h->lanes[lane].stream, d_bytes, B, n, (unsigned long long*)d_words, /*wg_per_cu=*/16);
 }
 
 int bposd_layout_info(bposd_handle* h, int64_t* natural, int64_t* chosen, int64_t* ideal) {
@@ -674,7 +574,7 @@ static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoP
     P.osd_list = (int*)L.osd_list.p;
     P.counters = L.d_counters;
     P.iter_total = (unsigned long long*)(L.d_counters + 4);
-    P.tail_flag = call.tail_gate ? L.h_tail : nullptr;
+    P.tail_flag = call.tail_gate ? L.h_tail.as<int>() : nullptr;
     P.packed_io = call.packed ? 1 : 0;
 
     // At most TWO calls have kernels on the device: this call's BP kernel waits for the END of the call two back (its OSD
@@ -743,7 +643,7 @@ static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoP
         Q.cost_alt = call.lane_alt ? L.d_alt + h->n : h->d_cost_alt;
         const char* dbg_env = getenv("BPOSD_OSD_DEBUG");
         if (dbg_env && dbg_env[0] == '1') {
-            if (!L.d_osd_dbg) HIP_TRY(h, hipMalloc((void**)&L.d_osd_dbg, 8192 * sizeof(long long)));
+            if (!L.d_osd_dbg) HIP_TRY(h, L.d_osd_dbg.alloc(8192 * sizeof(long long)));
             HIP_TRY(h, hipMemsetAsync(L.d_osd_dbg, 0, 8192 * sizeof(long long), call.osd_stream));
             Q.dbg = L.d_osd_dbg;
         }
@@ -763,7 +663,7 @@ static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoP
         HIP_TRY(h, hipEventRecord(L.ev_done, L.stream));  // both kernels of this call have ended
         L.done_recorded = true;
     }
-    HIP_TRY(h, hipMemcpyAsync(R.h_counters, L.d_counters, 32, hipMemcpyDeviceToHost, L.stream));
+    HIP_TRY(h, hipMemcpyAsync(R.counters(), L.d_counters, 32, hipMemcpyDeviceToHost, L.stream));
     R.recorded = true;
     R.timed = !lean;
     h->have_timing = true;
@@ -830,9 +730,8 @@ int bposd_decode_batch_device_packed(bposd_handle* h, const uint64_t* d_synd_wor
 // the alternative channel of the two-valued per-shot form: validated first, then its prior LLRs and OSD-W weights
 static int check_alt_channel(bposd_handle* h, const double* alt) {
     if (!alt) return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt is required");
-    for (int i = 0; i < h->n; ++i)
-        if (!(alt[i] >= 0.0 && alt[i] <= 1.0))
-            return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt[%d] = %g is not a probability", i, alt[i]);
+    if (const int64_t bad = first_bad_prob(alt, h->n))
+        return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt[%d] = %g is not a probability", (int)(bad - 1), alt[bad - 1]);
     return 0;
 }
 
@@ -865,14 +764,12 @@ int bposd_decode_batch_select_device(bposd_handle* h, const uint8_t* d_synd, int
     call.lane_alt = true;
     Lane& L = *call.lane;
     const size_t bytes = sizeof(double) * 2 * (size_t)h->n;
-    if (!L.d_alt) {
-        HIP_TRY(h, hipMalloc((void**)&L.d_alt, bytes));
-        HIP_TRY(h, hipHostMalloc((void**)&L.h_alt, bytes, hipHostMallocDefault));
-        HIP_TRY(h, hipEventCreateWithFlags(&L.ev_alt, hipEventDisableTiming));
-    }
+    if (!L.d_alt) HIP_TRY(h, L.d_alt.alloc(bytes));
+    if (const int rc = ensure_pinned(h, L.h_alt, bytes, hipHostMallocDefault)) return rc;
+    if (!L.ev_alt) HIP_TRY(h, hipEventCreateWithFlags(&L.ev_alt.raw, hipEventDisableTiming));
     if (L.alt_busy) HIP_TRY(h, hipEventSynchronize(L.ev_alt));  // the copy of this lane's previous select call has read the staging block
-    alt_channel_tables(h->n, alt, L.h_alt, L.h_alt + h->n);
-    HIP_TRY(h, hipMemcpyAsync(L.d_alt, L.h_alt, bytes, hipMemcpyHostToDevice, L.stream));
+    alt_channel_tables(h->n, alt, L.h_alt.as<double>(), L.h_alt.as<double>() + h->n);
+    HIP_TRY(h, hipMemcpyAsync(L.d_alt, L.h_alt.p, bytes, hipMemcpyHostToDevice, L.stream));
     HIP_TRY(h, hipEventRecord(L.ev_alt, L.stream));
     L.alt_busy = true;
     return decode_device_impl(h, call, IoPtrs{d_synd, d_sel, d_osdw, d_osd0, d_bp, d_conv, d_iters, d_llr}, B);
@@ -913,12 +810,10 @@ int bposd_decode_batch_rows(bposd_handle* h, const uint8_t* synd, int64_t B, con
     std::mutex mu;
     size_t first_bad = total;
     parallel_slices(total, [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; ++i)
-            if (!(channel_probs_rows[i] >= 0.0 && channel_probs_rows[i] <= 1.0)) {
-                std::lock_guard<std::mutex> g(mu);
-                first_bad = std::min(first_bad, i);
-                return;
-            }
+        if (const int64_t bad = first_bad_prob(channel_probs_rows + lo, (int64_t)(hi - lo))) {
+            std::lock_guard<std::mutex> g(mu);
+            first_bad = std::min(first_bad, lo + (size_t)bad - 1);
+        }
     });
     if (first_bad < total)
         return fail(h, BPOSD_ERR_INVALID, "channel_probs_rows[%lld][%d] = %g is not a probability", (long long)(first_bad / h->n),
@@ -1039,15 +934,8 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
                      total = o_rc + (rows_cost ? a64(b8 * n8 * 8) : 0);
         if (zero_copy && !packed && total <= (size_t)1 << 20) {
             Lane& L = h->lanes[0];
-            if (L.h_stage_bytes < total) {
-                if (L.h_stage) (void)hipHostFree(L.h_stage);
-                L.h_stage = nullptr;
-                L.h_stage_bytes = 0;
-                const size_t want = std::max<size_t>(total, (size_t)1 << 16);
-                HIP_TRY(h, hipHostMalloc(&L.h_stage, want, hipHostMallocMapped));
-                L.h_stage_bytes = want;
-            }
-            unsigned char* st = (unsigned char*)L.h_stage;
+            if (const int rcs = ensure_pinned(h, L.h_stage, std::max<size_t>(total, (size_t)1 << 16), hipHostMallocMapped)) return rcs;
+            unsigned char* st = L.h_stage.as<unsigned char>();
             memcpy(st + o_syn, host.synd, b8 * m8);
             if (host.sel) memcpy(st + o_sel, host.sel, b8 * n8);
             if (prob_rows) convert_rows(prob_rows, b8 * n8, (double*)(st + o_r0), rows_cost ? (double*)(st + o_rc) : nullptr);
@@ -1113,7 +1001,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
         L.copy_pending = false;
         if (!osd_on || !h->rec[c].ran_osd) return 0;
         const long long lo = clo[c];
-        const int count = h->rec[c].h_counters[1];
+        const int count = h->rec[c].counters()[1];
         if (count <= 0) return 0;
         std::vector<uint8_t> rows((size_t)count * rsn);
         for (int which = 0; which < 2; ++which) {
@@ -1128,7 +1016,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
             } else {
                 HIP_TRY(h, hipMemcpy(rows.data(), src, rows.size(), hipMemcpyDeviceToHost));
             }
-            for (int k = 0; k < count; ++k) memcpy(dst + ((size_t)lo + (size_t)L.h_list[k]) * rsn, rows.data() + (size_t)k * rsn, rsn);
+            for (int k = 0; k < count; ++k) memcpy(dst + ((size_t)lo + (size_t)L.h_list.as<int>()[k]) * rsn, rows.data() + (size_t)k * rsn, rsn);
         }
         return 0;
     };
@@ -1149,12 +1037,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
         if (osd_on) {
             if ((rc = ensure(h, L.io_cmpw, (size_t)CH * n))) return rc;
             if (host.osd0 && (rc = ensure(h, L.io_cmp0, (size_t)CH * n))) return rc;
-            if (L.h_list_cap < (size_t)CH) {
-                if (L.h_list) (void)hipHostFree(L.h_list);
-                L.h_list = nullptr; L.h_list_cap = 0;
-                HIP_TRY(h, hipHostMalloc((void**)&L.h_list, sizeof(int) * (size_t)CH, hipHostMallocDefault));
-                L.h_list_cap = (size_t)CH;
-            }
+            if ((rc = ensure_pinned(h, L.h_list, sizeof(int) * (size_t)CH, hipHostMallocDefault))) return rc;
         }
         if (c > 0) HIP_TRY(h, hipStreamWaitEvent(L.stream, h->lanes[(c - 1) % h->nlanes].ev_up, 0));
         if (packed) {
@@ -1173,15 +1056,11 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
             const size_t cap = (size_t)CH * n, want = cap * (rows_cost ? 2 : 1);
             if ((rc = ensure(h, L.io_l0rows, sizeof(double) * cap))) return rc;
             if (rows_cost && (rc = ensure(h, L.io_costrows, sizeof(double) * cap))) return rc;
-            if (L.h_rows_cap < want) {
-                if (L.h_rows) (void)hipHostFree(L.h_rows);
-                L.h_rows = nullptr; L.h_rows_cap = 0;
-                HIP_TRY(h, hipHostMalloc((void**)&L.h_rows, sizeof(double) * want, hipHostMallocDefault));
-                L.h_rows_cap = want;
-            }
-            convert_rows(prob_rows + (size_t)lo * n, bn, L.h_rows, rows_cost ? L.h_rows + cap : nullptr);
-            HIP_TRY(h, hipMemcpyAsync(L.io_l0rows.p, L.h_rows, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
-            if (rows_cost) HIP_TRY(h, hipMemcpyAsync(L.io_costrows.p, L.h_rows + cap, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
+            if ((rc = ensure_pinned(h, L.h_rows, sizeof(double) * want, hipHostMallocDefault))) return rc;
+            double* const rows = L.h_rows.as<double>();
+            convert_rows(prob_rows + (size_t)lo * n, bn, rows, rows_cost ? rows + cap : nullptr);
+            HIP_TRY(h, hipMemcpyAsync(L.io_l0rows.p, rows, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
+            if (rows_cost) HIP_TRY(h, hipMemcpyAsync(L.io_costrows.p, rows + cap, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
         }
         HIP_TRY(h, hipEventRecord(L.ev_up, L.stream));
         IoPtrs dev = lane_ptrs(L, native, host);
@@ -1199,7 +1078,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
             // poll the flag (a plain load from page-locked memory); the runtime is asked only every so often and the
             // thread backs off after a short spin -- a chunk's BP kernel runs for milliseconds
             hipError_t qe = hipErrorNotReady;
-            for (unsigned spins = 0; *(volatile int*)Pv.h_tail == 0; ++spins) {
+            for (unsigned spins = 0; *Pv.h_tail.as<volatile int>() == 0; ++spins) {
                 if ((spins & 63) == 63) {
                     qe = hipEventQuery(Pv.ev_bp);
                     if (qe != hipErrorNotReady) break;
@@ -1210,7 +1089,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
             if (qe != hipErrorNotReady && qe != hipSuccess)
                 return fail(h, BPOSD_ERR_HIP, "hipEventQuery failed while waiting for chunk %d: %s", c - 1, hipGetErrorString(qe));
         }
-        *(volatile int*)L.h_tail = 0;
+        *L.h_tail.as<volatile int>() = 0;
         DecodeCall call{&L, &h->rec[c], L.osd_stream};
         call.batch_hint = B;  // kernel variants are chosen for the call, not for a chunk
         call.cmp_osdw = osd_on ? (uint8_t*)L.io_cmpw.p : nullptr;
@@ -1229,7 +1108,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
         if (host.conv) HIP_TRY(h, hipMemcpyAsync(host.conv + lo, dev.conv, (size_t)cnt, hipMemcpyDeviceToHost, cs));
         if (host.iters) HIP_TRY(h, hipMemcpyAsync(host.iters + lo, dev.iters, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, cs));
         if (host.llr) HIP_TRY(h, hipMemcpyAsync(host.llr + (size_t)lo * n, dev.llr, sizeof(double) * bn, hipMemcpyDeviceToHost, cs));
-        if (osd_on) HIP_TRY(h, hipMemcpyAsync(L.h_list, L.osd_list.p, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, cs));
+        if (osd_on) HIP_TRY(h, hipMemcpyAsync(L.h_list.p, L.osd_list.p, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, cs));
         L.copy_pending = true;
     }
     for (int c = std::max(0, nchunks - h->nlanes); c < nchunks; ++c)
@@ -1335,8 +1214,8 @@ static int record_timing(bposd_handle* h, CallRecord* recs, int count, double* b
         }
         a_sum += a;
         if (R.ran_osd) b_sum += b;
-        it_sum += (int64_t)*R.h_iter_total;
-        osd_sum += R.h_counters[1];
+        it_sum += (int64_t)*R.iter_total();
+        osd_sum += R.counters()[1];
     }
     if (bp_ms) *bp_ms = a_sum;
     if (osd_ms) *osd_ms = b_sum;
@@ -1393,7 +1272,7 @@ void* bposd_host_alloc(size_t bytes) {
 }
 
 void bposd_host_free(void* p) {
-    if (p) (void)hipHostFree(p);
+    (void)free_pinned(p);
 }
 
 }  // extern "C"

@@ -41,10 +41,9 @@ int gf2_rank_host(int m, int n, const std::vector<int>& rp, const std::vector<in
 
 // One int table on the device.  A table that exists is freed first: the LDS kernel's tables are rebuilt when the workgroup
 // shape changes, and bposd_set_bp_variant(64) builds the serial tables on a handle that may have none yet.
-int upload_ints(bposd_handle* h, int** dst, const std::vector<int>& v) {
-    if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-    HIP_TRY(h, hipMalloc((void**)dst, sizeof(int) * std::max<size_t>(v.size(), 1)));
-    HIP_TRY(h, hipMemcpy(*dst, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice));
+int upload_ints(bposd_handle* h, DevArray<int>& dst, const std::vector<int>& v) {
+    HIP_TRY(h, dst.alloc(sizeof(int) * std::max<size_t>(v.size(), 1)));
+    HIP_TRY(h, hipMemcpy(dst, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -61,9 +60,14 @@ bool pick_pair(int dc, int dv, DegPair* out) {
 // makes) so that device arithmetic is add / compare / multiply only.  The handle's channel, the alternative channel and
 // the per-shot rows all come from here, which is what makes a row equal update_channel_probs with that row bit for bit.
 // Either output may be null.  Returns the index of the first value that is no probability + 1, 0 if there is none.
-int64_t channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost) {
+int64_t first_bad_prob(const double* probs, int64_t count) {
     for (int64_t i = 0; i < count; ++i)
         if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return i + 1;
+    return 0;
+}
+
+int64_t channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost) {
+    if (const int64_t bad = first_bad_prob(probs, count)) return bad;
     if (prior_llr)
         for (int64_t i = 0; i < count; ++i) prior_llr[i] = std::log((1 - probs[i]) / probs[i]);
     if (cost)
@@ -233,10 +237,10 @@ int build_tables(bposd_handle* h, int DC, int DV, int MP, int NT, int VPT) {
         }
     }
     int rc;
-    if ((rc = upload_ints(h, &h->d_chk_deg, chk_deg))) return rc;
-    if ((rc = upload_ints(h, &h->d_var_deg, var_deg))) return rc;
-    if ((rc = upload_ints(h, &h->d_var_pos, var_pos))) return rc;
-    if ((rc = upload_ints(h, &h->d_pos_bit, bit_of_pos))) return rc;
+    if ((rc = upload_ints(h, h->d_chk_deg, chk_deg))) return rc;
+    if ((rc = upload_ints(h, h->d_var_deg, var_deg))) return rc;
+    if ((rc = upload_ints(h, h->d_var_pos, var_pos))) return rc;
+    if ((rc = upload_ints(h, h->d_pos_bit, bit_of_pos))) return rc;
     h->tab_dc = DC;
     h->tab_dv = DV;
     h->tab_mp = MP;
@@ -327,12 +331,12 @@ int build_tables_local(bposd_handle* h) {
         }
     }
     int rc;
-    if ((rc = upload_ints(h, &h->d_lpos_chk, pos_chk))) return rc;
-    if ((rc = upload_ints(h, &h->d_lpos_bit, pos_bit))) return rc;
-    if ((rc = upload_ints(h, &h->d_lpos_alo, pos_alo))) return rc;
-    if ((rc = upload_ints(h, &h->d_lpos_ahi, pos_ahi))) return rc;
-    if ((rc = upload_ints(h, &h->d_lgrp_dl, grp_dl))) return rc;
-    if ((rc = upload_ints(h, &h->d_lpos_dl, pos_dl))) return rc;
+    if ((rc = upload_ints(h, h->d_lpos_chk, pos_chk))) return rc;
+    if ((rc = upload_ints(h, h->d_lpos_bit, pos_bit))) return rc;
+    if ((rc = upload_ints(h, h->d_lpos_alo, pos_alo))) return rc;
+    if ((rc = upload_ints(h, h->d_lpos_ahi, pos_ahi))) return rc;
+    if ((rc = upload_ints(h, h->d_lgrp_dl, grp_dl))) return rc;
+    if ((rc = upload_ints(h, h->d_lpos_dl, pos_dl))) return rc;
     h->local_mp = MP;
     h->local_ok = true;
     return 0;
@@ -382,11 +386,11 @@ int build_tables_class(bposd_handle* h) {
         fprintf(stderr, "[bposd] class BP layout: %d threads, stride %d, bit pass %ld read cycles (floor %ld) + %ld write cycles (floor %ld)\n", T.NT,
                 MP, T.read_cycles, T.read_floor, T.write_cycles, T.write_floor);
     int rc;
-    if ((rc = upload_ints(h, &h->d_cpos_chk, T.pos_chk))) return rc;
-    if ((rc = upload_ints(h, &h->d_cpos_bit, T.pos_bit))) return rc;
-    if ((rc = upload_ints(h, &h->d_cbit_slot, T.bit_slot))) return rc;
-    if ((rc = upload_ints(h, &h->d_cgrp_deg, T.grp_deg))) return rc;
-    if ((rc = upload_ints(h, &h->d_cgrp_cdeg, T.grp_cdeg))) return rc;
+    if ((rc = upload_ints(h, h->d_cpos_chk, T.pos_chk))) return rc;
+    if ((rc = upload_ints(h, h->d_cpos_bit, T.pos_bit))) return rc;
+    if ((rc = upload_ints(h, h->d_cbit_slot, T.bit_slot))) return rc;
+    if ((rc = upload_ints(h, h->d_cgrp_deg, T.grp_deg))) return rc;
+    if ((rc = upload_ints(h, h->d_cgrp_cdeg, T.grp_cdeg))) return rc;
     h->class_dclo = shp->dclo; h->class_dc = shp->dc; h->class_dvlo = shp->dvlo; h->class_dvhi = shp->dvhi; h->class_mp = MP; h->class_nt = T.NT;
     h->class_read_cycles = T.read_cycles; h->class_write_cycles = T.write_cycles;
     h->class_read_floor = T.read_floor; h->class_write_floor = T.write_floor;
@@ -408,10 +412,10 @@ int build_tables_large(bposd_handle* h, int DV, int MP) {
         }
     }
     int rc;
-    if ((rc = upload_ints(h, &h->d_chk_deg, chk_deg))) return rc;
-    if ((rc = upload_ints(h, &h->d_var_deg, var_deg))) return rc;
-    if ((rc = upload_ints(h, &h->d_var_pos, var_pos))) return rc;
-    if ((rc = upload_ints(h, &h->d_var_ck, var_ck))) return rc;
+    if ((rc = upload_ints(h, h->d_chk_deg, chk_deg))) return rc;
+    if ((rc = upload_ints(h, h->d_var_deg, var_deg))) return rc;
+    if ((rc = upload_ints(h, h->d_var_pos, var_pos))) return rc;
+    if ((rc = upload_ints(h, h->d_var_ck, var_ck))) return rc;
     h->tab_mp = MP;
     return 0;
 }
@@ -444,11 +448,11 @@ int build_tables_serial(bposd_handle* h) {
         for (int i = 0; i < n; ++i) lbits[pos[level[i] - 1]++] = i;  // ascending bit index inside a level
     }
     int rc;
-    if ((rc = upload_ints(h, &h->d_cp, cp))) return rc;
-    if ((rc = upload_ints(h, &h->d_ce, ce))) return rc;
-    if ((rc = upload_ints(h, &h->d_erow, erow))) return rc;
-    if ((rc = upload_ints(h, &h->d_lvl_ptr, lptr))) return rc;
-    if ((rc = upload_ints(h, &h->d_lvl_bits, lbits))) return rc;
+    if ((rc = upload_ints(h, h->d_cp, cp))) return rc;
+    if ((rc = upload_ints(h, h->d_ce, ce))) return rc;
+    if ((rc = upload_ints(h, h->d_erow, erow))) return rc;
+    if ((rc = upload_ints(h, h->d_lvl_ptr, lptr))) return rc;
+    if ((rc = upload_ints(h, h->d_lvl_bits, lbits))) return rc;
     h->nlevels = nlev;
     return 0;
 }
@@ -481,7 +485,6 @@ int probe_rank_large(bposd_handle* h, const DecodeCall& call, int* rank) {
         else if (got[5] < 0 || got[5] > std::min(h->m, h->n)) rc = fail(h, BPOSD_ERR_HIP, "rank probe returned %d", got[5]);
         else *rank = got[5];
     }
-    release(tmp);
     return rc;
 }
 

@@ -1,7 +1,8 @@
 // internal.h -- host-side state shared by the translation units of libbposd_mi355x.so (not part of the C-ABI).
 // bposd_capi.hip holds the C-ABI and the decode calls, host_tables.hip table construction and the layout searches; every
 // launch_*.hip holds the instantiations and launch code of one kernel family, so that the families compile in parallel
-// (bp_osd_amd/build.py).
+// (bp_osd_amd/build.py).  Every device block, page-locked block, stream and event below is held by an owning type of
+// owned.h: deleting a handle frees all of it, and a resource added to Lane, CallRecord or bposd_handle needs no line anywhere else.
 #pragma once
 #include "../../include/bposd_mi355x.h"
 #include "../../include/bposd_mi355x_debug.h"
@@ -16,11 +17,7 @@
 
 #include "bp_kernel.hip.h"   // BpParams, bp_lds_bytes (templates only: nothing is instantiated by including it)
 #include "osd_kernel.hip.h"  // OsdParams
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
+#include "owned.h"           // DeviceGuard, DevBuf, DevArray, PinnedBuf, Stream, Event
 
 // Per-call state.  A handle owns BPOSD_LANES of these and alternates between them: consecutive decode calls (and the
 // chunks of one host-pointer call) run on different HIP streams with their own workspaces, so the persistent
@@ -29,18 +26,17 @@ constexpr int BPOSD_LANES = 4;  // large codes (HBM-resident workspaces of sever
 constexpr int BPOSD_MAX_CHUNKS = 16;  // chunks of one host-pointer call (bposd_decode_batch)
 
 struct Lane {
-    hipStream_t stream = nullptr;
+    Stream stream;
     // The OSD kernel of a call runs on a stream of its own at the highest priority (ordered behind the call's BP kernel
     // and in front of whatever follows on `stream` by events): its few, fat workgroups otherwise queue behind the full
     // grid of the NEXT call's BP kernel for every CU that frees up and take many times their own run time.
-    hipStream_t osd_stream = nullptr;
-    hipEvent_t ev_bp = nullptr, ev_osd = nullptr;
-    hipEvent_t ev_done = nullptr;  // both kernels of the lane's last (non-lean) call have ended
+    Stream osd_stream;
+    Event ev_bp, ev_osd;
+    Event ev_done;  // both kernels of the lane's last (non-lean) call have ended
     bool done_recorded = false;
-    void* h_stage = nullptr;     // page-locked, device-visible staging for small host-pointer calls (zero-copy path)
-    size_t h_stage_bytes = 0;
-    hipEvent_t ev_up = nullptr;  // host-pointer calls: this lane's chunk has been uploaded (uploads go one at a time, in
-                                 // chunk order: the first chunk's kernels then start after one chunk's copy time)
+    PinnedBuf h_stage;  // page-locked, device-visible staging for small host-pointer calls (zero-copy path)
+    Event ev_up;        // host-pointer calls: this lane's chunk has been uploaded (uploads go one at a time, in
+                        // chunk order: the first chunk's kernels then start after one chunk's copy time)
     DevBuf bpl_msg, bpl_llr;  // large BP workspaces (bpl_llr also serves the local-edge kernel: LLRs of the current syndrome)
     DevBuf osdl_ws;           // large OSD workspaces (matrix, sort keys, pivots, weights) carved from one allocation
     DevBuf osd_rows_ws;       // OSD kernel's per-workgroup spill area for finished row words
@@ -48,42 +44,45 @@ struct Lane {
     // host-pointer calls with a channel row per shot (bposd_decode_batch_rows): the chunk's prior and weight rows, [chunk][n]
     // doubles each, and the page-locked block the host converts the caller's probabilities into before the upload
     DevBuf io_l0rows, io_costrows;
-    double* h_rows = nullptr;
-    size_t h_rows_cap = 0;           // doubles
+    PinnedBuf h_rows;
     // host-pointer calls: the outputs are downloaded on a copy stream of the lane's own right after the BP kernel (event-
     // ordered), the rows the OSD kernel rewrites come from compact copies [list slot][n] once it has run
     DevBuf io_cmp0, io_cmpw;
     // bit-packed host I/O (bposd_decode_batch_packed): packed syndromes in, packed rows out, packed compact OSD rows
     DevBuf io_psynd, io_posdw, io_posd0, io_pbp, io_pcmp;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copy = nullptr;    // the chunk's downloads have left the lane's io buffers
-    int* h_list = nullptr;           // page-locked copy of the chunk's OSD list (syndrome index per slot)
-    size_t h_list_cap = 0;
+    Stream copy_stream;
+    Event ev_copy;                   // the chunk's downloads have left the lane's io buffers
+    PinnedBuf h_list;                // page-locked copy of the chunk's OSD list (syndrome index per slot, ints)
     bool copy_pending = false;
-    long long* d_osd_dbg = nullptr;  // diagnostics (BPOSD_OSD_DEBUG=1): phase timestamps
-    int* d_counters = nullptr;       // 4 ints
+    DevArray<long long> d_osd_dbg;   // diagnostics (BPOSD_OSD_DEBUG=1): phase timestamps
+    DevArray<int> d_counters;        // 4 ints, and behind them the 64-bit iteration total
     // per-shot channel of a device-pointer call (bposd_decode_batch_select_device): priors and weights of the alternative
     // channel, 2n doubles, copied from a page-locked staging block on the lane's own stream -- consecutive select calls
     // overlap like plain ones (the first version drained every lane and made two blocking copies per call)
-    double* d_alt = nullptr;
-    double* h_alt = nullptr;
-    hipEvent_t ev_alt = nullptr;     // the staging block has been read
+    DevArray<double> d_alt;
+    PinnedBuf h_alt;
+    Event ev_alt;                    // the staging block has been read
     bool alt_busy = false;
-    int* h_tail = nullptr;           // page-locked, device-visible: the BP kernel of this lane's current call has entered its tail
+    PinnedBuf h_tail;                // one int, page-locked, device-visible: the BP kernel of this lane's current call has entered its tail
 };
 
 // What bposd_last_timing reports: one record per kernel pair launched by the last call (one per chunk for a
 // host-pointer call).  Events and the pinned counter copies live in the handle so that records outlive lane reuse.
 struct CallRecord {
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    int* h_counters = nullptr;               // pinned: 4 ints
-    unsigned long long* h_iter_total = nullptr;  // pinned
+    Event ev[3];
+    PinnedBuf h_counters;  // 4 ints, and behind them the 64-bit iteration total (the layout of Lane::d_counters)
+    int* counters() const { return h_counters.as<int>(); }
+    unsigned long long* iter_total() const { return (unsigned long long*)(counters() + 4); }
     bool ran_osd = false;
     bool recorded = false;  // the counters (and, when timed, the events) have been recorded at least once
     bool timed = false;     // the three events bracket the kernels of this record (not on the lean small-call path)
 };
 
 struct bposd_handle {
+    // lives where `new` put it: DecodeCall points into lanes[] and the record arrays
+    bposd_handle() = default;
+    bposd_handle(const bposd_handle&) = delete;
+    bposd_handle& operator=(const bposd_handle&) = delete;
     bposd_config cfg{};
     int device = 0;
     Lane lanes[BPOSD_LANES];
@@ -103,13 +102,13 @@ struct bposd_handle {
     int local_mp = 0;
     long long local_passes = 0;  // modelled ds_read_b64 cycles of the bit pass in the chosen layout (floor: 4 * MP / 32)
     long long local_wcycles = 0; // modelled ds_write_b64 cycles of the bit pass (floor: 6 * 4 * MP / 64)
-    int *d_lpos_chk = nullptr, *d_lpos_bit = nullptr, *d_lpos_alo = nullptr, *d_lpos_ahi = nullptr, *d_lgrp_dl = nullptr, *d_lpos_dl = nullptr;
+    DevArray<int> d_lpos_chk, d_lpos_bit, d_lpos_alo, d_lpos_ahi, d_lgrp_dl, d_lpos_dl;
     // class BP kernel (bp_class_kernel.hip.h): every check has the same degree, bit degrees inside one compiled range
     bool bp_any = false;  // degrees beyond the compiled kernels: bp_anydeg_kernel.hip.h (run-time degree loops, messages in HBM)
     bool class_ok = false;
     int class_dclo = 0, class_dc = 0, class_dvlo = 0, class_dvhi = 0, class_mp = 0, class_nt = 0;
     long class_read_cycles = 0, class_write_cycles = 0, class_read_floor = 0, class_write_floor = 0;  // modelled, one bit pass
-    int *d_cpos_chk = nullptr, *d_cpos_bit = nullptr, *d_cbit_slot = nullptr, *d_cgrp_deg = nullptr, *d_cgrp_cdeg = nullptr;
+    DevArray<int> d_cpos_chk, d_cpos_bit, d_cbit_slot, d_cgrp_deg, d_cgrp_cdeg;
     bool large = false;   // beyond the register-resident OSD kernel: HBM-resident matrix, device rank probe
     bool bp_hbm = false;  // BP messages do not fit one CU's LDS either: HBM-resident BP kernel
     int max_iter = 0;
@@ -127,17 +126,17 @@ struct bposd_handle {
     std::vector<int> rp, ci;
     std::vector<double> probs;
     // device tables
-    int *d_rp = nullptr, *d_ci = nullptr;
-    int *d_chk_deg = nullptr, *d_var_deg = nullptr, *d_var_pos = nullptr, *d_pos_bit = nullptr, *d_var_ck = nullptr;
+    DevArray<int> d_rp, d_ci;
+    DevArray<int> d_chk_deg, d_var_deg, d_var_pos, d_pos_bit, d_var_ck;
     int large_form = 0;  // form of the last bp_large_kernel launch: 0 per-edge messages (product-sum), 1 check records in the workspace, 2 per-check data in LDS
     int tab_np = 0;
     long layout_cost = 0, layout_cost_natural = 0, layout_cost_ideal = 0;  // simulated LDS cycles of the bit pass
-    double* d_llr0 = nullptr;
-    double* d_cost = nullptr;  // log(1/p_i): OSD-W weights of the ldpc-v2 weight function
-    double *d_llr0_alt = nullptr, *d_cost_alt = nullptr;  // alternative channel of the two-valued per-shot form
+    DevArray<double> d_llr0;
+    DevArray<double> d_cost;  // log(1/p_i): OSD-W weights of the ldpc-v2 weight function
+    DevArray<double> d_llr0_alt, d_cost_alt;  // alternative channel of the two-valued per-shot form
     bool fp_weights = false;   // non-uniform (or degenerate) channel: candidate weights need the fp64 sums
     // serial schedule (cfg.schedule == 1): CSC view and level lists
-    int *d_cp = nullptr, *d_ce = nullptr, *d_erow = nullptr, *d_lvl_ptr = nullptr, *d_lvl_bits = nullptr;
+    DevArray<int> d_cp, d_ce, d_erow, d_lvl_ptr, d_lvl_bits;
     int nlevels = 0;
     int tab_dc = 0, tab_dv = 0, tab_mp = 0;  // layout the tables were built for
     bool have_timing = false;
@@ -184,10 +183,10 @@ int set_max_lds(bposd_handle* h, const void* kernel, size_t lds);
 int cached_occupancy(bposd_handle* h, const void* kernel, int nt, size_t lds, int* out);
 int ensure(bposd_handle* h, DevBuf& b, size_t bytes);
 int ensure_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes);
-void release(DevBuf& b);
+int ensure_pinned(bposd_handle* h, PinnedBuf& b, size_t bytes, unsigned flags);  // as ensure(): freed, then allocated anew
 
 // ---- table construction (host_tables.hip)
-int upload_ints(bposd_handle* h, int** dst, const std::vector<int>& v);  // (a table that exists is freed first)
+int upload_ints(bposd_handle* h, DevArray<int>& dst, const std::vector<int>& v);  // (a table that exists is freed first)
 int build_tables(bposd_handle* h, int DC, int DV, int MP, int NT, int VPT);  // bp_kernel (rebuilt by launch_bp when the shape changes)
 int build_tables_local(bposd_handle* h);  // sets local_ok
 int build_tables_class(bposd_handle* h);  // sets class_ok
@@ -197,6 +196,7 @@ struct DegPair { int dc, dv; };
 bool pick_pair(int dc, int dv, DegPair* out);  // the compiled bp_kernel degree pair that covers (dc, dv)
 int gf2_rank_host(int m, int n, const std::vector<int>& rp, const std::vector<int>& ci);
 int upload_priors(bposd_handle* h);
+int64_t first_bad_prob(const double* probs, int64_t count);  // index + 1 of the first value outside [0, 1] (NaN included), 0: none
 int64_t channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost);  // bposd_channel_tables
 int probe_rank_large(bposd_handle* h, const DecodeCall& call, int* rank);
 int num_candidates(const bposd_handle* h);

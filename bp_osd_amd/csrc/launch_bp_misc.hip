@@ -143,10 +143,10 @@ extern "C" int bposd_debug_portable_math(int32_t which, const double* a, const d
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BPOSD_ERR_NO_DEVICE;
     const size_t bytes = sizeof(double) * (size_t)count;
-    double *d_a = nullptr, *d_b = nullptr, *d_y = nullptr;
-    hipError_t e = hipMalloc((void**)&d_a, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_y, bytes);
-    if (e == hipSuccess && which == 4) e = hipMalloc((void**)&d_b, bytes);
+    DevArray<double> d_a, d_b, d_y;
+    hipError_t e = d_a.alloc(bytes);
+    if (e == hipSuccess) e = d_y.alloc(bytes);
+    if (e == hipSuccess && which == 4) e = d_b.alloc(bytes);
     if (e == hipSuccess) e = hipMemcpy(d_a, a, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess && which == 4) e = hipMemcpy(d_b, b, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -155,8 +155,5 @@ extern "C" int bposd_debug_portable_math(int32_t which, const double* a, const d
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(y, d_y, bytes, hipMemcpyDeviceToHost);  // (synchronises with the kernel on the null stream)
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    (void)hipFree(d_y);
     return e == hipSuccess ? BPOSD_OK : BPOSD_ERR_HIP;
 }

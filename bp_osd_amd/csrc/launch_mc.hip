@@ -10,6 +10,7 @@
 #include <climits>
 #include <cstdarg>
 #include <cstring>
+#include <memory>
 
 #include "mc_kernels.hip.h"
 
@@ -22,20 +23,20 @@ struct bposd_mc {
     long long capacity = 0, last_B = 0;
     int num_cu = 0;
     size_t device_bytes = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_sampled = nullptr, ev_x = nullptr, ev_z = nullptr;
+    Stream stream;
+    Event ev_sampled, ev_x, ev_z;
     std::vector<double> alt;  // second decoder's probabilities where the first one's osdw bit is 1 (channel_update != none)
     // device tables
-    double* d_thr = nullptr;
-    int *d_hx_rp = nullptr, *d_hx_ci = nullptr, *d_hz_rp = nullptr, *d_hz_ci = nullptr;
-    unsigned long long *d_lxT = nullptr, *d_lzT = nullptr;
+    DevArray<double> d_thr;
+    DevArray<int> d_hx_rp, d_hx_ci, d_hz_rp, d_hz_ci;
+    DevArray<unsigned long long> d_lxT, d_lzT;
     // per-batch buffers (capacity rows)
-    unsigned long long *d_err_x = nullptr, *d_err_z = nullptr, *d_psynd_x = nullptr, *d_psynd_z = nullptr;
-    uint8_t *d_synd_x = nullptr, *d_synd_z = nullptr, *d_flags = nullptr;
-    uint8_t* d_out[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // bp x, bp z, osd0 x, osd0 z, osdw x, osdw z
-    uint8_t *d_conv_x = nullptr, *d_conv_z = nullptr;
-    int* d_counters = nullptr;
-    int* h_counters = nullptr;  // page-locked: [0..6] results, [8..14] the initial values
+    DevArray<unsigned long long> d_err_x, d_err_z, d_psynd_x, d_psynd_z;
+    DevArray<uint8_t> d_synd_x, d_synd_z, d_flags;
+    DevArray<uint8_t> d_out[6];  // bp x, bp z, osd0 x, osd0 z, osdw x, osdw z
+    DevArray<uint8_t> d_conv_x, d_conv_z;
+    DevArray<int> d_counters;
+    PinnedBuf h_counters;  // 16 ints: [0..6] results, [8..14] the initial values
     std::string err;
 };
 
@@ -60,34 +61,19 @@ int mc_fail(bposd_mc* mc, int code, const char* fmt, ...) {
             return mc_fail(mc, BPOSD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
-// the engine works on its device and puts the caller's current device back on exit
-struct McDeviceGuard {
-    int prev = -1, dev = -1;
-    hipError_t err = hipSuccess;
-    explicit McDeviceGuard(int d) : dev(d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) err = hipSetDevice(dev);
-    }
-    ~McDeviceGuard() {
-        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-    }
-    McDeviceGuard(const McDeviceGuard&) = delete;
-    McDeviceGuard& operator=(const McDeviceGuard&) = delete;
-};
-
 template <class T>
-int mc_alloc(bposd_mc* mc, T** p, size_t count) {
+int mc_alloc(bposd_mc* mc, DevArray<T>& p, size_t count) {
     const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-    MC_TRY(mc, hipMalloc((void**)p, bytes));
+    MC_TRY(mc, p.alloc(bytes));
     mc->device_bytes += bytes;
     return 0;
 }
 
 template <class T>
-int mc_upload(bposd_mc* mc, T** p, const T* src, size_t count) {
+int mc_upload(bposd_mc* mc, DevArray<T>& p, const T* src, size_t count) {
     int rc = mc_alloc(mc, p, count);
     if (rc) return rc;
-    if (count) MC_TRY(mc, hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    if (count) MC_TRY(mc, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -122,32 +108,33 @@ int create_impl(bposd_mc* mc, const int32_t* hx_rp, const int32_t* hx_ci, const 
         thr[(size_t)n + i] = pz[i] + px[i];
         thr[2 * (size_t)n + i] = px[i] + py[i] + pz[i];
     }
-    if ((rc = mc_upload(mc, &mc->d_thr, thr.data(), thr.size()))) return rc;
-    if ((rc = mc_upload(mc, &mc->d_hx_rp, hx_rp, (size_t)mc->mx + 1))) return rc;
-    if ((rc = mc_upload(mc, &mc->d_hx_ci, hx_ci, (size_t)hx_rp[mc->mx]))) return rc;
-    if ((rc = mc_upload(mc, &mc->d_hz_rp, hz_rp, (size_t)mc->mz + 1))) return rc;
-    if ((rc = mc_upload(mc, &mc->d_hz_ci, hz_ci, (size_t)hz_rp[mc->mz]))) return rc;
+    if ((rc = mc_upload(mc, mc->d_thr, thr.data(), thr.size()))) return rc;
+    if ((rc = mc_upload(mc, mc->d_hx_rp, hx_rp, (size_t)mc->mx + 1))) return rc;
+    if ((rc = mc_upload(mc, mc->d_hx_ci, hx_ci, (size_t)hx_rp[mc->mx]))) return rc;
+    if ((rc = mc_upload(mc, mc->d_hz_rp, hz_rp, (size_t)mc->mz + 1))) return rc;
+    if ((rc = mc_upload(mc, mc->d_hz_ci, hz_ci, (size_t)hz_rp[mc->mz]))) return rc;
     const auto lxT = transpose_words(lx, mc->k, mc->words), lzT = transpose_words(lz, mc->k, mc->words);
-    if ((rc = mc_upload(mc, &mc->d_lxT, lxT.data(), lxT.size()))) return rc;
-    if ((rc = mc_upload(mc, &mc->d_lzT, lzT.data(), lzT.size()))) return rc;
+    if ((rc = mc_upload(mc, mc->d_lxT, lxT.data(), lxT.size()))) return rc;
+    if ((rc = mc_upload(mc, mc->d_lzT, lzT.data(), lzT.size()))) return rc;
     const size_t C = (size_t)mc->capacity;
-    if ((rc = mc_alloc(mc, &mc->d_err_x, C * mc->words))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_err_z, C * mc->words))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_psynd_x, C * mc->swx))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_psynd_z, C * mc->swz))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_synd_x, C * mc->mz))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_synd_z, C * mc->mx))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_flags, C))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_err_x, C * mc->words))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_err_z, C * mc->words))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_psynd_x, C * mc->swx))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_psynd_z, C * mc->swz))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_synd_x, C * mc->mz))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_synd_z, C * mc->mx))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_flags, C))) return rc;
     for (auto& p : mc->d_out)
-        if ((rc = mc_alloc(mc, &p, C * n))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_conv_x, C))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_conv_z, C))) return rc;
-    if ((rc = mc_alloc(mc, &mc->d_counters, 8))) return rc;
-    MC_TRY(mc, hipHostMalloc((void**)&mc->h_counters, 16 * sizeof(int), hipHostMallocDefault));
-    for (int i = 0; i < 16; ++i) mc->h_counters[i] = 0;
-    mc->h_counters[8 + 5] = mc->h_counters[8 + 6] = INT_MAX;
-    MC_TRY(mc, hipStreamCreateWithFlags(&mc->stream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&mc->ev_sampled, &mc->ev_x, &mc->ev_z}) MC_TRY(mc, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        if ((rc = mc_alloc(mc, p, C * n))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_conv_x, C))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_conv_z, C))) return rc;
+    if ((rc = mc_alloc(mc, mc->d_counters, 8))) return rc;
+    MC_TRY(mc, mc->h_counters.alloc(16 * sizeof(int), hipHostMallocDefault));
+    int* const hc = mc->h_counters.as<int>();
+    for (int i = 0; i < 16; ++i) hc[i] = 0;
+    hc[8 + 5] = hc[8 + 6] = INT_MAX;
+    MC_TRY(mc, hipStreamCreateWithFlags(&mc->stream.raw, hipStreamNonBlocking));
+    for (Event* e : {&mc->ev_sampled, &mc->ev_x, &mc->ev_z}) MC_TRY(mc, hipEventCreateWithFlags(&e->raw, hipEventDisableTiming));
     return 0;
 }
 
@@ -171,18 +158,8 @@ const char* bposd_mc_last_error(bposd_mc* mc) { return mc ? mc->err.c_str() : bp
 
 void bposd_mc_destroy(bposd_mc* mc) {
     if (!mc) return;
-    McDeviceGuard guard(mc->cfg.device);
+    DeviceGuard guard(mc->cfg.device);  // (outlives the delete)
     if (mc->stream) (void)hipStreamSynchronize(mc->stream);
-    for (void* p : {(void*)mc->d_thr, (void*)mc->d_hx_rp, (void*)mc->d_hx_ci, (void*)mc->d_hz_rp, (void*)mc->d_hz_ci, (void*)mc->d_lxT,
-                    (void*)mc->d_lzT, (void*)mc->d_err_x, (void*)mc->d_err_z, (void*)mc->d_psynd_x, (void*)mc->d_psynd_z, (void*)mc->d_synd_x,
-                    (void*)mc->d_synd_z, (void*)mc->d_flags, (void*)mc->d_out[0], (void*)mc->d_out[1], (void*)mc->d_out[2],
-                    (void*)mc->d_out[3], (void*)mc->d_out[4], (void*)mc->d_out[5], (void*)mc->d_conv_x, (void*)mc->d_conv_z,
-                    (void*)mc->d_counters})
-        if (p) (void)hipFree(p);
-    if (mc->h_counters) (void)hipHostFree(mc->h_counters);
-    for (hipEvent_t e : {mc->ev_sampled, mc->ev_x, mc->ev_z})
-        if (e) (void)hipEventDestroy(e);
-    if (mc->stream) (void)hipStreamDestroy(mc->stream);
     delete mc;
 }
 
@@ -212,7 +189,8 @@ int bposd_mc_create(const bposd_mc_config* cfg, bposd_handle* dec_x, bposd_handl
     if ((rc = check_csr(nullptr, "hx", hx_indptr, hx_indices, mx, n))) return rc;
     if ((rc = check_csr(nullptr, "hz", hz_indptr, hz_indices, mz, n))) return rc;
 
-    bposd_mc* mc = new bposd_mc();
+    std::unique_ptr<bposd_mc, decltype(&bposd_mc_destroy)> owner(new bposd_mc(), bposd_mc_destroy);
+    bposd_mc* const mc = owner.get();
     mc->cfg = *cfg;
     mc->dec_x = dec_x;
     mc->dec_z = dec_z;
@@ -227,16 +205,12 @@ int bposd_mc_create(const bposd_mc_config* cfg, bposd_handle* dec_x, bposd_handl
     mc->num_cu = dec_x->num_cu > 0 ? dec_x->num_cu : 256;
     if (alt_probs) mc->alt.assign(alt_probs, alt_probs + n);
     {
-        McDeviceGuard guard(cfg->device);
+        DeviceGuard guard(cfg->device);
         rc = guard.err != hipSuccess ? mc_fail(mc, BPOSD_ERR_HIP, "hipSetDevice(%d) failed", cfg->device)
                                      : create_impl(mc, hx_indptr, hx_indices, hz_indptr, hz_indices, lx_words, lz_words, probs_x, probs_y, probs_z);
     }
-    if (rc) {
-        mc_fail(nullptr, rc, "%s", mc->err.c_str());
-        bposd_mc_destroy(mc);
-        return rc;
-    }
-    *out = mc;
+    if (rc) return mc_fail(nullptr, rc, "%s", mc->err.c_str());
+    *out = owner.release();
     return BPOSD_OK;
 }
 
@@ -244,7 +218,7 @@ int bposd_mc_run(bposd_mc* mc, uint64_t first_shot, int64_t B, int64_t counters[
     if (!mc) return BPOSD_ERR_INVALID;
     if (!counters) return mc_fail(mc, BPOSD_ERR_INVALID, "counters is NULL");
     if (B < 1 || B > mc->capacity) return mc_fail(mc, BPOSD_ERR_INVALID, "batch size %lld outside [1, capacity %lld]", (long long)B, mc->capacity);
-    McDeviceGuard guard(mc->cfg.device);
+    DeviceGuard guard(mc->cfg.device);
     MC_TRY(mc, guard.err);
     mc->last_B = 0;
     const unsigned grid = (unsigned)std::min<long long>(B, (long long)mc->num_cu * 8);
@@ -274,7 +248,7 @@ int bposd_mc_run(bposd_mc* mc, uint64_t first_shot, int64_t B, int64_t counters[
     hipLaunchKernelGGL(mc_sample_kernel, dim3(grid), dim3(MC_THREADS), 2 * sizeof(unsigned long long) * (size_t)mc->words, mc->stream, S);
     MC_TRY(mc, hipGetLastError());
     MC_TRY(mc, hipEventRecord(mc->ev_sampled, mc->stream));
-    MC_TRY(mc, hipMemcpyAsync(mc->d_counters, mc->h_counters + 8, 7 * sizeof(int), hipMemcpyHostToDevice, mc->stream));
+    MC_TRY(mc, hipMemcpyAsync(mc->d_counters, mc->h_counters.as<int>() + 8, 7 * sizeof(int), hipMemcpyHostToDevice, mc->stream));
 
     uint8_t *bp_x = mc->d_out[0], *bp_z = mc->d_out[1], *osd0_x = mc->d_out[2], *osd0_z = mc->d_out[3], *osdw_x = mc->d_out[4], *osdw_z = mc->d_out[5];
     int rc;
@@ -311,9 +285,9 @@ int bposd_mc_run(bposd_mc* mc, uint64_t first_shot, int64_t B, int64_t counters[
     Q.counters = mc->d_counters;
     hipLaunchKernelGGL(mc_score_kernel, dim3(grid), dim3(MC_THREADS), 6 * sizeof(unsigned long long) * (size_t)mc->words + 8 * sizeof(int), mc->stream, Q);
     MC_TRY(mc, hipGetLastError());
-    MC_TRY(mc, hipMemcpyAsync(mc->h_counters, mc->d_counters, 7 * sizeof(int), hipMemcpyDeviceToHost, mc->stream));
+    MC_TRY(mc, hipMemcpyAsync(mc->h_counters.p, mc->d_counters, 7 * sizeof(int), hipMemcpyDeviceToHost, mc->stream));
     MC_TRY(mc, hipStreamSynchronize(mc->stream));  // the batch's one host wait
-    for (int i = 0; i < 7; ++i) counters[i] = mc->h_counters[i];
+    for (int i = 0; i < 7; ++i) counters[i] = mc->h_counters.as<int>()[i];
     mc->last_B = B;
     return BPOSD_OK;
 }
@@ -337,7 +311,7 @@ int bposd_mc_fetch(bposd_mc* mc, int32_t what, void* host_dst, size_t bytes) {
     const size_t want = row * (size_t)mc->last_B;
     if (bytes != want) return mc_fail(mc, BPOSD_ERR_INVALID, "the last batch holds %zu bytes of item %d, not %zu", want, what, bytes);
     if (want == 0) return BPOSD_OK;
-    McDeviceGuard guard(mc->cfg.device);
+    DeviceGuard guard(mc->cfg.device);
     MC_TRY(mc, guard.err);
     MC_TRY(mc, hipMemcpy(host_dst, src, want, hipMemcpyDeviceToHost));  // bposd_mc_run has waited for the batch
     return BPOSD_OK;
