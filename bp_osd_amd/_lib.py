@@ -37,6 +37,14 @@ EXPORTED_SYMBOLS = (
     "bposd_decode_batch_rows_device",
     "bposd_pack_rows_device",
     "bposd_pack_rows_device_lane",
+    "bposd_observable_table",
+    "bposd_set_observables",
+    "bposd_observables_device_lane",
+    "bposd_decode_batch_observables_device",
+    "bposd_decode_batch_observables",
+    "bposd_decode_batch_observables_packed",
+    "bposd_decode_batch_observables_async",
+    "bposd_decode_batch_observables_packed_async",
     "bposd_synchronize",
     "bposd_num_lanes",
     "bposd_last_lane",
@@ -68,6 +76,7 @@ DEBUG_SYMBOLS = (
     "bposd_debug_local_keys",
     "bposd_debug_local_waves",
     "bposd_debug_last_pair_key",
+    "bposd_debug_obs_timing",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
     "bposd_debug_portable_math",
@@ -156,6 +165,18 @@ def load():
     lib.bposd_decode_batch_rows_device.restype = C.c_int
     lib.bposd_pack_rows_device.argtypes = [vp, vp, C.c_int64, C.c_int32, vp]
     lib.bposd_pack_rows_device.restype = C.c_int
+    lib.bposd_observable_table.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
+    lib.bposd_observable_table.restype = C.c_int
+    lib.bposd_set_observables.argtypes = [vp, vp, C.c_int32]
+    lib.bposd_set_observables.restype = C.c_int
+    lib.bposd_observables_device_lane.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int64, vp]
+    lib.bposd_observables_device_lane.restype = C.c_int
+    lib.bposd_decode_batch_observables_device.argtypes = [vp, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp]
+    lib.bposd_decode_batch_observables_device.restype = C.c_int
+    for name in ("bposd_decode_batch_observables", "bposd_decode_batch_observables_packed", "bposd_decode_batch_observables_async",
+                 "bposd_decode_batch_observables_packed_async"):
+        getattr(lib, name).argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+        getattr(lib, name).restype = C.c_int
     lib.bposd_synchronize.argtypes = [vp]
     lib.bposd_synchronize.restype = C.c_int
     lib.bposd_num_lanes.argtypes = [vp]
@@ -193,6 +214,8 @@ def load():
     lib.bposd_debug_local_waves.restype = C.c_int
     lib.bposd_debug_last_pair_key.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.bposd_debug_last_pair_key.restype = C.c_int
+    lib.bposd_debug_obs_timing.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    lib.bposd_debug_obs_timing.restype = C.c_int
     lib.bposd_debug_class_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.bposd_debug_class_layout.restype = C.c_int
     lib.bposd_debug_last_instance.argtypes = [vp, vp, vp]

@@ -115,6 +115,17 @@ int ensure_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes) {
     }
     return 0;
 }
+
+// The same buffer of every lane holds at least `bytes`; where one has to grow, the calls in flight are drained first (once
+// per entry point: `drained`) -- they may still use the old buffers.  No allocation inside a later call of the same size.
+int grow_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes, bool* drained) {
+    bool have = true;
+    for (int l = 0; l < h->nlanes; ++l) have = have && (h->lanes[l].*member).p && (h->lanes[l].*member).bytes >= bytes;
+    if (have) return 0;
+    if (!*drained && h->async_pending) { int rcs = sync_all_lanes(h); if (rcs) return rcs; }
+    *drained = true;
+    return ensure_lanes(h, member, bytes);
+}
 }  // namespace bposd_host
 
 __global__ void pack_rows_kernel(const uint8_t* __restrict__ in, long long B, int n, int wpr,
@@ -614,6 +625,7 @@ static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoP
     }
     if (!lean) HIP_TRY(h, hipEventRecord(R.ev[1], L.stream));
     R.ran_osd = false;
+    R.ran_obs = false;
     if (!lean && (osd_on || call.tail_gate)) HIP_TRY(h, hipEventRecord(L.ev_bp, L.stream));  // the BP kernel has ended
     if (osd_on) {
         if (!lean) HIP_TRY(h, hipStreamWaitEvent(L.osd_stream, L.ev_bp, 0));
@@ -864,6 +876,15 @@ struct DrainOnError {
     }
 };
 
+// Chunks of a synchronous host-pointer call of B syndromes, about `target` each (BPOSD_HOST_CHUNK overrides the target), at
+// most BPOSD_MAX_CHUNKS; an HBM-resident code keeps at least four workgroups per CU in a chunk.
+static int host_chunk_count(const bposd_handle* h, int64_t B, long long target) {
+    if (const char* e = getenv("BPOSD_HOST_CHUNK")) target = std::max(1LL, atoll(e));
+    int nchunks = (int)std::min<long long>(BPOSD_MAX_CHUNKS, std::max<long long>(1, (B + target / 2) / target));
+    if (h->large) nchunks = (int)std::min<long long>(nchunks, std::max<long long>(1, B / (4LL * h->num_cu)));
+    return nchunks;
+}
+
 static size_t row_bytes(int bits, bool packed) { return packed ? ((size_t)bits + 63) / 64 * 8 : (size_t)bits; }
 
 // A lane's staging buffers for a host-pointer call that wants the outputs named in `host`: rows of words or of bytes.
@@ -967,9 +988,7 @@ static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool
     long long target = 32768;
     // (a channel row per shot is 16 n bytes next to the syndrome's m: chunks of ~64 MB of rows bound what a lane stages)
     if (prob_rows) target = std::min<long long>(target, std::max<long long>(1024, ((long long)64 << 20) / (16LL * h->n)));
-    if (const char* e = getenv("BPOSD_HOST_CHUNK")) target = std::max(1LL, atoll(e));
-    int nchunks = (int)std::min<long long>(BPOSD_MAX_CHUNKS, std::max<long long>(1, (B + target / 2) / target));
-    if (h->large) nchunks = (int)std::min<long long>(nchunks, std::max<long long>(1, B / (4LL * h->num_cu)));
+    int nchunks = host_chunk_count(h, B, target);
     long long CH = (B + nchunks - 1) / nchunks;  // capacity of a lane's io buffers = the largest chunk
     nchunks = (int)((B + CH - 1) / CH);
     // chunk boundaries: equal sizes, except that a four-chunk call (one chunk per lane) tapers 7 : 7 : 6 : 4 -- what
@@ -1135,14 +1154,7 @@ static int decode_host_async_impl(bposd_handle* h, const IoPtrs& host, int64_t B
     const size_t rsn = row_bytes(h->n, packed), rsm = row_bytes(h->m, packed);
     int rc;
     bool grew = false;
-    auto need = [&](DevBuf Lane::*member, size_t bytes) -> int {
-        bool have = true;
-        for (int l = 0; l < h->nlanes; ++l) have = have && (h->lanes[l].*member).p && (h->lanes[l].*member).bytes >= bytes;
-        if (have) return 0;
-        if (!grew && h->async_pending) { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls may still use the old buffers
-        grew = true;
-        return ensure_lanes(h, member, bytes);
-    };
+    auto need = [&](DevBuf Lane::*member, size_t bytes) -> int { return grow_lanes(h, member, bytes, &grew); };
     if ((rc = need(&Lane::io_synd, b8 * m))) return rc;
     if ((rc = need(&Lane::io_osdw, b8 * n))) return rc;
     if (host.osd0 && (rc = need(&Lane::io_osd0, b8 * n))) return rc;
@@ -1198,6 +1210,235 @@ int bposd_decode_batch_packed_async(bposd_handle* h, const uint64_t* synd_words,
                                     uint64_t* bp_words, uint8_t* conv, int32_t* iters) {
     return decode_host_async_impl(h, IoPtrs{(const uint8_t*)synd_words, nullptr, (uint8_t*)osdw_words, (uint8_t*)osd0_words, (uint8_t*)bp_words, conv,
                                             iters, nullptr}, B, /*packed=*/true);
+}
+
+// ================================================================================ logical observables
+// What a caller asks of a correction is which logical observables it flips: obs_kernel (obs_kernel.hip.h) computes L . row for
+// the rows a decode left on its lane, and ceil(k / 64) words per shot and output leave the device instead of ceil(n / 64).
+
+int bposd_observable_table(const int32_t* indptr, const int32_t* indices, int32_t k, int32_t n, uint64_t* table) {
+    std::string why;
+    if (const int rc = observable_table(indptr, indices, k, n, table, &why)) return fail(nullptr, rc, "%s", why.c_str());
+    return BPOSD_OK;
+}
+
+int bposd_set_observables(bposd_handle* h, const uint64_t* table, int32_t k) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (k < 0 || k > obs_max_k()) return fail(h, BPOSD_ERR_INVALID, "bposd_set_observables: k = %d is outside 0 .. %d", k, obs_max_k());
+    if (k > 0 && !table) return fail(h, BPOSD_ERR_INVALID, "bposd_set_observables: the table is required");
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls may still read the old table
+    h->obs_k = 0;
+    if (k == 0) {
+        HIP_TRY(h, h->d_obs_table.release());
+        return BPOSD_OK;
+    }
+    const size_t bytes = sizeof(uint64_t) * (size_t)((h->n + 63) / 64) * (size_t)k;
+    HIP_TRY(h, h->d_obs_table.alloc(bytes));
+    HIP_TRY(h, hipMemcpy(h->d_obs_table, table, bytes, hipMemcpyHostToDevice));
+    h->obs_k = k;
+    return BPOSD_OK;
+}
+
+static int check_observables(bposd_handle* h) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (h->obs_k <= 0) return fail(h, BPOSD_ERR_INVALID, "no observables are set on this handle (bposd_set_observables)");
+    return BPOSD_OK;
+}
+
+int bposd_observables_device_lane(bposd_handle* h, int32_t lane, const void* d_rows, int32_t packed, int64_t B, uint64_t* d_obs_words) {
+    if (const int rc = check_observables(h)) return rc;
+    if (lane < 0 || lane >= h->nlanes) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range", lane);
+    if (B < 0 || B > 0x7fffffffLL || (B > 0 && (!d_rows || !d_obs_words))) return fail(h, BPOSD_ERR_INVALID, "bad observables arguments");
+    if (B == 0) return BPOSD_OK;
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    // queued behind the device-pointer decode that ran on this lane (stream order)
+    const void* const rows[3] = {d_rows, nullptr, nullptr};
+    uint64_t* const outs[3] = {d_obs_words, nullptr, nullptr};
+    return launch_obs(h, h->lanes[lane].stream, rows, packed != 0, B, outs);
+}
+
+// The outputs of an observables decode: rows of ceil(k / 64) words, flags and iteration counts (host or device memory).
+struct ObsOut {
+    uint64_t *osdw = nullptr, *osd0 = nullptr, *bp = nullptr;
+    uint8_t* conv = nullptr;
+    int32_t* iters = nullptr;
+};
+
+// Lane buffers of an observables decode of up to `cap` syndromes: the rows the kernels write (packed where the kernels are,
+// bytes otherwise), the syndromes in the kernels' form where the caller's are in the other one, and for a host-pointer
+// call the syndromes as uploaded and the outputs to download.
+static int obs_reserve(bposd_handle* h, size_t cap, const ObsOut& out, bool host, bool synd_packed) {
+    const bool native = native_packed(h);
+    const size_t rs = row_bytes(h->n, native), ob = sizeof(uint64_t) * (size_t)((h->obs_k + 63) / 64);
+    bool drained = false;
+    int rc;
+    if ((rc = grow_lanes(h, native ? &Lane::io_posdw : &Lane::io_osdw, cap * rs, &drained))) return rc;
+    if (out.osd0 && (rc = grow_lanes(h, native ? &Lane::io_posd0 : &Lane::io_osd0, cap * rs, &drained))) return rc;
+    if (out.bp && (rc = grow_lanes(h, native ? &Lane::io_pbp : &Lane::io_bp, cap * rs, &drained))) return rc;
+    if ((host || native != synd_packed) && (rc = grow_lanes(h, native ? &Lane::io_psynd : &Lane::io_synd, cap * row_bytes(h->m, native), &drained))) return rc;
+    if (!host) return 0;
+    if (native != synd_packed && (rc = grow_lanes(h, synd_packed ? &Lane::io_psynd : &Lane::io_synd, cap * row_bytes(h->m, synd_packed), &drained))) return rc;
+    if ((rc = grow_lanes(h, &Lane::io_obsw, cap * ob, &drained))) return rc;
+    if (out.osd0 && (rc = grow_lanes(h, &Lane::io_obs0, cap * ob, &drained))) return rc;
+    if (out.bp && (rc = grow_lanes(h, &Lane::io_obsbp, cap * ob, &drained))) return rc;
+    if ((rc = grow_lanes(h, &Lane::io_conv, cap, &drained))) return rc;
+    return grow_lanes(h, &Lane::io_iters, sizeof(int) * cap, &drained);
+}
+
+// One decode into the lane's own row buffers with obs_kernel behind it, everything on the call's lane: `d_synd` (bytes or
+// packed words) is brought into the kernels' form first where it is in the other one; `out` is device memory.
+static int decode_obs_impl(bposd_handle* h, DecodeCall call, const void* d_synd, bool synd_packed, int64_t B, const ObsOut& out) {
+    Lane& L = *call.lane;
+    // the lane's io buffers are also read by its copy stream in the host-pointer decode path
+    if (L.copy_pending) { HIP_TRY(h, hipStreamSynchronize(L.copy_stream)); L.copy_pending = false; }
+    const bool native = native_packed(h);
+    int rc;
+    if (native && !synd_packed) {
+        if ((rc = launch_pack(h, L.stream, (const uint8_t*)d_synd, B, h->m, (unsigned long long*)L.io_psynd.p))) return rc;
+        d_synd = L.io_psynd.p;
+    } else if (!native && synd_packed) {
+        if ((rc = launch_unpack(h, L.stream, (const unsigned long long*)d_synd, B, h->m, (uint8_t*)L.io_synd.p))) return rc;
+        d_synd = L.io_synd.p;
+    }
+    call.packed = native;
+    IoPtrs dev;
+    dev.synd = (const uint8_t*)d_synd;
+    dev.osdw = (uint8_t*)(native ? L.io_posdw.p : L.io_osdw.p);
+    dev.osd0 = out.osd0 ? (uint8_t*)(native ? L.io_posd0.p : L.io_osd0.p) : nullptr;
+    dev.bp = out.bp ? (uint8_t*)(native ? L.io_pbp.p : L.io_bp.p) : nullptr;
+    dev.conv = out.conv;
+    dev.iters = out.iters;
+    if ((rc = decode_device_impl(h, call, dev, B))) return rc;
+    // (decode_device_impl has made the lane's stream wait for the OSD kernel: the rows are final)
+    const void* const rows[3] = {dev.osdw, dev.osd0, dev.bp};
+    uint64_t* const outs[3] = {out.osdw, out.osd0, out.bp};
+    CallRecord& R = *call.rec;  // (bposd_last_timing's events end in front of obs_kernel: it has a pair of its own)
+    for (auto& e : R.ev_obs)
+        if (!e) HIP_TRY(h, hipEventCreate(&e.raw));
+    HIP_TRY(h, hipEventRecord(R.ev_obs[0], L.stream));
+    if ((rc = launch_obs(h, L.stream, rows, native, B, outs))) return rc;
+    HIP_TRY(h, hipEventRecord(R.ev_obs[1], L.stream));
+    R.ran_obs = true;
+    return 0;
+}
+
+int bposd_decode_batch_observables_device(bposd_handle* h, const void* d_synd, int32_t synd_packed, int64_t B, uint64_t* d_obs_osdw,
+                                          uint64_t* d_obs_osd0, uint64_t* d_obs_bp, uint8_t* d_conv, int32_t* d_iters) {
+    if (const int rc = check_observables(h)) return rc;
+    if (const int rc = check_batch(h, B, d_synd, d_obs_osdw); rc || B == 0) return rc;
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    const ObsOut out{d_obs_osdw, d_obs_osd0, d_obs_bp, d_conv, d_iters};
+    if (const int rc = obs_reserve(h, (size_t)B, out, /*host=*/false, synd_packed != 0)) return rc;
+    return decode_obs_impl(h, take_next_lane(h), d_synd, synd_packed != 0, B, out);
+}
+
+// Syndromes [lo, lo + cnt) of a host-pointer call on the call's lane, in stream order: upload, decode + obs_kernel on
+// lane-resident rows, download of cnt x ceil(k / 64) words per requested output and of the flags and iteration counts.
+// (An asynchronous call with its copies and the conversion kernel on the lane's high-priority stream, the way
+// decode_host_async_impl places its own, was measured and is slower here: 23.4 against 22.8 ms per call of 131072 on
+// [[1922,50]], DESIGN.md 4.10 -- these copies are 24 B per shot, not 744.)
+static int obs_host_step(bposd_handle* h, const DecodeCall& call, const uint8_t* synd, bool synd_packed, int64_t lo, int64_t cnt,
+                         const ObsOut& host) {
+    Lane& L = *call.lane;
+    const size_t rsm = row_bytes(h->m, synd_packed), kw = (size_t)((h->obs_k + 63) / 64), c8 = (size_t)cnt;
+    void* const wire = synd_packed ? L.io_psynd.p : L.io_synd.p;
+    HIP_TRY(h, hipMemcpyAsync(wire, synd + (size_t)lo * rsm, c8 * rsm, hipMemcpyHostToDevice, L.stream));
+    ObsOut dev;
+    dev.osdw = (uint64_t*)L.io_obsw.p;
+    dev.osd0 = host.osd0 ? (uint64_t*)L.io_obs0.p : nullptr;
+    dev.bp = host.bp ? (uint64_t*)L.io_obsbp.p : nullptr;
+    dev.conv = (uint8_t*)L.io_conv.p;
+    dev.iters = (int32_t*)L.io_iters.p;
+    if (const int rc = decode_obs_impl(h, call, wire, synd_packed, cnt, dev)) return rc;
+    const struct { uint64_t* host; const uint64_t* dev; } outs[3] = {{host.osdw, dev.osdw}, {host.osd0, dev.osd0}, {host.bp, dev.bp}};
+    for (auto& o : outs)
+        if (o.host) HIP_TRY(h, hipMemcpyAsync(o.host + (size_t)lo * kw, o.dev, sizeof(uint64_t) * c8 * kw, hipMemcpyDeviceToHost, L.stream));
+    if (host.conv) HIP_TRY(h, hipMemcpyAsync(host.conv + lo, dev.conv, c8, hipMemcpyDeviceToHost, L.stream));
+    if (host.iters) HIP_TRY(h, hipMemcpyAsync(host.iters + lo, dev.iters, sizeof(int) * c8, hipMemcpyDeviceToHost, L.stream));
+    return 0;
+}
+
+// Host-pointer observables decode.  Synchronous: chunks of ~32768 syndromes alternate between the lanes like those of
+// bposd_decode_batch, one record per chunk.  Asynchronous: the whole call on the handle's next lane.  Neither needs the
+// compact-row machinery of decode_host_impl: obs_kernel runs after OSD has rewritten its rows on the device.
+static int decode_obs_host_impl(bposd_handle* h, const void* synd, bool synd_packed, int64_t B, const ObsOut& host, bool async) {
+    if (const int rc = check_observables(h)) return rc;
+    if (const int rc = check_batch(h, B, synd, host.osdw); rc || B == 0) return rc;
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    int rc;
+    if (async) {
+        if ((rc = obs_reserve(h, (size_t)B, host, /*host=*/true, synd_packed))) return rc;
+        const DecodeCall call = take_next_lane(h);
+        DrainOnError drain{h};
+        if ((rc = obs_host_step(h, call, (const uint8_t*)synd, synd_packed, 0, B, host))) return rc;
+        drain.armed = false;
+        return BPOSD_OK;
+    }
+    // the records and lanes are about to be reused: earlier asynchronous calls must have drained
+    if (h->async_pending) { int rcs = sync_all_lanes(h); if (rcs) return rcs; }
+    int nchunks = host_chunk_count(h, B, 32768);
+    const long long CH = (B + nchunks - 1) / nchunks;
+    nchunks = (int)((B + CH - 1) / CH);
+    if ((rc = obs_reserve(h, (size_t)CH, host, /*host=*/true, synd_packed))) return rc;
+    DrainOnError drain{h};
+    for (int c = 0; c < nchunks; ++c) {
+        const long long lo = (long long)c * CH, cnt = std::min<long long>(CH, B - lo);
+        Lane& L = h->lanes[c % h->nlanes];
+        DecodeCall call{&L, &h->rec[c], L.osd_stream};
+        call.batch_hint = B;  // kernel variants are chosen for the call, not for a chunk
+        if ((rc = obs_host_step(h, call, (const uint8_t*)synd, synd_packed, lo, cnt, host))) return rc;
+    }
+    h->nrec = nchunks;
+    drain.armed = false;
+    return sync_all_lanes(h);
+}
+
+int bposd_decode_batch_observables(bposd_handle* h, const uint8_t* synd, int64_t B, uint64_t* obs_osdw, uint64_t* obs_osd0,
+                                   uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
+    return decode_obs_host_impl(h, synd, false, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/false);
+}
+
+int bposd_decode_batch_observables_packed(bposd_handle* h, const uint64_t* synd_words, int64_t B, uint64_t* obs_osdw, uint64_t* obs_osd0,
+                                          uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
+    return decode_obs_host_impl(h, synd_words, true, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/false);
+}
+
+int bposd_decode_batch_observables_async(bposd_handle* h, const uint8_t* synd, int64_t B, uint64_t* obs_osdw, uint64_t* obs_osd0,
+                                         uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
+    return decode_obs_host_impl(h, synd, false, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/true);
+}
+
+int bposd_decode_batch_observables_packed_async(bposd_handle* h, const uint64_t* synd_words, int64_t B, uint64_t* obs_osdw,
+                                                uint64_t* obs_osd0, uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
+    return decode_obs_host_impl(h, synd_words, true, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/true);
+}
+
+int bposd_debug_obs_timing(bposd_handle* h, int32_t lane, double* obs_ms) {
+    if (!h || !obs_ms) return BPOSD_ERR_INVALID;
+    if (lane < -1 || lane >= BPOSD_LANES) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range", lane);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    CallRecord* recs = lane < 0 ? h->rec : &h->lane_rec[lane];
+    const int count = lane < 0 ? h->nrec : 1;
+    if (lane < 0) { int rcs = sync_all_lanes(h); if (rcs) return rcs; }
+    else HIP_TRY(h, hipStreamSynchronize(h->lanes[lane].stream));
+    double sum = 0.0;
+    bool any = false;
+    for (int r = 0; r < count; ++r) {
+        if (!recs[r].ran_obs) continue;
+        float ms = 0.f;
+        HIP_TRY(h, hipEventElapsedTime(&ms, recs[r].ev_obs[0], recs[r].ev_obs[1]));
+        sum += ms;
+        any = true;
+    }
+    if (!any) return fail(h, BPOSD_ERR_INVALID, "no observables call has run there");
+    *obs_ms = sum;
+    return BPOSD_OK;
 }
 
 static int record_timing(bposd_handle* h, CallRecord* recs, int count, double* bp_ms, double* osd_ms,

@@ -64,6 +64,8 @@ struct Lane {
     Event ev_alt;                    // the staging block has been read
     bool alt_busy = false;
     PinnedBuf h_tail;                // one int, page-locked, device-visible: the BP kernel of this lane's current call has entered its tail
+    // host-pointer observables calls (bposd_decode_batch_observables): the chunk's observable words, [chunk][ceil(k/64)] each
+    DevBuf io_obsw, io_obs0, io_obsbp;
 };
 
 // What bposd_last_timing reports: one record per kernel pair launched by the last call (one per chunk for a
@@ -76,6 +78,8 @@ struct CallRecord {
     bool ran_osd = false;
     bool recorded = false;  // the counters (and, when timed, the events) have been recorded at least once
     bool timed = false;     // the three events bracket the kernels of this record (not on the lean small-call path)
+    Event ev_obs[2];        // an observables call: around obs_kernel, which runs behind ev[2] (bposd_debug_obs_timing)
+    bool ran_obs = false;
 };
 
 struct bposd_handle {
@@ -142,6 +146,9 @@ struct bposd_handle {
     bool have_timing = false;
     bool async_pending = false;        // a device-pointer call may still be running on some lane
     std::string err;
+    // logical observables (bposd_set_observables): L transposed and packed, [ceil(n/64)][obs_k] words; obs_k = 0: none set
+    DevArray<unsigned long long> d_obs_table;
+    int obs_k = 0;
 };
 
 // One BP + OSD launch pair: what it needs beyond the handle's per-code state.  The entry point that makes the call fills
@@ -183,6 +190,7 @@ int set_max_lds(bposd_handle* h, const void* kernel, size_t lds);
 int cached_occupancy(bposd_handle* h, const void* kernel, int nt, size_t lds, int* out);
 int ensure(bposd_handle* h, DevBuf& b, size_t bytes);
 int ensure_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes);
+int grow_lanes(bposd_handle* h, DevBuf Lane::*member, size_t bytes, bool* drained);  // as ensure_lanes, draining the calls in flight first
 int ensure_pinned(bposd_handle* h, PinnedBuf& b, size_t bytes, unsigned flags);  // as ensure(): freed, then allocated anew
 
 // ---- table construction (host_tables.hip)
@@ -221,6 +229,10 @@ int launch_osd(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& 
 int osd_words(int n);
 int launch_osd_large(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& P, long long B, int* d_rank_out);  // launch_osd_large.hip
 int osd_large_maxspan(bool cs);
+// ---- logical observables (launch_obs.hip: obs_kernel)
+int obs_max_k();
+int observable_table(const int32_t* indptr, const int32_t* indices, int k, int n, uint64_t* table, std::string* why);
+int launch_obs(bposd_handle* h, hipStream_t st, const void* const rows[3], bool packed, long long B, uint64_t* const out[3]);
 // do the kernels this handle runs read packed syndromes / write packed rows themselves (else unpack / pack kernels surround them)?
 inline bool native_packed(const bposd_handle* h) {
     // (forced local-edge variants 16 .. 26 have no packed instantiation; the LDS and class kernels switch at run time)

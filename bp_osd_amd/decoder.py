@@ -174,6 +174,11 @@ class BpOsdDecoder:
         self.batch_osd0 = None
         self.batch_bp = None
         self.batch_llr = None
+        # logical observables: rows of the matrix given to set_observables, results of the last decode_batch_observables
+        self.num_observables = 0
+        self.batch_obs_osdw = None
+        self.batch_obs_osd0 = None
+        self.batch_obs_bp = None
 
     # ------------------------------------------------------------------ lifetime
     def __del__(self):
@@ -533,6 +538,139 @@ class BpOsdDecoder:
         else:
             rc = self._lib.bposd_pack_rows_device_lane(self._h, int(lane), d_bytes, int(B), int(n), d_words)
         _lib.check(self._lib, self._h, rc)
+
+    # ------------------------------------------------------------------ logical observables
+    @staticmethod
+    def observable_table(L, n=None):
+        """The table the observables kernel reads of a k x n matrix ``L`` over GF(2) (dense 0/1 array or scipy sparse; the
+        logical operators of a code, the observable rows of a detector error model): uint64 ``[ceil(n/64), k]``, transposed
+        and packed (``bposd_observable_table``; host only).  ValueError for k outside 1 .. 4096 or a shape that is not (k, n)."""
+        if sp.issparse(L):
+            csr = sp.csr_matrix(L).astype(np.int64)
+        else:
+            arr = np.asarray(L)
+            if arr.ndim != 2:
+                raise ValueError("The observables must be a 2-D array or scipy.sparse matrix of shape (k, n)")
+            csr = sp.csr_matrix(arr.astype(np.int64) & 1)
+        csr.sum_duplicates()
+        csr.data %= 2
+        csr.eliminate_zeros()
+        csr.sort_indices()
+        k, cols = csr.shape
+        n = cols if n is None else int(n)
+        if cols != n:
+            raise ValueError(f"The observables must have shape (k, {n}). Not {csr.shape}.")
+        indptr = np.ascontiguousarray(csr.indptr, dtype=np.int32)
+        indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
+        table = np.zeros(((max(n, 0) + 63) // 64, max(k, 0)), np.uint64)
+        lib = _lib.load()
+        _lib.check(lib, None, lib.bposd_observable_table(indptr.ctypes.data, indices.ctypes.data, k, n, table.ctypes.data))
+        return table
+
+    def set_observables(self, L):
+        """Give the decoder the k x n matrix whose products with the corrections the ``*_observables`` calls return
+        (replaces an earlier one; waits for queued work).  ``None`` or a matrix without rows removes it."""
+        if L is not None and (L.shape[0] if hasattr(L, "shape") else len(L)) > 0:
+            table = self.observable_table(L, self.n)
+            k = table.shape[1]
+            rc = self._lib.bposd_set_observables(self._h, table.ctypes.data, k)
+        else:
+            k = 0
+            rc = self._lib.bposd_set_observables(self._h, None, 0)
+        _lib.check(self._lib, self._h, rc)
+        self.num_observables = k
+
+    def _syndrome_rows(self, syndromes):
+        """(array, packed): C-contiguous uint64 words [B, ceil(m/64)] as they are, anything else as uint8 rows [B, m]."""
+        s = np.asarray(syndromes)
+        wm = (self.m + 63) // 64
+        if s.ndim == 2 and s.dtype == np.uint64 and s.shape[1] == wm:
+            return np.ascontiguousarray(s), True
+        if s.ndim != 2 or s.shape[1] != self.m:
+            raise ValueError(f"The syndromes must have shape (B, {self.m}) or be uint64 words of shape (B, {wm}). Not {s.shape}.")
+        return (np.ascontiguousarray(s) if s.dtype == np.uint8 else np.ascontiguousarray(s.astype(np.int64) & 1, dtype=np.uint8)), False
+
+    def decode_batch_observables(self, syndromes, want_osd0=False, want_bp=False, packed=False):
+        """Decode B syndromes (uint8 rows [B, m] or uint64 words [B, ceil(m/64)]) and return the observables of the OSD-W
+        corrections: uint8 ``[B, k]``, or uint64 ``[B, ceil(k/64)]`` with ``packed=True`` -- ``(L @ osdw.T).T & 1`` without
+        the corrections leaving the device.  The result is also left as ``batch_obs_osdw``, next to ``batch_obs_osd0`` /
+        ``batch_obs_bp`` (if requested), ``batch_converge`` and ``batch_iter``.  Needs :meth:`set_observables`."""
+        s, _ = self._syndrome_rows(syndromes)
+        B, k = s.shape[0], getattr(self, "num_observables", 0)
+        kw = (k + 63) // 64
+        self.batch_obs_osdw = self.batch_obs_osd0 = self.batch_obs_bp = None
+        ow = np.zeros((B, kw), np.uint64)
+        o0 = np.zeros((B, kw), np.uint64) if want_osd0 else None
+        ob = np.zeros((B, kw), np.uint64) if want_bp else None
+        conv, iters = np.zeros(B, np.uint8), np.zeros(B, np.int32)
+        self.decode_batch_observables_into(s, ow, o0, ob, conv, iters)
+        form = (lambda a: a) if packed else (lambda a: None if a is None else self.unpack_rows(a, k))
+        self.batch_converge = conv.astype(bool)
+        self.batch_iter = iters
+        self.batch_obs_osdw, self.batch_obs_osd0, self.batch_obs_bp = form(ow), form(o0), form(ob)
+        return self.batch_obs_osdw
+
+    def decode_batch_observables_into(self, syndromes, obs_osdw, obs_osd0=None, obs_bp=None, converged=None, iters=None, wait=True):
+        """Host-pointer observables decode into caller-owned C-contiguous arrays: ``uint8 [B, m]`` or ``uint64 [B, ceil(m/64)]``
+        in; ``uint64 [B, ceil(k/64)]``, ``uint8 [B]``, ``int32 [B]`` out (any output but ``obs_osdw`` may be None).
+        ``wait=False``: the call is only enqueued (``bposd_decode_batch_observables_async``; arrays from :meth:`pinned_empty`
+        make the copies asynchronous) and the lane to :meth:`synchronize` on is returned (None for an empty batch)."""
+        self._timing_override = None
+        s = syndromes
+        wm = (self.m + 63) // 64
+        words = s.dtype == np.uint64
+        if s.ndim != 2 or s.dtype not in (np.uint8, np.uint64) or s.shape[1] != (wm if words else self.m) or not s.flags.c_contiguous:
+            raise ValueError(f"syndromes must be a C-contiguous uint8 array of shape (B, {self.m}) or uint64 array of shape (B, {wm})")
+        B, k = s.shape[0], getattr(self, "num_observables", 0)
+        kw = (k + 63) // 64
+        if obs_osdw is None:
+            raise ValueError("obs_osdw is required")
+        for name, a, dt, shp in (("obs_osdw", obs_osdw, np.uint64, (B, kw)), ("obs_osd0", obs_osd0, np.uint64, (B, kw)),
+                                 ("obs_bp", obs_bp, np.uint64, (B, kw)), ("converged", converged, np.uint8, (B,)),
+                                 ("iters", iters, np.int32, (B,))):
+            if a is None:
+                continue
+            # (without a table the library refuses the call; the shapes cannot be told here then)
+            if a.dtype != dt or not a.flags.c_contiguous or (k > 0 and a.shape != shp):
+                raise ValueError(f"{name} must be a C-contiguous {np.dtype(dt).name} array of shape {shp}")
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        fn = getattr(self._lib, "bposd_decode_batch_observables" + ("_packed" if words else "") + ("" if wait else "_async"))
+        rc = fn(self._h, s.ctypes.data, B, ptr(obs_osdw), ptr(obs_osd0), ptr(obs_bp), ptr(converged), ptr(iters))
+        _lib.check(self._lib, self._h, rc)
+        if wait:
+            return obs_osdw
+        if B == 0:
+            return None  # nothing was enqueued: no lane to wait for
+        lane = self.last_lane
+        self._hold(lane, s, obs_osdw, obs_osd0, obs_bp, converged, iters)
+        return lane
+
+    def decode_observables_device(self, d_syndromes, B, d_obs_osdw, d_obs_osd0=None, d_obs_bp=None, d_converged=None, d_iters=None,
+                                  packed=False):
+        """Asynchronous observables decode on device pointers (``bposd_decode_batch_observables_device``): ``d_syndromes`` is
+        uint8 [B, m], or uint64 [B, ceil(m/64)] with ``packed=True``; the outputs are uint64 [B, ceil(k/64)].  The lane rules of
+        :meth:`decode_batch_device` apply; call :meth:`synchronize` before reading the outputs."""
+        self._timing_override = None
+        rc = self._lib.bposd_decode_batch_observables_device(self._h, d_syndromes, 1 if packed else 0, int(B), d_obs_osdw, d_obs_osd0,
+                                                             d_obs_bp, d_converged, d_iters)
+        _lib.check(self._lib, self._h, rc)
+
+    def observables_device(self, d_rows, B, d_obs, packed, lane=None):
+        """Observables of B caller-owned device rows of n bits -- uint64 [B, ceil(n/64)] with ``packed=True``, else uint8
+        [B, n] -- into device uint64 [B, ceil(k/64)] (asynchronous).  Queued on ``lane`` or, like :meth:`pack_rows_device`, on
+        the lane of the most recent device-pointer decode."""
+        lane = self.last_lane if lane is None else int(lane)
+        rc = self._lib.bposd_observables_device_lane(self._h, lane, d_rows, 1 if packed else 0, int(B), d_obs)
+        _lib.check(self._lib, self._h, rc)
+
+    def obs_kernel_ms(self, lane=None):
+        """Duration of obs_kernel in the last observables call queued on ``lane`` (HIP events; waits for that lane), or, without
+        a lane, summed over the chunks of the last synchronous host-pointer observables call.  :meth:`last_timing` and
+        :meth:`lane_timing` end in front of that kernel and do not include it."""
+        ms = C.c_double()
+        rc = self._lib.bposd_debug_obs_timing(self._h, -1 if lane is None else int(lane), C.byref(ms))
+        _lib.check(self._lib, self._h, rc)
+        return ms.value
 
     def synchronize(self, lane=None):
         """Wait for everything queued on this decoder, or (``lane``) for the calls queued on one lane only."""

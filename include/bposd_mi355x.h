@@ -226,6 +226,53 @@ int bposd_pack_rows_device(bposd_handle *h, const uint8_t *d_bytes, int64_t B, i
 int bposd_pack_rows_device_lane(bposd_handle *h, int32_t lane, const uint8_t *d_bytes, int64_t B, int32_t n,
                                 uint64_t *d_words);
 
+/*
+ * Logical observables.  What most callers ask of a correction is which logical observables it flips: observable j of a row
+ * is the parity of popcount(L_j & row) for a k x n matrix L over GF(2) (the logical operators of a code, the observable
+ * rows of a detector error model).  With a table set, the calls below decode as the calls above do and return, per shot
+ * and per output, ceil(k/64) words instead of a row of n bits: bit (j & 63) of word (j >> 6) is observable j, padding bits
+ * are zero.  The rows themselves stay on the device, in buffers the lane owns, and obs_kernel runs behind the OSD kernel
+ * on the lane's stream.  (No counterpart in the reference: its callers multiply by the logicals themselves,
+ * css_decode_sim.py:257-272.)
+ *
+ * bposd_observable_table: L as CSR (indptr[k+1], indices, columns strictly ascending within a row) -> the table the kernel
+ * reads, table[ceil(n/64)][k] (transposed and packed: bit (c & 63) of table[(c >> 6) * k + j] = L[j][c]).  Host only: no
+ * handle, no device.  BPOSD_ERR_INVALID (text: bposd_last_error(NULL)) for k outside 1 .. 4096, a column outside [0, n) or
+ * columns that do not ascend strictly; nothing is written then.
+ * bposd_set_observables: copies a table for this handle's n to the device; it replaces any earlier table once every lane
+ * has drained.  k = 0 removes it (table may be NULL then).
+ */
+int bposd_observable_table(const int32_t *indptr, const int32_t *indices, int32_t k, int32_t n, uint64_t *table);
+int bposd_set_observables(bposd_handle *h, const uint64_t *table, int32_t k);
+
+/* obs_kernel alone on caller-owned device rows of this handle's n bits -- packed != 0: uint64[B][ceil(n/64)] in the layout of
+ * bposd_decode_batch_packed (padding bits zero), else uint8[B][n] (bit 0 of every byte) -- into d_obs_words
+ * [B][ceil(k/64)], on a given lane: ordered like bposd_pack_rows_device_lane. */
+int bposd_observables_device_lane(bposd_handle *h, int32_t lane, const void *d_rows, int32_t packed, int64_t B,
+                                  uint64_t *d_obs_words);
+
+/* Device-pointer decode to observables.  d_syndromes holds uint8[B][m], or (syndromes_packed != 0) uint64[B][ceil(m/64)];
+ * either form works on every handle.  d_obs_osdw [B][ceil(k/64)] is required; d_obs_osd0, d_obs_bp, d_converged and d_iters
+ * may be NULL.  Takes the handle's next lane and is asynchronous like bposd_decode_batch_device (see "Lanes" below).
+ * Without a table every decode call of this group returns BPOSD_ERR_INVALID; B = 0 is a valid call that does nothing. */
+int bposd_decode_batch_observables_device(bposd_handle *h, const void *d_syndromes, int32_t syndromes_packed, int64_t B,
+                                          uint64_t *d_obs_osdw, uint64_t *d_obs_osd0, uint64_t *d_obs_bp,
+                                          uint8_t *d_converged, int32_t *d_iters);
+
+/* Host-pointer forms: syndromes as uint8[B*m] or (_packed) as B rows of ceil(m/64) words.  The synchronous calls run in
+ * chunks over the lanes like bposd_decode_batch; per chunk the syndromes go up and ceil(k/64) words per shot and requested
+ * output, the flags and the iteration counts come down.  The _async forms enqueue the whole call on the next lane under
+ * the rules of bposd_decode_batch_async. */
+int bposd_decode_batch_observables(bposd_handle *h, const uint8_t *syndromes, int64_t B, uint64_t *obs_osdw,
+                                   uint64_t *obs_osd0, uint64_t *obs_bp, uint8_t *converged, int32_t *iters);
+int bposd_decode_batch_observables_packed(bposd_handle *h, const uint64_t *syndrome_words, int64_t B, uint64_t *obs_osdw,
+                                          uint64_t *obs_osd0, uint64_t *obs_bp, uint8_t *converged, int32_t *iters);
+int bposd_decode_batch_observables_async(bposd_handle *h, const uint8_t *syndromes, int64_t B, uint64_t *obs_osdw,
+                                         uint64_t *obs_osd0, uint64_t *obs_bp, uint8_t *converged, int32_t *iters);
+int bposd_decode_batch_observables_packed_async(bposd_handle *h, const uint64_t *syndrome_words, int64_t B,
+                                                uint64_t *obs_osdw, uint64_t *obs_osd0, uint64_t *obs_bp,
+                                                uint8_t *converged, int32_t *iters);
+
 /* Wait for all work queued on the handle (every lane, see below). */
 int bposd_synchronize(bposd_handle *h);
 

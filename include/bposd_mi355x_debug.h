@@ -71,6 +71,11 @@ int bposd_debug_local_waves(const int32_t *csr_indptr, const int32_t *csr_indice
  * after a launch of another kernel family. */
 int bposd_debug_last_pair_key(bposd_handle *h, int32_t *pair_key);
 
+/* Diagnostics: duration of obs_kernel in the last observables call queued on `lane` (HIP events on the lane's stream; waits
+ * for that lane), or, lane = -1, summed over the chunks of the last synchronous host-pointer observables call.  obs_kernel
+ * runs behind the events of bposd_last_timing / bposd_lane_timing: their bp_ms and osd_ms do not include it. */
+int bposd_debug_obs_timing(bposd_handle *h, int32_t lane, double *obs_ms);
+
 /* Diagnostics, host only: the tables bp_class_kernel would run with for a pcm whose check and bit degrees fall inside one
  * compiled instance -- (check degrees; bit degrees) = (7; 3..4), (6; 3), (4; 2), (8; 4), (3..4; 1..2) -- and
  * BPOSD_ERR_UNSUPPORTED otherwise.  info[11]: highest check degree, lowest / highest bit degree, bit slots per thread, LDS
