@@ -64,6 +64,14 @@ EXPORTED_SYMBOLS = (
     "bposd_mc_device_bytes",
     "bposd_mc_last_error",
     "bposd_mc_destroy",
+    "bposd_dem_tables",
+    "bposd_dem_create",
+    "bposd_dem_sample",
+    "bposd_dem_run",
+    "bposd_dem_fetch",
+    "bposd_dem_device_bytes",
+    "bposd_dem_last_error",
+    "bposd_dem_destroy",
     "bposd_last_error",
     "bposd_destroy",
 )
@@ -77,6 +85,7 @@ DEBUG_SYMBOLS = (
     "bposd_debug_local_waves",
     "bposd_debug_last_pair_key",
     "bposd_debug_obs_timing",
+    "bposd_debug_dem_timing",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
     "bposd_debug_portable_math",
@@ -107,6 +116,20 @@ class BposdMcConfig(C.Structure):
         ("seed", C.c_uint64),
         ("capacity", C.c_int64),
     ]
+
+
+class BposdDemConfig(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("seed", C.c_uint64),
+        ("capacity", C.c_int64),
+    ]
+
+
+# bposd_dem_fetch(what): item -> (number, dtype, columns: "N" / "M" / "k" packed into words, "k32" = k int32 in one row, None = [B])
+DEM_ITEMS = {"faults": (0, "<u8", "N"), "detectors": (1, "<u8", "M"), "observables": (2, "<u8", "k"), "obs_bp": (3, "<u8", "k"),
+             "obs_osd0": (4, "<u8", "k"), "obs_osdw": (5, "<u8", "k"), "flags": (6, "u1", None), "converged": (7, "u1", None),
+             "iters": (8, "<i4", None), "obs_fail": (9, "<i4", "k32")}
 
 
 # bposd_mc_config.channel_update / bposd_mc_fetch(what)
@@ -245,8 +268,37 @@ def load():
     lib.bposd_mc_last_error.restype = C.c_char_p
     lib.bposd_mc_destroy.argtypes = [vp]
     lib.bposd_mc_destroy.restype = None
+    lib.bposd_dem_tables.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
+    lib.bposd_dem_tables.restype = C.c_int
+    lib.bposd_dem_create.argtypes = [C.POINTER(BposdDemConfig), vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(vp)]
+    lib.bposd_dem_create.restype = C.c_int
+    lib.bposd_dem_sample.argtypes = [vp, C.c_uint64, C.c_int64]
+    lib.bposd_dem_sample.restype = C.c_int
+    lib.bposd_dem_run.argtypes = [vp, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]
+    lib.bposd_dem_run.restype = C.c_int
+    lib.bposd_dem_fetch.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+    lib.bposd_dem_fetch.restype = C.c_int
+    lib.bposd_dem_device_bytes.argtypes = [vp]
+    lib.bposd_dem_device_bytes.restype = C.c_int64
+    lib.bposd_dem_last_error.argtypes = [vp]
+    lib.bposd_dem_last_error.restype = C.c_char_p
+    lib.bposd_dem_destroy.argtypes = [vp]
+    lib.bposd_dem_destroy.restype = None
+    lib.bposd_debug_dem_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.bposd_debug_dem_timing.restype = C.c_int
     _lib = lib
     return lib
+
+
+def check_dem(lib, dem, rc):
+    """check() for the detector-error-model engine's calls (dem None: a failed bposd_dem_create / bposd_dem_tables)."""
+    if rc == BPOSD_OK:
+        return
+    msg = lib.bposd_dem_last_error(dem)
+    msg = msg.decode() if msg else f"error {rc}"
+    if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
+        raise ValueError(msg)
+    raise RuntimeError(msg)
 
 
 def check_mc(lib, mc, rc):

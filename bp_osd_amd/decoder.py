@@ -580,6 +580,10 @@ class BpOsdDecoder:
         _lib.check(self._lib, self._h, rc)
         self.num_observables = k
 
+    def _observables_installed(self, k):
+        """An engine of the library has set this handle's table itself (``bposd_dem_create``): keep the wrapper in step."""
+        self.num_observables = int(k)
+
     def _syndrome_rows(self, syndromes):
         """(array, packed): C-contiguous uint64 words [B, ceil(m/64)] as they are, anything else as uint8 rows [B, m]."""
         s = np.asarray(syndromes)

@@ -1,0 +1,286 @@
+"""Monte-Carlo harness for detector error models (DEMs): the second engine next to ``css_decode_sim``.
+
+A model is three things: a check matrix ``H`` (``M`` detectors x ``N`` fault mechanisms), an observable matrix ``L``
+(``k x N``) and one prior per mechanism.  A shot samples the faults ``f`` (fault ``i`` fires with probability
+``priors[i]``), forms the detector row ``H f`` and the true observables ``L f``, decodes the detector row to a correction
+``c`` and succeeds when ``L c == L f``.  Nothing of it is CSS-shaped: circuit-level and phenomenological models run here,
+where ``css_decode_sim`` is the code-capacity harness of the reference.
+
+``engine="native"`` runs all of it in libbposd_mi355x.so (include/bposd_mi355x.h "Detector-error-model Monte-Carlo
+engine"): one call per batch samples, multiplies, decodes straight to observables, compares and returns
+five integers.  It needs no torch.  ``engine="numpy"`` is the same loop on the host around any decoder with a
+``decode_batch``.  Both draw from the project's counter-based Philox stream (``sim.philox_uniforms``), indexed by (shot,
+fault): they see the same shots whatever their batch sizes, and a CPU run reproduces a GPU run shot for shot.
+
+``phenomenological_dem`` builds ``(H, L, priors)`` of the repeated-measurement model of a code, so that the engine can be
+used with no circuit simulator at hand; INTEGRATION.md says how the three come out of a detector-error-model file.
+"""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import scipy.sparse as sp
+
+from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
+
+__all__ = ["dem_decode_sim", "phenomenological_dem"]
+
+_COUNTS = ("bp_converge_count", "bp_success_count", "osd0_success_count", "osdw_success_count", "trivial_count")
+
+
+def _gf2_csr(a, what):
+    """scipy CSR over GF(2) with sorted indices and no stored zeros."""
+    if sp.issparse(a):
+        m = sp.csr_matrix(a).astype(np.int64)
+    else:
+        arr = np.asarray(a)
+        if arr.ndim != 2:
+            raise ValueError(f"{what} must be a 2-D array or scipy.sparse matrix")
+        m = sp.csr_matrix(arr.astype(np.int64) & 1)
+    m.sum_duplicates()
+    m.data %= 2
+    m.eliminate_zeros()
+    m.sort_indices()
+    return m.astype(np.uint8)
+
+
+def phenomenological_dem(h, l, rounds, p_data, p_meas):
+    """``(H, L, priors)`` of the phenomenological noise model of a code with checks ``h`` (m x n) and logicals ``l`` (k x n)
+    measured for ``R = rounds`` noisy rounds and one perfect round:
+
+        H = [ I_{R+1} (x) h | D (x) I_m ],  D[t, t] = D[t+1, t] = 1  ((R+1) x R)
+        L = [ 1^T_{R+1} (x) l | 0 ]
+        priors = [p_data] * (R+1) n  ++  [p_meas] * R m
+
+    Column (t, i) of the first block is a flip of data bit i entering at round t, column (t, c) of the second a flipped
+    outcome of check c at round t; detector (t, c) is the change of check c between rounds t - 1 and t.  ``R = 0`` is
+    code capacity: ``(h, l, p_data)``.  H and L are scipy CSR (uint8), priors float64."""
+    R = int(rounds)
+    if R < 0:
+        raise ValueError("rounds must be >= 0")
+    h, l = _gf2_csr(h, "h"), _gf2_csr(l, "l")
+    m, n = h.shape
+    if l.shape[1] != n:
+        raise ValueError(f"l must have {n} columns, not {l.shape[1]}")
+    if R == 0:
+        return h, l, np.full(n, float(p_data), np.float64)
+    D = sp.lil_matrix((R + 1, R), dtype=np.uint8)
+    for t in range(R):
+        D[t, t] = D[t + 1, t] = 1
+    H = sp.hstack([sp.kron(sp.identity(R + 1, dtype=np.uint8), h), sp.kron(D, sp.identity(m, dtype=np.uint8))], format="csr")
+    L = sp.hstack([sp.kron(np.ones((1, R + 1), np.uint8), l), sp.csr_matrix((l.shape[0], R * m), dtype=np.uint8)], format="csr")
+    priors = np.concatenate([np.full((R + 1) * n, float(p_data)), np.full(R * m, float(p_meas))]).astype(np.float64)
+    return _gf2_csr(H, "H"), _gf2_csr(L, "L"), priors
+
+
+def _pack(rows):
+    """uint8 0/1 rows [B, c] -> uint64 [B, ceil(c/64)] (the C-ABI's packed form)."""
+    a = np.ascontiguousarray(rows, dtype=np.uint8)
+    by = np.packbits(a, axis=1, bitorder="little")
+    out = np.zeros((a.shape[0], 8 * ((a.shape[1] + 63) // 64)), np.uint8)
+    out[:, :by.shape[1]] = by
+    return out.view("<u8")
+
+
+class dem_decode_sim:
+    """See the module docstring.
+
+    H, L, priors : the model (scipy sparse or dense 0/1 matrices of shapes (M, N) and (k, N); N floats in [0, 1])
+    batch_size : shots per batch (default 4096)
+    engine : "native" (everything in the library; builds ``BpOsdDecoder(H, channel_probs=priors, **decoder_kwargs)``) or
+        "numpy" (host loop around ``decoder_factory(H, channel_probs=priors, **decoder_kwargs).decode_batch``)
+    seed : key of the Philox stream (used as given: 0 is a seed like any other)
+    target_runs : shots to run
+    decoder_factory : engine="numpy" only; default the MI355X ``BpOsdDecoder``.  ``decode_batch(detectors)`` returns either a
+        mapping with "osdw", "osd0", "bp", "converged", "iters", or the osdw rows with the rest left as ``batch_osd0``,
+        ``batch_bp``, ``batch_converge``, ``batch_iter``
+    run_sim : run at once (default) or wait for :meth:`run_decode_sim`
+
+    Results: ``run_count``, ``bp_converge_count``, ``bp_success_count`` (converged and observables right),
+    ``osd0_success_count``, ``osdw_success_count``, ``trivial_count`` (no detector fired), ``*_logical_error_rate`` with
+    ``*_logical_error_rate_eb = sqrt(L (1 - L) / runs)`` as css_decode_sim has them, ``osdw_observable_error_rates``
+    (float [k]), :meth:`output_dict` and :meth:`last_batch`."""
+
+    def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=100, decoder_factory=None, run_sim=True,
+                 **decoder_kwargs):
+        if engine not in ("native", "numpy"):
+            raise ValueError("engine must be 'native' or 'numpy'")
+        if engine == "native" and decoder_factory is not None:
+            raise ValueError("engine='native' drives the MI355X decoder through device pointers; decoder_factory must be None")
+        self._engine = engine
+        self._H, self._L = _gf2_csr(H, "H"), _gf2_csr(L, "L")
+        self.M, self.N = self._H.shape
+        self.K = self._L.shape[0]
+        if self._L.shape[1] != self.N:
+            raise ValueError(f"L must have shape (k, {self.N}), not {self._L.shape}")
+        if not 1 <= self.K <= 4096:
+            raise ValueError(f"the number of observables k = {self.K} is outside 1 .. 4096")
+        p = np.ascontiguousarray(priors, dtype=np.float64)
+        if p.shape != (self.N,):
+            raise ValueError(f"priors must have length {self.N}, not {p.shape}")
+        bad = np.flatnonzero(~((p >= 0) & (p <= 1)))
+        if bad.size:
+            raise ValueError(f"the prior of fault {int(bad[0])} ({p[bad[0]]}) is not a probability")
+        self._priors = p
+        self._batch_size = int(batch_size)
+        if self._batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.target_runs = int(target_runs)
+        self.engine = engine
+        self.run_count = 0
+        for key in _COUNTS:
+            setattr(self, key, 0)
+        for key in ("bp", "osd0", "osdw"):
+            setattr(self, f"{key}_logical_error_rate", 0.0)
+            setattr(self, f"{key}_logical_error_rate_eb", 0.0)
+        self._obs_fail = np.zeros(self.K, np.int64)
+        self.osdw_observable_error_rates = np.zeros(self.K, np.float64)
+        self._last = None
+        self._dem = None
+        if engine == "native":
+            from .decoder import BpOsdDecoder
+
+            self.decoder = BpOsdDecoder(self._H, channel_probs=p, **decoder_kwargs)
+            self._native_setup()
+        else:
+            self.decoder = (decoder_factory or _default_decoder_factory)(self._H, channel_probs=p, **decoder_kwargs)
+        if run_sim:
+            self.run_decode_sim()
+
+    # ------------------------------------------------------------------ the library's engine
+    def _native_setup(self):
+        import ctypes as C
+
+        from . import _lib
+
+        lib = self._lib = _lib.load()
+        cfg = _lib.BposdDemConfig(device=int(self.decoder.device), seed=self.seed, capacity=self._batch_size)
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        keep = [i32(self._H.indptr), i32(self._H.indices), i32(self._L.indptr), i32(self._L.indices)]
+        dem = C.c_void_p()
+        rc = lib.bposd_dem_create(C.byref(cfg), self.decoder._h, keep[0].ctypes.data, keep[1].ctypes.data, self.M, keep[2].ctypes.data,
+                                  keep[3].ctypes.data, self.K, self.N, self._priors.ctypes.data, C.byref(dem))
+        if rc != 0:
+            _lib.check_dem(lib, None, rc)
+        self._dem = dem
+        self.decoder._observables_installed(self.K)  # bposd_dem_create has set the decoder's table
+        self._last_B = 0
+
+    def _run_batch_native(self, B):
+        import ctypes as C
+
+        from . import _lib
+
+        c = (C.c_int64 * 5)()
+        _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_run(self._dem, int(self.run_count), int(B), c))
+        self._last_B = B
+        self._accumulate(B, [int(v) for v in c], self.last_batch("obs_fail"))
+
+    def device_bytes(self):
+        """engine="native": bytes of device memory the engine holds for its batches (the decoder's workspaces are its own)."""
+        if self._dem is None:
+            raise RuntimeError("device_bytes needs engine='native'")
+        return int(self._lib.bposd_dem_device_bytes(self._dem))
+
+    def kernel_ms(self):
+        """engine="native": (dem_sample_kernel, dem_score_kernel) durations of the last batch in ms (HIP events)."""
+        import ctypes as C
+
+        from . import _lib
+
+        if self._dem is None:
+            raise RuntimeError("kernel_ms needs engine='native'")
+        a, b = C.c_double(), C.c_double()
+        _lib.check_dem(self._lib, self._dem, self._lib.bposd_debug_dem_timing(self._dem, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def __del__(self):
+        dem, self._dem = getattr(self, "_dem", None), None
+        if dem is not None:  # before the decoder it points to goes
+            self._lib.bposd_dem_destroy(dem)
+
+    # ------------------------------------------------------------------ the host loop
+    def _run_batch_numpy(self, B):
+        faults = (philox_uniforms(self.seed, self.run_count, B, self.N) < self._priors).astype(np.uint8)
+        detectors = _mod2_mul(self._H, faults)
+        truth = _mod2_mul(self._L, faults)
+        r = self.decoder.decode_batch(detectors)
+        if isinstance(r, dict):
+            rows = {"osdw": r["osdw"], "osd0": r["osd0"], "bp": r["bp"]}
+            conv, iters = np.asarray(r["converged"]), np.asarray(r["iters"])
+        else:
+            d = self.decoder
+            rows = {"osdw": r, "osd0": d.batch_osd0, "bp": d.batch_bp}
+            conv, iters = np.asarray(d.batch_converge), np.asarray(d.batch_iter)
+        conv = conv.astype(bool)
+        obs = {key: _mod2_mul(self._L, np.asarray(v, dtype=np.uint8) & 1) for key, v in rows.items()}
+        wrong = {key: (v != truth).any(axis=1) for key, v in obs.items()}
+        quiet = ~detectors.any(axis=1)
+        flags = (wrong["bp"].astype(np.uint8) | (wrong["osd0"].astype(np.uint8) << 1) | (wrong["osdw"].astype(np.uint8) << 2)
+                 | (quiet.astype(np.uint8) << 3))
+        obs_fail = (obs["osdw"] != truth).sum(axis=0).astype(np.int32)
+        self._last = {"faults": _pack(faults), "detectors": _pack(detectors), "observables": _pack(truth), "obs_bp": _pack(obs["bp"]),
+                      "obs_osd0": _pack(obs["osd0"]), "obs_osdw": _pack(obs["osdw"]), "flags": flags, "converged": conv.astype(np.uint8),
+                      "iters": iters.astype(np.int32), "obs_fail": obs_fail}
+        counters = [int(conv.sum()), int((conv & ~wrong["bp"]).sum()), int((~wrong["osd0"]).sum()), int((~wrong["osdw"]).sum()),
+                    int(quiet.sum())]
+        self._accumulate(B, counters, obs_fail)
+
+    # ------------------------------------------------------------------ common
+    def _accumulate(self, B, counters, obs_fail):
+        self.run_count += B
+        for key, v in zip(_COUNTS, counters):
+            setattr(self, key, getattr(self, key) + v)
+        self._obs_fail += np.asarray(obs_fail, dtype=np.int64)
+        n = self.run_count
+        for key in ("osdw", "osd0", "bp"):  # css_decode_sim's formulas
+            ler = 1 - getattr(self, f"{key}_success_count") / n
+            setattr(self, f"{key}_logical_error_rate", ler)
+            setattr(self, f"{key}_logical_error_rate_eb", float(np.sqrt((1 - ler) * ler / n)))
+        self.osdw_observable_error_rates = self._obs_fail / n
+
+    def run_decode_sim(self):
+        while self.run_count < self.target_runs:
+            B = min(self._batch_size, self.target_runs - self.run_count)
+            if self._engine == "native":
+                self._run_batch_native(B)
+            else:
+                self._run_batch_numpy(B)
+        return self.output_dict()
+
+    def last_batch(self, what):
+        """One array of the last batch: "faults", "detectors", "observables" (the true ones), "obs_bp", "obs_osd0", "obs_osdw"
+        (bit-packed rows, uint64 [B, ceil(./64)]: ``BpOsdDecoder.unpack_rows`` expands them), "flags" (uint8 [B]: bit 0 bp
+        wrong, 1 osd0 wrong, 2 osdw wrong, 3 no detector fired), "converged" (uint8 [B]), "iters" (int32 [B]) or "obs_fail"
+        (int32 [k]: osdw failures per observable in that batch).  engine="native" copies it from the device."""
+        from . import _lib
+
+        if what not in _lib.DEM_ITEMS:
+            raise ValueError(f"what must be one of {sorted(_lib.DEM_ITEMS)}")
+        if self._engine == "numpy":
+            if self._last is None:
+                raise RuntimeError("last_batch needs a batch that has run")
+            return self._last[what]
+        if not self._last_B:
+            raise RuntimeError("last_batch needs a batch that has run")
+        item, dtype, cols = _lib.DEM_ITEMS[what]
+        B = self._last_B
+        width = {"N": self.N, "M": self.M, "k": self.K}
+        shape = (B,) if cols is None else (self.K,) if cols == "k32" else (B, (width[cols] + 63) // 64)
+        out = np.empty(shape, dtype=np.dtype(dtype))
+        _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_fetch(self._dem, item, out.ctypes.data, out.nbytes))
+        return out
+
+    def output_dict(self):
+        """The counters and rates as a JSON string (as css_decode_sim.output_dict returns one)."""
+        out = {"N": self.N, "M": self.M, "K": self.K, "seed": self.seed, "engine": self.engine, "target_runs": self.target_runs,
+               "run_count": self.run_count}
+        for key in _COUNTS:
+            out[key] = int(getattr(self, key))
+        for key in ("bp", "osd0", "osdw"):
+            out[f"{key}_logical_error_rate"] = float(getattr(self, f"{key}_logical_error_rate"))
+            out[f"{key}_logical_error_rate_eb"] = float(getattr(self, f"{key}_logical_error_rate_eb"))
+        out["osdw_observable_error_rates"] = [float(v) for v in self.osdw_observable_error_rates]
+        return json.dumps(out, sort_keys=True, indent=4)

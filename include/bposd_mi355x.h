@@ -415,6 +415,93 @@ const char *bposd_mc_last_error(bposd_mc *mc);
 
 void bposd_mc_destroy(bposd_mc *mc);
 
+/*
+ * Detector-error-model Monte-Carlo engine: the second engine, for circuit-level and phenomenological models.  A model is
+ * a check matrix H (M detectors x N fault mechanisms), an observable matrix L (k x N) and one prior per mechanism; nothing
+ * of it is CSS-shaped.  One bposd_dem_run is one batch of shots: sample the faults f -> detector row H . f and true
+ * observable row L . f -> one decode straight to observables (bposd_decode_batch_observables_device) -> compare -> five
+ * integers.  The engine owns every device buffer of a batch and needs no torch; bp_osd_amd/dem.py drives it as
+ * dem_decode_sim(engine="native").  (No counterpart in the reference: its harness is the code-capacity CSS loop above.)
+ *
+ * Random stream: the one defined above ("Random stream"), with the fault index in the place of the qubit index.  Fault i
+ * of global shot s fires iff u(s, i) < priors[i]: counter (s lo, s hi, i >> 1, 0), key = seed, (o0, o1) serve even i and
+ * (o2, o3) odd i, u = uniform53; the compare is in fp64 against priors[i] as given (0 never fires, 1 always does).
+ * Host restatement: sim.philox_uniforms(seed, first_shot, B, N) < priors.  Shot s of a run is row s - first_shot.
+ *
+ * The sampler scatters: a fault that fired walks its column of H stacked on L and flips one bit per entry of the shot's
+ * row in LDS (XOR commutes: the row is bit-exact whatever the arrival order).  bposd_dem_tables builds that CSC.
+ */
+typedef struct bposd_dem bposd_dem;
+
+typedef struct {
+    int32_t device;    /* HIP device ordinal; the decoder must live there                                     */
+    uint64_t seed;     /* key of the random stream                                                            */
+    int64_t capacity;  /* largest batch a run may ask for: every per-batch buffer is allocated for it         */
+} bposd_dem_config;
+
+/* What bposd_dem_fetch copies out of the last batch (B rows each, but for the last item). */
+enum {
+    BPOSD_DEM_FAULTS = 0,      /* uint64[B][ceil(N/64)]: packed rows, the layout of bposd_decode_batch_packed         */
+    BPOSD_DEM_DETECTORS = 1,   /* uint64[B][ceil(M/64)]: H . faults                                                   */
+    BPOSD_DEM_OBSERVABLES = 2, /* uint64[B][ceil(k/64)]: L . faults, the true observables                             */
+    BPOSD_DEM_OBS_BP = 3,      /* uint64[B][ceil(k/64)]: L . correction of the bp / osd0 / osdw output, as decoded    */
+    BPOSD_DEM_OBS_OSD0 = 4,
+    BPOSD_DEM_OBS_OSDW = 5,
+    BPOSD_DEM_FLAGS = 6,       /* uint8[B]: bit 0 bp wrong, bit 1 osd0 wrong, bit 2 osdw wrong, bit 3 no detector fired */
+    BPOSD_DEM_CONVERGED = 7,   /* uint8[B]                                                                            */
+    BPOSD_DEM_ITERS = 8,       /* int32[B]                                                                            */
+    BPOSD_DEM_OBS_FAIL = 9     /* int32[k]: osdw failures per observable in this batch                                */
+};
+
+/*
+ * CSR of H (h_indptr[M+1]) and of L (l_indptr[k+1]) -> the stacked CSC the sampler reads: col_ptr[N+1], and col_bits[nnz(H)
+ * + nnz(L)] holding, per fault and ascending, the bits it flips -- detector r is bit r, observable j is bit
+ * 64 * ceil(M/64) + j, so that the detector words and the observable words of a row are contiguous ranges of one array.
+ * Host only: no handle, no device.  BPOSD_ERR_INVALID (text: bposd_last_error(NULL)) for a column outside [0, N), columns
+ * that do not ascend strictly within a row, k outside 1 .. 4096, M < 1 or N < 1; nothing is written then.  Columns without
+ * an entry are legal, and so are columns that touch observables only.
+ */
+int bposd_dem_tables(const int32_t *h_indptr, const int32_t *h_indices, int32_t M, const int32_t *l_indptr,
+                     const int32_t *l_indices, int32_t k, int32_t N, int32_t *col_ptr, int32_t *col_bits);
+
+/*
+ * priors[N]: each in [0, 1], a NaN is refused (the message names the fault).  With a decoder: dec's (m, n) must be (M, N)
+ * and it must live on cfg->device; THE ENGINE SETS THE DECODER'S OBSERVABLE TABLE -- it builds the table of L and installs
+ * it with bposd_set_observables(dec, ...), so that the L that scores and the L the decoder multiplies by cannot differ
+ * (a run after someone replaced that table by one of another k is refused).  The decoder's channel stays whatever its
+ * owner gave it; the Python layer passes the priors to both.  dec == NULL makes a sample-only engine, on which
+ * bposd_dem_run returns BPOSD_ERR_INVALID.  Everything is copied; the decoder stays the caller's and must outlive the
+ * engine; the table is installed last, so a create that fails leaves the decoder as it was.  BPOSD_ERR_UNSUPPORTED for a model whose row of M + k bits does not fit the sampler's LDS (two rows in 64 KB).
+ */
+int bposd_dem_create(const bposd_dem_config *cfg, bposd_handle *dec, const int32_t *h_indptr, const int32_t *h_indices,
+                     int32_t M, const int32_t *l_indptr, const int32_t *l_indices, int32_t k, int32_t N,
+                     const double *priors, bposd_dem **out);
+
+/* The sampler alone: shots first_shot .. first_shot + B - 1 (1 <= B <= capacity); waits for the kernel.  Items 0-2 of
+ * bposd_dem_fetch hold the batch afterwards. */
+int bposd_dem_sample(bposd_dem *dem, uint64_t first_shot, int64_t B);
+
+/*
+ * One batch: sample on the engine's stream, decode on the decoder's next lane (ordered by events), score on the engine's
+ * stream.  Returns with the counters on the host -- the one host wait of a batch:
+ *   [0] bp converged   [1] bp success (converged AND observables equal the true ones)   [2] osd0 success
+ *   [3] osdw success   [4] shots in which no detector fired
+ * B outside [1, capacity] is BPOSD_ERR_INVALID.  All ten items of bposd_dem_fetch hold the batch afterwards.
+ */
+int bposd_dem_run(bposd_dem *dem, uint64_t first_shot, int64_t B, int64_t counters[5]);
+
+/* Copy one item (BPOSD_DEM_FAULTS ...) of the last batch to host memory; bytes must be that item's size for the last B.
+ * After bposd_dem_sample only items 0-2 are there.  BPOSD_DEM_OBS_FAIL came down with the counters: no device call. */
+int bposd_dem_fetch(bposd_dem *dem, int32_t what, void *host_dst, size_t bytes);
+
+/* Device memory the engine holds (the sum of its own allocations; the decoder's workspaces are its own). */
+int64_t bposd_dem_device_bytes(bposd_dem *dem);
+
+/* Message for the last error on this engine (dem == NULL: the last bposd_dem_create / bposd_dem_tables failure). */
+const char *bposd_dem_last_error(bposd_dem *dem);
+
+void bposd_dem_destroy(bposd_dem *dem);
+
 /* Message for the last error on this handle (h == NULL: last create() failure). */
 const char *bposd_last_error(bposd_handle *h);
 

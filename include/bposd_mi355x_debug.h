@@ -76,6 +76,10 @@ int bposd_debug_last_pair_key(bposd_handle *h, int32_t *pair_key);
  * runs behind the events of bposd_last_timing / bposd_lane_timing: their bp_ms and osd_ms do not include it. */
 int bposd_debug_obs_timing(bposd_handle *h, int32_t lane, double *obs_ms);
 
+/* Diagnostics: durations of dem_sample_kernel and dem_score_kernel in the engine's last batch (HIP events on the engine's
+ * stream; the batch has been waited for).  score_ms is 0 after bposd_dem_sample.  Either pointer may be NULL. */
+int bposd_debug_dem_timing(bposd_dem *dem, double *sample_ms, double *score_ms);
+
 /* Diagnostics, host only: the tables bp_class_kernel would run with for a pcm whose check and bit degrees fall inside one
  * compiled instance -- (check degrees; bit degrees) = (7; 3..4), (6; 3), (4; 2), (8; 4), (3..4; 1..2) -- and
  * BPOSD_ERR_UNSUPPORTED otherwise.  info[11]: highest check degree, lowest / highest bit degree, bit slots per thread, LDS

@@ -1,0 +1,149 @@
+"""Rates of the detector-error-model Monte-Carlo engine (``dem_decode_sim(engine="native")``, bposd_dem_*) on one MI355X.
+
+``--model h1922``: ``phenomenological_dem(h1922.hz, lz, R=0, 0.05, -)`` -- the headline matrix under the headline decoder
+(min-sum, osd_cs 7), so the decode underneath is the known observables call.  ``--model hgp400r3``: the R = 3 model of
+hgp(mkmn_16_4_6) (768 x 2176, k = 16, p = q = 0.02), which runs on the HBM-resident kernels.
+
+Per model, ``--rounds`` rounds, alternating, of ``--steps`` calls each:
+  (a) ``bposd_dem_run`` (the C call alone) at ``--batch`` shots: runs/s, the two kernels' times from the HIP events the library records around
+      them, ``bposd_dem_device_bytes``;
+  (b) the bare ``decode_observables_device`` call on one of those batches' detector rows (device-resident, one call at a
+      time, as the engine issues it): the engine's overhead over it is (a) - (b), with its spread over the rounds;
+  (c) once, the loop the engine replaces on ``--host-shots`` of the same shots: host Philox draw, ``_mod2_mul``,
+      ``decode_batch_observables``, numpy compare -- and its counters against the engine's on those shots.
+Prints one line per figure; ``--out FILE`` appends them there (profiles/dem_rates.txt)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def model(name):
+    from bp_osd_amd import phenomenological_dem
+    from bp_osd_amd.codes import h1922, hgp
+
+    if name == "h1922":
+        code = h1922(compute_logicals=True)
+        kw = dict(max_iter=0, bp_method="ms", ms_scaling_factor=0, osd_method="osd_cs", osd_order=7)
+        return phenomenological_dem(code.hz, code.lz, 0, 0.05, 0.0), kw, "[[1922,50]] hz, R = 0, p = 0.05; min-sum, osd_cs 7"
+    seed = np.loadtxt(os.path.join(ROOT, "tests", "golden", "mkmn_16_4_6.txt")).astype(np.uint8)
+    code = hgp(seed)
+    kw = dict(max_iter=0, bp_method="ms", ms_scaling_factor=0, osd_method="osd_cs", osd_order=7)
+    return phenomenological_dem(code.hz, code.lz, 3, 0.02, 0.02), kw, "hgp(mkmn_16_4_6) hz, R = 3, p = q = 0.02; min-sum, osd_cs 7"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("h1922", "hgp400r3"), default="h1922")
+    ap.add_argument("--batch", type=int, default=131072)
+    ap.add_argument("--steps", type=int, default=4)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--host-shots", type=int, default=16384)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import torch  # (plumbing of (b) only: a device buffer for the bare decode call)
+    torch.cuda.init()  # torch's HIP runtime before libbposd_mi355x.so pulls in the system one
+    from bp_osd_amd import BpOsdDecoder, dem_decode_sim
+    from bp_osd_amd.sim import _mod2_mul, philox_uniforms
+
+    (H, L, priors), kw, what = model(a.model)
+    M, N = H.shape
+    k = L.shape[0]
+    B, seed = a.batch, 5
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"# tools/dem_probe.py on one MI355X: {what}; H {M} x {N}, k = {k}, B = {B}; {a.rounds} rounds of {a.steps} calls, alternating")
+    sim = dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=0, run_sim=False, **kw)
+    dec = sim.decoder
+    for _ in range(2):  # warm-up: workspaces, the kernels' first launch
+        sim._run_batch_native(B)
+    say(f"bposd_dem_device_bytes: {sim.device_bytes():,} B for capacity {B} = {sim.device_bytes() / B:.1f} B per shot "
+        f"(faults {8 * ((N + 63) // 64)}, detectors {8 * ((M + 63) // 64)}, observables 4 x {8 * ((k + 63) // 64)}, flags + converged + iters 6)")
+    det = sim.last_batch("detectors")
+    kw_ = (k + 63) // 64
+    d_det = torch.from_numpy(det.view(np.int64)).cuda()
+    d_obs = [torch.empty((B, kw_), dtype=torch.int64, device="cuda") for _ in range(3)]
+    d_conv = torch.empty(B, dtype=torch.uint8, device="cuda")
+    d_it = torch.empty(B, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def bare():
+        dec.decode_observables_device(d_det.data_ptr(), B, d_obs[0].data_ptr(), d_obs[1].data_ptr(), d_obs[2].data_ptr(), d_conv.data_ptr(),
+                                      d_it.data_ptr(), packed=True)
+        dec.synchronize()
+
+    bare()
+    same = (d_obs[0].cpu().numpy().view(np.uint64) == sim.last_batch("obs_osdw")).all()
+    say(f"the bare call on the last batch's detector rows returns the engine's osdw observables: {same}")
+
+    import ctypes as C
+
+    t_run, t_bare, k_sample, k_score = [], [], [], []
+    c5, shot = (C.c_int64 * 5)(), sim.run_count
+    for _ in range(a.rounds):
+        dt = 0.0
+        for _ in range(a.steps):  # the C call alone is timed: the event reads below are the probe's, not the engine's
+            t0 = time.perf_counter()
+            rc = sim._lib.bposd_dem_run(sim._dem, shot, B, c5)
+            dt += time.perf_counter() - t0
+            assert rc == 0, sim._lib.bposd_dem_last_error(sim._dem)
+            sim._last_B = B
+            sim._accumulate(B, [int(v) for v in c5], sim.last_batch("obs_fail"))
+            shot += B
+            ms = sim.kernel_ms()
+            k_sample.append(ms[0])
+            k_score.append(ms[1])
+        t_run.append(dt / a.steps * 1e3)
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            bare()
+        t_bare.append((time.perf_counter() - t0) / a.steps * 1e3)
+    fmt = lambda v: " / ".join(f"{x:.2f}" for x in v)
+    over = [r - b for r, b in zip(t_run, t_bare)]
+    say(f"bposd_dem_run, ms per batch: {fmt(t_run)} ({B / np.mean(t_run) * 1e3:,.0f} runs/s)")
+    say(f"bare decode_observables_device on device-resident detectors, ms per call: {fmt(t_bare)} ({B / np.mean(t_bare) * 1e3:,.0f} syndromes/s)")
+    say(f"engine minus bare call, per round: {fmt(over)} ms; mean {np.mean(over):+.3f} ms, spread {max(over) - min(over):.3f} ms "
+        f"({100 * np.mean(over) / np.mean(t_bare):+.1f} % of the bare call)")
+    say(f"dem_sample_kernel, HIP events: mean {np.mean(k_sample):.3f} ms (min {min(k_sample):.3f}, max {max(k_sample):.3f}, {len(k_sample)} batches); "
+        f"dem_score_kernel: mean {np.mean(k_score):.3f} ms (min {min(k_score):.3f}, max {max(k_score):.3f})")
+    say(f"after {sim.run_count} shots: osdw logical error rate {sim.osdw_logical_error_rate:.5f} +- {sim.osdw_logical_error_rate_eb:.5f}, "
+        f"bp converged {sim.bp_converge_count / sim.run_count:.4f}, no detector fired {sim.trivial_count / sim.run_count:.5f}")
+
+    # ---- (c) the loop the engine replaces, on shots [0, host_shots) of the same stream
+    Bh = min(a.host_shots, B)
+    ref = dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=Bh, decoder_factory=None, **kw)
+    want = [ref.bp_converge_count, ref.bp_success_count, ref.osd0_success_count, ref.osdw_success_count, ref.trivial_count]
+    host = BpOsdDecoder(H, channel_probs=priors, **kw)
+    host.set_observables(L)
+    host.decode_batch_observables(np.zeros((64, M), np.uint8), want_osd0=True, want_bp=True)  # warm-up
+    t0 = time.perf_counter()
+    faults = (philox_uniforms(seed, 0, Bh, N) < priors).astype(np.uint8)
+    t1 = time.perf_counter()
+    detectors, truth = _mod2_mul(H, faults), _mod2_mul(L, faults)
+    t2 = time.perf_counter()
+    ow = host.decode_batch_observables(detectors, want_osd0=True, want_bp=True)
+    t3 = time.perf_counter()
+    wrong = [(o != truth).any(axis=1) for o in (host.batch_obs_bp, host.batch_obs_osd0, ow)]
+    conv = host.batch_converge
+    got = [int(conv.sum()), int((conv & ~wrong[0]).sum()), int((~wrong[1]).sum()), int((~wrong[2]).sum()), int((~detectors.any(axis=1)).sum())]
+    t4 = time.perf_counter()
+    say(f"host loop on {Bh} of the same shots: {Bh / (t4 - t0):,.0f} runs/s (Philox draw {1e3 * (t1 - t0):.0f} ms, _mod2_mul {1e3 * (t2 - t1):.0f} ms, "
+        f"decode_batch_observables {1e3 * (t3 - t2):.0f} ms, numpy compare {1e3 * (t4 - t3):.0f} ms); its five counters equal the engine's: {got == want} {got}")
+    say(f"engine / host loop: {B / np.mean(t_run) * 1e3 / (Bh / (t4 - t0)):.0f} x")
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n\n")
+
+
+if __name__ == "__main__":
+    main()
