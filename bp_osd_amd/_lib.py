@@ -72,6 +72,15 @@ EXPORTED_SYMBOLS = (
     "bposd_dem_device_bytes",
     "bposd_dem_last_error",
     "bposd_dem_destroy",
+    "bposd_window_create",
+    "bposd_window_decode_device",
+    "bposd_window_synchronize",
+    "bposd_window_decode",
+    "bposd_window_run",
+    "bposd_window_fetch",
+    "bposd_window_device_bytes",
+    "bposd_window_last_error",
+    "bposd_window_destroy",
     "bposd_last_error",
     "bposd_destroy",
 )
@@ -86,6 +95,8 @@ DEBUG_SYMBOLS = (
     "bposd_debug_last_pair_key",
     "bposd_debug_obs_timing",
     "bposd_debug_dem_timing",
+    "bposd_debug_window_step",
+    "bposd_debug_window_timing",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
     "bposd_debug_portable_math",
@@ -124,6 +135,51 @@ class BposdDemConfig(C.Structure):
         ("seed", C.c_uint64),
         ("capacity", C.c_int64),
     ]
+
+
+class BposdWindowConfig(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("capacity", C.c_int64),
+    ]
+
+
+class BposdWindowStep(C.Structure):
+    """bposd_window_step_args of include/bposd_mi355x_debug.h (every pointer a host pointer)."""
+    _fields_ = [
+        ("device", C.c_int32),
+        ("M", C.c_int32),
+        ("N", C.c_int32),
+        ("k", C.c_int32),
+        ("h_indptr", C.c_void_p),
+        ("h_indices", C.c_void_p),
+        ("l_indptr", C.c_void_p),
+        ("l_indices", C.c_void_p),
+        ("B", C.c_int64),
+        ("n_commit", C.c_int32),
+        ("commit_pos", C.c_void_p),
+        ("commit_fault", C.c_void_p),
+        ("decoded_cols", C.c_int32),
+        ("decoded_packed", C.c_int32),
+        ("decoded", C.c_void_p),
+        ("prev_converged", C.c_void_p),
+        ("prev_iters", C.c_void_p),
+        ("n_gather", C.c_int32),
+        ("gather_det", C.c_void_p),
+        ("syndrome_packed", C.c_int32),
+        ("syndrome", C.c_void_p),
+        ("running", C.c_void_p),
+        ("observables", C.c_void_p),
+        ("correction", C.c_void_p),
+        ("conv_all", C.c_void_p),
+        ("iters", C.c_void_p),
+        ("word_range", C.c_int32 * 2),
+    ]
+
+
+# bposd_window_fetch(what): item -> (number, dtype, columns) in the notation of DEM_ITEMS
+WINDOW_ITEMS = {"obs_osdw": (0, "<u8", "k"), "observables": (1, "<u8", "k"), "correction": (2, "<u8", "N"), "residual": (3, "<u8", "M"),
+                "flags": (4, "u1", None), "converged": (5, "u1", None), "iters": (6, "<i4", None), "obs_fail": (7, "<i4", "k32")}
 
 
 # bposd_dem_fetch(what): item -> (number, dtype, columns: "N" / "M" / "k" packed into words, "k32" = k int32 in one row, None = [B])
@@ -286,6 +342,29 @@ def load():
     lib.bposd_dem_destroy.restype = None
     lib.bposd_debug_dem_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.bposd_debug_dem_timing.restype = C.c_int
+    lib.bposd_window_create.argtypes = [C.POINTER(BposdWindowConfig), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32,
+                                        C.POINTER(vp), vp, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.bposd_window_create.restype = C.c_int
+    lib.bposd_window_decode_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.bposd_window_decode_device.restype = C.c_int
+    lib.bposd_window_synchronize.argtypes = [vp]
+    lib.bposd_window_synchronize.restype = C.c_int
+    lib.bposd_window_decode.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.bposd_window_decode.restype = C.c_int
+    lib.bposd_window_run.argtypes = [vp, vp, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]
+    lib.bposd_window_run.restype = C.c_int
+    lib.bposd_window_fetch.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+    lib.bposd_window_fetch.restype = C.c_int
+    lib.bposd_window_device_bytes.argtypes = [vp]
+    lib.bposd_window_device_bytes.restype = C.c_int64
+    lib.bposd_window_last_error.argtypes = [vp]
+    lib.bposd_window_last_error.restype = C.c_char_p
+    lib.bposd_window_destroy.argtypes = [vp]
+    lib.bposd_window_destroy.restype = None
+    lib.bposd_debug_window_step.argtypes = [C.POINTER(BposdWindowStep)]
+    lib.bposd_debug_window_step.restype = C.c_int
+    lib.bposd_debug_window_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.bposd_debug_window_timing.restype = C.c_int
     _lib = lib
     return lib
 
@@ -295,6 +374,17 @@ def check_dem(lib, dem, rc):
     if rc == BPOSD_OK:
         return
     msg = lib.bposd_dem_last_error(dem)
+    msg = msg.decode() if msg else f"error {rc}"
+    if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
+        raise ValueError(msg)
+    raise RuntimeError(msg)
+
+
+def check_window(lib, win, rc):
+    """check() for the sliding-window engine's calls (win None: a failed bposd_window_create / bposd_debug_window_step)."""
+    if rc == BPOSD_OK:
+        return
+    msg = lib.bposd_window_last_error(win)
     msg = msg.decode() if msg else f"error {rc}"
     if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
         raise ValueError(msg)

@@ -1,0 +1,36 @@
+// dem_engine.h -- the state of a detector-error-model engine (bposd_dem of include/bposd_mi355x.h), shared by launch_dem.hip,
+// which owns it, and launch_window.hip, whose Monte-Carlo run samples on a sample-only engine and reads its rows.
+#pragma once
+#include "internal.h"
+
+struct bposd_dem {
+    bposd_dem_config cfg{};
+    bposd_handle* dec = nullptr;  // NULL: a sample-only engine
+    int N = 0, M = 0, k = 0, fw = 0, dw = 0, ow = 0;
+    long long capacity = 0;
+    long long sampled_B = 0, scored_B = 0;  // rows of the last batch that items 0-2 / items 3-9 hold
+    int num_cu = 0;
+    size_t device_bytes = 0;
+    Stream stream;
+    Event ev_sampled, ev_decoded;
+    Event ev_t[4];  // around the two kernels of the last batch (bposd_debug_dem_timing)
+    // device tables
+    DevArray<double> d_priors;
+    DevArray<int> d_col_ptr, d_col_bits;
+    // per-batch buffers (capacity rows)
+    DevArray<unsigned long long> d_faults, d_detectors, d_observables;
+    DevArray<unsigned long long> d_obs_bp, d_obs_osd0, d_obs_osdw;
+    DevArray<uint8_t> d_flags, d_conv;
+    DevArray<int> d_iters, d_counters, d_obs_fail;
+    PinnedBuf h_counters;  // 8 ints (5 counters), and behind them the k ints of obs_fail: both come down in front of the batch's one host wait
+    std::string err;
+};
+
+namespace bposd_host {
+
+// bposd_dem_sample without the host wait, for another engine's batch: the sampler for rows [0, B) on the engine's stream,
+// and `waiter` ordered behind it by the engine's ev_sampled.  Items 0-2 of bposd_dem_fetch hold the batch once the caller
+// has waited for `waiter`.  Errors are left in dem->err.
+int dem_sample_async(bposd_dem* dem, uint64_t first_shot, int64_t B, hipStream_t waiter);
+
+}  // namespace bposd_host

@@ -12,32 +12,10 @@
 #include <cstring>
 #include <memory>
 
+#include "dem_engine.h"
 #include "dem_kernels.hip.h"
 
 using namespace bposd_dem_dev;
-
-struct bposd_dem {
-    bposd_dem_config cfg{};
-    bposd_handle* dec = nullptr;  // NULL: a sample-only engine
-    int N = 0, M = 0, k = 0, fw = 0, dw = 0, ow = 0;
-    long long capacity = 0;
-    long long sampled_B = 0, scored_B = 0;  // rows of the last batch that items 0-2 / items 3-9 hold
-    int num_cu = 0;
-    size_t device_bytes = 0;
-    Stream stream;
-    Event ev_sampled, ev_decoded;
-    Event ev_t[4];  // around the two kernels of the last batch (bposd_debug_dem_timing)
-    // device tables
-    DevArray<double> d_priors;
-    DevArray<int> d_col_ptr, d_col_bits;
-    // per-batch buffers (capacity rows)
-    DevArray<unsigned long long> d_faults, d_detectors, d_observables;
-    DevArray<unsigned long long> d_obs_bp, d_obs_osd0, d_obs_osdw;
-    DevArray<uint8_t> d_flags, d_conv;
-    DevArray<int> d_iters, d_counters, d_obs_fail;
-    PinnedBuf h_counters;  // 8 ints (5 counters), and behind them the k ints of obs_fail: both come down in front of the batch's one host wait
-    std::string err;
-};
 
 namespace {
 
@@ -188,6 +166,18 @@ int enqueue_sample(bposd_dem* dem, uint64_t first_shot, long long B) {
 }
 
 }  // namespace
+
+int bposd_host::dem_sample_async(bposd_dem* dem, uint64_t first_shot, int64_t B, hipStream_t waiter) {
+    if (B < 1 || B > dem->capacity) return dem_fail(dem, BPOSD_ERR_INVALID, "batch size %lld outside [1, capacity %lld]", (long long)B, dem->capacity);
+    DeviceGuard guard(dem->cfg.device);
+    DEM_TRY(dem, guard.err);
+    dem->sampled_B = dem->scored_B = 0;
+    if (const int rc = enqueue_sample(dem, first_shot, B)) return rc;
+    DEM_TRY(dem, hipEventRecord(dem->ev_sampled, dem->stream));
+    DEM_TRY(dem, hipStreamWaitEvent(waiter, dem->ev_sampled, 0));
+    dem->sampled_B = B;
+    return BPOSD_OK;
+}
 
 extern "C" {
 

@@ -24,7 +24,7 @@ import scipy.sparse as sp
 
 from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
 
-__all__ = ["dem_decode_sim", "phenomenological_dem"]
+__all__ = ["dem_decode_sim", "phenomenological_dem", "phenomenological_detector_times"]
 
 _COUNTS = ("bp_converge_count", "bp_success_count", "osd0_success_count", "osdw_success_count", "trivial_count")
 
@@ -72,6 +72,12 @@ def phenomenological_dem(h, l, rounds, p_data, p_meas):
     L = sp.hstack([sp.kron(np.ones((1, R + 1), np.uint8), l), sp.csr_matrix((l.shape[0], R * m), dtype=np.uint8)], format="csr")
     priors = np.concatenate([np.full((R + 1) * n, float(p_data)), np.full(R * m, float(p_meas))]).astype(np.float64)
     return _gf2_csr(H, "H"), _gf2_csr(L, "L"), priors
+
+
+def phenomenological_detector_times(m, rounds):
+    """The time of every detector of ``phenomenological_dem`` for a code with ``m`` checks: detector (t, c) is row t m + c and
+    has time t, for t = 0 .. rounds (what ``bp_osd_amd.window`` takes as ``detector_time``)."""
+    return np.repeat(np.arange(int(rounds) + 1), int(m))
 
 
 def _pack(rows):

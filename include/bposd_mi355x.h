@@ -502,6 +502,109 @@ const char *bposd_dem_last_error(bposd_dem *dem);
 
 void bposd_dem_destroy(bposd_dem *dem);
 
+/*
+ * Sliding-window engine: a detector error model decoded window by window along time, every window on a decoder of its own,
+ * all of it on the device.  Decoding a model as one matrix meets the size limits above after a few rounds and costs more
+ * per round the longer the experiment is; here the cost per round is constant.  bp_osd_amd/window.py builds the windows
+ * (window_plan) and drives the engine as WindowedDemDecoder and windowed_dem_decode_sim(engine="native"); DESIGN.md 4.12
+ * has the definition.  (No counterpart in the reference.)
+ *
+ * The model is H (M x N), L (k x N); window w is a list D_w of detectors and a list F_w of faults, both ascending, a commit
+ * flag per entry of F_w, and a decoder for H[D_w][:, F_w].  Per shot, with r = the detector row, obs = 0, corr = 0, and
+ * for w = 0 .. nwin - 1 in order:
+ *     s = r[D_w]  ->  osdw row c of decs[w]  ->  for every j with commit flag 1 and c_j = 1:
+ *         r ^= H[:, F_w[j]] (the whole column),  obs ^= L[:, F_w[j]],  corr[F_w[j]] = 1.
+ * Outputs per shot: obs (ceil(k/64) words), corr (ceil(N/64) words), the final r (ceil(M/64) words; zero where every window
+ * has full row rank, which window_plan checks), "BP converged in every window" and the windows' iteration counts summed.
+ *
+ * Between two decodes runs one window_step_kernel (csrc/window_kernels.hip.h): it commits window w - 1 and gathers the
+ * syndrome of window w, staging in LDS only the words of the detector row that the step can touch.  nwin + 1 launches per
+ * batch; the first only gathers, the last only commits.  Window w's decode is the plain device-pointer call of decs[w]
+ * (packed rows where that decoder's kernels take them, byte rows otherwise) on its next lane, ordered against the engine's
+ * stream by events.  The windows of a batch run one after another; the batch is the parallelism.
+ */
+typedef struct bposd_window bposd_window;
+
+typedef struct {
+    int32_t device;    /* HIP device ordinal; every decoder must live there                                   */
+    int64_t capacity;  /* largest batch of one device call: every per-batch buffer is allocated for it        */
+} bposd_window_config;
+
+/* What bposd_window_fetch copies out of the last bposd_window_run (B rows each, but for the last item). */
+enum {
+    BPOSD_WINDOW_OBS = 0,         /* uint64[B][ceil(k/64)]: L . correction                                            */
+    BPOSD_WINDOW_OBSERVABLES = 1, /* uint64[B][ceil(k/64)]: L . faults, the true observables (copied from the sampler) */
+    BPOSD_WINDOW_CORRECTION = 2,  /* uint64[B][ceil(N/64)]                                                            */
+    BPOSD_WINDOW_RESIDUAL = 3,    /* uint64[B][ceil(M/64)]: the detector row behind the last window                   */
+    BPOSD_WINDOW_FLAGS = 4,       /* uint8[B]: bit 0 observables wrong, bit 1 residual not zero, bit 3 no detector fired */
+    BPOSD_WINDOW_CONVERGED = 5,   /* uint8[B]: BP converged in every window                                           */
+    BPOSD_WINDOW_ITERS = 6,       /* int32[B]: BP iterations summed over the windows                                  */
+    BPOSD_WINDOW_OBS_FAIL = 7     /* int32[k]: failures per observable in this batch                                  */
+};
+
+/*
+ * H and L as CSR (columns strictly ascending within a row, as bposd_dem_tables takes them).  Window w holds detectors
+ * win_det[win_det_ptr[w] .. win_det_ptr[w+1]) and faults win_fault[win_fault_ptr[w] .. win_fault_ptr[w+1]), and
+ * win_commit has one byte (0 / 1) per entry of win_fault.  BPOSD_ERR_INVALID, with the window named in the text
+ * (bposd_window_last_error(NULL)), for an empty list, an index out of range or lists that do not ascend strictly, a fault
+ * committed by two windows, a decoder that is NULL, lives on another device or whose (m, n) is not (|D_w|, |F_w|), or whose
+ * matrix is not H[D_w][:, F_w].  BPOSD_ERR_UNSUPPORTED for a step whose staged words -- detector words in range, ceil(k/64)
+ * observable words, the correction words its commit list touches -- exceed 64 KB of LDS.  Everything is copied.  The
+ * engine touches neither the decoders' channels nor their observable tables; decoders may be shared between windows and
+ * between engines, stay the caller's and must outlive the engine.
+ *
+ * Device memory (bposd_window_device_bytes; every block is at least 256 bytes), with cap = capacity, dw = ceil(M/64),
+ * ow = ceil(k/64), fw = ceil(N/64), nc = commit entries over all windows, ncw = correction words over all steps,
+ * synd / dec = the largest syndrome / decoded row of a window in its decoder's form (packed: 8 ceil(./64) bytes; else one
+ * byte per entry):
+ *     tables   4 (N + 1) + 4 (nnz(H) + nnz(L))  col_ptr, col_bits;   3 * 4 nc  commit pos / fault / slot;   4 ncw;   4 sum |D_w|
+ *     batch    8 cap (dw + 2 ow + fw)    running detector rows, observables, true observables, correction
+ *              cap (synd + dec)          the current window's syndrome and decoded rows
+ *              cap (1 + 4 + 1 + 4 + 1)   converged and iterations (all windows; current window), flags
+ *              4 * 8 + 4 k               counters, obs_fail
+ */
+int bposd_window_create(const bposd_window_config *cfg, int32_t M, int32_t N, int32_t k, const int32_t *h_indptr,
+                        const int32_t *h_indices, const int32_t *l_indptr, const int32_t *l_indices, int32_t nwin,
+                        bposd_handle *const *decs, const int32_t *win_det_ptr, const int32_t *win_det,
+                        const int32_t *win_fault_ptr, const int32_t *win_fault, const uint8_t *win_commit,
+                        bposd_window **out);
+
+/* Decode B (1 <= B <= capacity) packed detector rows, every pointer a DEVICE pointer on the engine's device:
+ * d_detector_words [B][ceil(M/64)] in (padding bits zero; not written), d_obs_words [B][ceil(k/64)] out; optional (NULL:
+ * not wanted) d_correction_words [B][ceil(N/64)], d_residual_words [B][ceil(M/64)], d_conv uint8[B], d_iters int32[B].
+ * Asynchronous on the engine's own stream, which is not ordered against the caller's streams: the inputs must be complete
+ * at the call, and bposd_window_synchronize comes before the outputs are read or the next call is made with the same
+ * buffers.  Calls on one engine run one after another. */
+int bposd_window_decode_device(bposd_window *win, const uint64_t *d_detector_words, int64_t B, uint64_t *d_obs_words,
+                               uint64_t *d_correction_words, uint64_t *d_residual_words, uint8_t *d_conv, int32_t *d_iters);
+int bposd_window_synchronize(bposd_window *win);
+
+/* The same with HOST pointers and any B >= 0: runs in chunks of `capacity`, synchronous. */
+int bposd_window_decode(bposd_window *win, const uint64_t *detector_words, int64_t B, uint64_t *obs_words,
+                        uint64_t *correction_words, uint64_t *residual_words, uint8_t *conv, int32_t *iters);
+
+/*
+ * One Monte-Carlo batch: `sampler` -- a sample-only bposd_dem (dec == NULL) of the same M, N, k and device, which holds the
+ * priors and the seed -- samples shots first_shot .. first_shot + B - 1 on its stream, the windows run here, the scorer
+ * compares, and the call returns with the counters on the host: the one host wait of a batch.
+ *   [0] BP converged in every window   [1] success (observables equal the true ones)
+ *   [2] residual not zero              [3] shots in which no detector fired
+ * Afterwards bposd_window_fetch holds the batch, and items 0-2 of bposd_dem_fetch(sampler, ...) its faults, detectors and
+ * true observables.
+ */
+int bposd_window_run(bposd_window *win, bposd_dem *sampler, uint64_t first_shot, int64_t B, int64_t counters[4]);
+
+/* Copy one item (BPOSD_WINDOW_OBS ...) of the last bposd_window_run to host memory; bytes must be that item's size. */
+int bposd_window_fetch(bposd_window *win, int32_t what, void *host_dst, size_t bytes);
+
+/* Device memory the engine holds: the sum documented at bposd_window_create (the decoders' workspaces are their own). */
+int64_t bposd_window_device_bytes(bposd_window *win);
+
+/* Message for the last error on this engine (win == NULL: the last bposd_window_create / bposd_debug_window_step failure). */
+const char *bposd_window_last_error(bposd_window *win);
+
+void bposd_window_destroy(bposd_window *win);
+
 /* Message for the last error on this handle (h == NULL: last create() failure). */
 const char *bposd_last_error(bposd_handle *h);
 

@@ -80,6 +80,41 @@ int bposd_debug_obs_timing(bposd_handle *h, int32_t lane, double *obs_ms);
  * stream; the batch has been waited for).  score_ms is 0 after bposd_dem_sample.  Either pointer may be NULL. */
 int bposd_debug_dem_timing(bposd_dem *dem, double *sample_ms, double *score_ms);
 
+/* Diagnostics: one window_step_kernel launch on rows the caller supplies, with no decoder and no engine involved -- the
+ * commit of one window from `decoded` and the gather of the next into `syndrome`.  Every pointer is a HOST pointer; rows
+ * go up, the kernel runs on `device`, rows come back.  H, L as bposd_dem_tables takes them.  Commit entry c is position
+ * commit_pos[c] (ascending, < decoded_cols) of a decoded row and global fault commit_fault[c] (ascending); decoded holds B
+ * rows of decoded_cols bytes, or (decoded_packed) of ceil(decoded_cols/64) words.  gather_det[n_gather] ascends; syndrome
+ * receives B rows of n_gather bytes or (syndrome_packed) of ceil(n_gather/64) words.  running [B][ceil(M/64)], observables
+ * [B][ceil(k/64)], correction [B][ceil(N/64)] (may be NULL), conv_all uint8[B] and iters int32[B] are read and written
+ * in place; prev_converged / prev_iters [B] may be NULL.  n_commit = 0 is a gather-only step (decoded may be NULL),
+ * n_gather = 0 a commit-only one (syndrome may be NULL).  word_range receives the staged detector words [w_lo, w_hi). */
+typedef struct {
+    int32_t device, M, N, k;
+    const int32_t *h_indptr, *h_indices, *l_indptr, *l_indices;
+    int64_t B;
+    int32_t n_commit;
+    const int32_t *commit_pos, *commit_fault;
+    int32_t decoded_cols, decoded_packed;
+    const void *decoded;
+    const uint8_t *prev_converged;
+    const int32_t *prev_iters;
+    int32_t n_gather;
+    const int32_t *gather_det;
+    int32_t syndrome_packed;
+    void *syndrome;
+    uint64_t *running, *observables, *correction;
+    uint8_t *conv_all;
+    int32_t *iters;
+    int32_t word_range[2];
+} bposd_window_step_args;
+int bposd_debug_window_step(bposd_window_step_args *args);
+
+/* Diagnostics: the durations of the window_step_kernel launches of the engine's last batch, summed, and of
+ * window_score_kernel (HIP events on the engine's stream; waits for the batch).  score_ms is 0 after a decode call.  Either
+ * pointer may be NULL. */
+int bposd_debug_window_timing(bposd_window *win, double *step_ms, double *score_ms);
+
 /* Diagnostics, host only: the tables bp_class_kernel would run with for a pcm whose check and bit degrees fall inside one
  * compiled instance -- (check degrees; bit degrees) = (7; 3..4), (6; 3), (4; 2), (8; 4), (3..4; 1..2) -- and
  * BPOSD_ERR_UNSUPPORTED otherwise.  info[11]: highest check degree, lowest / highest bit degree, bit slots per thread, LDS
