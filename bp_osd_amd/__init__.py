@@ -9,7 +9,7 @@ when the HIP library or a device is missing (there is no CPU fallback).
 """
 from .decoder import BpOsdDecoder, bposd_decoder  # noqa: F401
 from . import codes  # noqa: F401
-from .dem import dem_decode_sim, phenomenological_dem, phenomenological_detector_times  # noqa: F401
+from .dem import dem_decode_sim, importance_table, phenomenological_dem, phenomenological_detector_times  # noqa: F401
 from .window import WindowedDemDecoder, window_plan, windowed_dem_decode_sim  # noqa: F401
 
 __version__ = "0.1.0"

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "bposd_mc_destroy",
     "bposd_dem_tables",
     "bposd_dem_create",
+    "bposd_dem_set_sampling",
     "bposd_dem_sample",
     "bposd_dem_run",
     "bposd_dem_fetch",
@@ -185,7 +186,7 @@ WINDOW_ITEMS = {"obs_osdw": (0, "<u8", "k"), "observables": (1, "<u8", "k"), "co
 # bposd_dem_fetch(what): item -> (number, dtype, columns: "N" / "M" / "k" packed into words, "k32" = k int32 in one row, None = [B])
 DEM_ITEMS = {"faults": (0, "<u8", "N"), "detectors": (1, "<u8", "M"), "observables": (2, "<u8", "k"), "obs_bp": (3, "<u8", "k"),
              "obs_osd0": (4, "<u8", "k"), "obs_osdw": (5, "<u8", "k"), "flags": (6, "u1", None), "converged": (7, "u1", None),
-             "iters": (8, "<i4", None), "obs_fail": (9, "<i4", "k32")}
+             "iters": (8, "<i4", None), "obs_fail": (9, "<i4", "k32"), "logw": (10, "<i8", None)}
 
 
 # bposd_mc_config.channel_update / bposd_mc_fetch(what)
@@ -328,6 +329,8 @@ def load():
     lib.bposd_dem_tables.restype = C.c_int
     lib.bposd_dem_create.argtypes = [C.POINTER(BposdDemConfig), vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.POINTER(vp)]
     lib.bposd_dem_create.restype = C.c_int
+    lib.bposd_dem_set_sampling.argtypes = [vp, vp, vp]
+    lib.bposd_dem_set_sampling.restype = C.c_int
     lib.bposd_dem_sample.argtypes = [vp, C.c_uint64, C.c_int64]
     lib.bposd_dem_sample.restype = C.c_int
     lib.bposd_dem_run.argtypes = [vp, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]

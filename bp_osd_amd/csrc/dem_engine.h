@@ -9,6 +9,8 @@ struct bposd_dem {
     int N = 0, M = 0, k = 0, fw = 0, dw = 0, ow = 0;
     long long capacity = 0;
     long long sampled_B = 0, scored_B = 0;  // rows of the last batch that items 0-2 / items 3-9 hold
+    long long logw_B = 0;                   // rows of the last batch that item 10 holds: sampled_B if it was drawn weighted, else 0
+    bool weighted = false;                  // bposd_dem_set_sampling: draw against d_sample_priors and sum d_incr per shot
     int num_cu = 0;
     size_t device_bytes = 0;
     Stream stream;
@@ -17,11 +19,14 @@ struct bposd_dem {
     // device tables
     DevArray<double> d_priors;
     DevArray<int> d_col_ptr, d_col_bits;
+    DevArray<double> d_sample_priors;  // importance sampling (allocated by the first bposd_dem_set_sampling)
+    DevArray<long long> d_incr;
     // per-batch buffers (capacity rows)
     DevArray<unsigned long long> d_faults, d_detectors, d_observables;
     DevArray<unsigned long long> d_obs_bp, d_obs_osd0, d_obs_osdw;
     DevArray<uint8_t> d_flags, d_conv;
     DevArray<int> d_iters, d_counters, d_obs_fail;
+    DevArray<long long> d_logw;
     PinnedBuf h_counters;  // 8 ints (5 counters), and behind them the k ints of obs_fail: both come down in front of the batch's one host wait
     std::string err;
 };

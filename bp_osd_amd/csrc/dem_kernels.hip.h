@@ -36,6 +36,10 @@ struct DemSampleParams {
     unsigned long long* faults;       // [B][fw]
     unsigned long long* detectors;    // [B][dw]: the layout of bposd_decode_batch_packed, padding bits zero
     unsigned long long* observables;  // [B][ow]
+    // weighted sampling only (dem_sample_kernel<true>; the plain instance reads neither): `priors` is then the row the faults
+    // are drawn against, incr[i] the 2^-32 units of log-weight a fired fault i adds, logw[b] their sum over shot b's faults
+    const long long* incr;  // [N]
+    long long* logw;        // [B]
 };
 
 // every entry of one fault's column: one LDS XOR of a single bit each.  32-bit operations: an entry flips one bit, so the
@@ -49,23 +53,32 @@ __device__ inline void dem_flip_column(unsigned* acc, const int* __restrict__ co
     }
 }
 
+// WEIGHTED: importance sampling.  The draw is the same; every shot also leaves the integer sum of
+// incr[i] over its fired faults.  Each lane sums its own faults across its chunks, the wave reduces the 64 sums as 64-bit
+// values (so a carry between the halves is the adder's business) and one lane adds the wave's sum to one more 64-bit word
+// behind the shot's accumulator row with one LDS atomic.  The word goes out and is cleared with the row: no barrier of its
+// own.  Integer sums do not depend on arrival order, so logw is bit-exact like the rows.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(DEM_THREADS) void dem_sample_kernel(DemSampleParams P) {
-    // [2][dw + ow] accumulator rows.  Two of them, used in turn, make one barrier per shot enough: behind the barrier of
+    // [2][dw + ow] accumulator rows ([2][dw + ow + 1] when WEIGHTED).  Two of them, used in turn, make one barrier per shot
+    // enough: behind the barrier of
     // shot t every thread writes out and clears its own words of row t & 1 while the faults of shot t + 1 already flip bits
     // of the other row, whose words were cleared behind the barrier of shot t - 1 -- that is, in front of the barrier of shot t.
     extern __shared__ unsigned long long dem_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rw = P.dw + P.ow;
+    const int rs = WEIGHTED ? rw + 1 : rw;  // words of a row in LDS
     const int chunks = (P.N + 127) >> 7;  // a wave step covers 128 faults: lane l draws the pair (2l, 2l + 1) of it
-    for (int w = threadIdx.x; w < 2 * rw; w += DEM_THREADS) dem_lds[w] = 0;
+    for (int w = threadIdx.x; w < 2 * rs; w += DEM_THREADS) dem_lds[w] = 0;
     __syncthreads();
 
     int turn = 0;
     for (long long b = blockIdx.x; b < P.B; b += gridDim.x, turn ^= 1) {
-        unsigned long long* row = dem_lds + (size_t)turn * rw;
+        unsigned long long* row = dem_lds + (size_t)turn * rs;
         unsigned* acc = (unsigned*)row;
         const unsigned long long s = P.first_shot + (unsigned long long)b;
         const uint32_t s_lo = (uint32_t)s, s_hi = (uint32_t)(s >> 32);
+        long long lw = 0;  // this lane's share of the shot's log-weight
         for (int ch = wave; ch < chunks; ch += DEM_WAVES) {
             const int pair = ch * 64 + lane;
             const int i0 = 2 * pair, i1 = i0 + 1;
@@ -86,13 +99,24 @@ __global__ __launch_bounds__(DEM_THREADS) void dem_sample_kernel(DemSampleParams
             }
             if (f0) dem_flip_column(acc, P.col_ptr, P.col_bits, i0);
             if (f1) dem_flip_column(acc, P.col_ptr, P.col_bits, i1);
+            if constexpr (WEIGHTED) {
+                if (f0) lw += P.incr[i0];
+                if (f1) lw += P.incr[i1];
+            }
+        }
+        if constexpr (WEIGHTED) {
+            if (wave < chunks) {  // (wave-uniform: the lanes of a wave that drew are all here)
+                for (int d = 32; d; d >>= 1) lw += __shfl_xor(lw, d);
+                if (lane == 0 && lw) atomicAdd(&row[rw], (unsigned long long)lw);
+            }
         }
         __syncthreads();  // the row is complete
-        for (int w = threadIdx.x; w < rw; w += DEM_THREADS) {
+        for (int w = threadIdx.x; w < rs; w += DEM_THREADS) {
             const unsigned long long v = row[w];
             row[w] = 0;  // for shot t + 2
             if (w < P.dw) P.detectors[(size_t)b * P.dw + w] = v;
-            else P.observables[(size_t)b * P.ow + (w - P.dw)] = v;
+            else if (!WEIGHTED || w < rw) P.observables[(size_t)b * P.ow + (w - P.dw)] = v;
+            else P.logw[b] = (long long)v;
         }
     }
 }

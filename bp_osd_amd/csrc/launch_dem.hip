@@ -1,5 +1,6 @@
 // launch_dem.hip -- the detector-error-model Monte-Carlo engine of libbposd_mi355x.so: bposd_dem_* of include/bposd_mi355x.h.
-// One translation unit: dem_sample_kernel and dem_score_kernel (dem_kernels.hip.h) are instantiated here and nowhere else.
+// One translation unit: both instances of dem_sample_kernel and dem_score_kernel (dem_kernels.hip.h) are instantiated here and
+// nowhere else.
 //
 // A batch is sample faults -> detectors and true observables -> one decode straight to observables -> compare -> five
 // integers.  The engine owns every buffer of it and a stream of its own; the decode goes through the decoder's
@@ -138,7 +139,10 @@ int create_impl(bposd_dem* dem, const std::vector<int32_t>& col_ptr, const std::
     return 0;
 }
 
-size_t sample_lds_bytes(const bposd_dem* dem) { return 2 * sizeof(unsigned long long) * (size_t)(dem->dw + dem->ow); }
+// two accumulator rows, and behind each the log-weight word of the weighted instance
+size_t sample_lds_bytes(const bposd_dem* dem, bool weighted) {
+    return 2 * sizeof(unsigned long long) * (size_t)(dem->dw + dem->ow + (weighted ? 1 : 0));
+}
 
 // dem_sample_kernel for rows [0, B) on the engine's stream, between ev_t[0] and ev_t[1]
 int enqueue_sample(bposd_dem* dem, uint64_t first_shot, long long B) {
@@ -151,17 +155,24 @@ int enqueue_sample(bposd_dem* dem, uint64_t first_shot, long long B) {
     S.fw = dem->fw;
     S.dw = dem->dw;
     S.ow = dem->ow;
-    S.priors = dem->d_priors;
+    S.priors = dem->weighted ? dem->d_sample_priors : dem->d_priors;
     S.col_ptr = dem->d_col_ptr;
     S.col_bits = dem->d_col_bits;
     S.faults = dem->d_faults;
     S.detectors = dem->d_detectors;
     S.observables = dem->d_observables;
+    S.incr = dem->d_incr;  // (NULL until the first bposd_dem_set_sampling; the plain instance reads neither)
+    S.logw = dem->d_logw;
     const unsigned grid = (unsigned)std::min<long long>(B, (long long)dem->num_cu * 8);
+    dem->logw_B = 0;
     DEM_TRY(dem, hipEventRecord(dem->ev_t[0], dem->stream));
-    hipLaunchKernelGGL(dem_sample_kernel, dim3(grid), dim3(DEM_THREADS), sample_lds_bytes(dem), dem->stream, S);
+    if (dem->weighted)
+        hipLaunchKernelGGL(dem_sample_kernel<true>, dim3(grid), dim3(DEM_THREADS), sample_lds_bytes(dem, true), dem->stream, S);
+    else
+        hipLaunchKernelGGL(dem_sample_kernel<false>, dim3(grid), dim3(DEM_THREADS), sample_lds_bytes(dem, false), dem->stream, S);
     DEM_TRY(dem, hipGetLastError());
     DEM_TRY(dem, hipEventRecord(dem->ev_t[1], dem->stream));
+    if (dem->weighted) dem->logw_B = B;
     return 0;
 }
 
@@ -233,9 +244,9 @@ int bposd_dem_create(const bposd_dem_config* cfg, bposd_handle* dec, const int32
     dem->ow = (k + 63) / 64;
     dem->capacity = cfg->capacity;
     dem->num_cu = dec ? dec->num_cu : 0;
-    if (sample_lds_bytes(dem) > 64 * 1024)
+    if (sample_lds_bytes(dem, false) > 64 * 1024)
         return dem_fail(nullptr, BPOSD_ERR_UNSUPPORTED, "%d detectors and %d observables need %zu bytes of LDS per workgroup, more than 65536", M, k,
-                        sample_lds_bytes(dem));
+                        sample_lds_bytes(dem, false));
     int rc = 0;
     std::vector<uint64_t> table;
     if (dec) {  // (validated before anything is allocated)
@@ -251,6 +262,41 @@ int bposd_dem_create(const bposd_dem_config* cfg, bposd_handle* dec, const int32
     // create that fails leaves the caller's decoder as it was.
     if (dec && (rc = bposd_set_observables(dec, table.data(), k))) return dem_fail(nullptr, rc, "bposd_set_observables: %s", bposd_last_error(dec));
     *out = owner.release();
+    return BPOSD_OK;
+}
+
+int bposd_dem_set_sampling(bposd_dem* dem, const double* sample_priors, const int64_t* incr) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if ((sample_priors == nullptr) != (incr == nullptr))
+        return dem_fail(dem, BPOSD_ERR_INVALID, "sample_priors and incr go together: give both, or NULL for both to sample plainly");
+    if (!sample_priors) {  // back to the model's own priors; the tables stay allocated for the next switch
+        dem->weighted = false;
+        dem->logw_B = 0;
+        return BPOSD_OK;
+    }
+    // everything is validated before anything changes: a refusal leaves the engine in the mode it was in
+    unsigned long long total = 0;  // sum of |incr|: every term and the running sum stay below 2^63
+    for (int i = 0; i < dem->N; ++i) {
+        if (!(sample_priors[i] >= 0.0 && sample_priors[i] <= 1.0))  // (a NaN fails both comparisons)
+            return dem_fail(dem, BPOSD_ERR_INVALID, "the sampling probability of fault %d (%g) is not a probability", i, sample_priors[i]);
+        const unsigned long long a = incr[i] < 0 ? 0ull - (unsigned long long)incr[i] : (unsigned long long)incr[i];
+        if (a >= (1ull << 62) || (total += a) >= (1ull << 62))
+            return dem_fail(dem, BPOSD_ERR_INVALID, "the increments up to fault %d sum to 2^62 or more in magnitude: a shot's log-weight could overflow", i);
+    }
+    if (sample_lds_bytes(dem, true) > 64 * 1024)
+        return dem_fail(dem, BPOSD_ERR_UNSUPPORTED, "weighted sampling needs %zu bytes of LDS per workgroup, more than 65536", sample_lds_bytes(dem, true));
+    DeviceGuard guard(dem->cfg.device);
+    DEM_TRY(dem, guard.err);
+    DEM_TRY(dem, hipStreamSynchronize(dem->stream));  // no sampler is reading the tables
+    int rc;
+    if (!dem->d_sample_priors.p && (rc = dem_alloc(dem, dem->d_sample_priors, (size_t)dem->N))) return rc;
+    if (!dem->d_incr.p && (rc = dem_alloc(dem, dem->d_incr, (size_t)dem->N))) return rc;
+    if (!dem->d_logw.p && (rc = dem_alloc(dem, dem->d_logw, (size_t)dem->capacity))) return rc;
+    dem->weighted = false;  // (until both tables are the new ones)
+    dem->logw_B = 0;        // what item 10 held was summed from the table that goes
+    DEM_TRY(dem, hipMemcpy(dem->d_sample_priors, sample_priors, sizeof(double) * (size_t)dem->N, hipMemcpyHostToDevice));
+    DEM_TRY(dem, hipMemcpy(dem->d_incr, incr, sizeof(int64_t) * (size_t)dem->N, hipMemcpyHostToDevice));
+    dem->weighted = true;
     return BPOSD_OK;
 }
 
@@ -325,10 +371,14 @@ int bposd_dem_run(bposd_dem* dem, uint64_t first_shot, int64_t B, int64_t counte
 int bposd_dem_fetch(bposd_dem* dem, int32_t what, void* host_dst, size_t bytes) {
     if (!dem) return BPOSD_ERR_INVALID;
     if (!host_dst) return dem_fail(dem, BPOSD_ERR_INVALID, "destination is NULL");
-    if (what < BPOSD_DEM_FAULTS || what > BPOSD_DEM_OBS_FAIL)
-        return dem_fail(dem, BPOSD_ERR_INVALID, "what = %d is not one of BPOSD_DEM_FAULTS .. BPOSD_DEM_OBS_FAIL", what);
+    if (what < BPOSD_DEM_FAULTS || what > BPOSD_DEM_LOGW)
+        return dem_fail(dem, BPOSD_ERR_INVALID, "what = %d is not one of BPOSD_DEM_FAULTS .. BPOSD_DEM_LOGW", what);
+    if (what == BPOSD_DEM_LOGW && !dem->weighted)
+        return dem_fail(dem, BPOSD_ERR_INVALID, "item %d needs weighted sampling (bposd_dem_set_sampling): this engine samples plainly", what);
     if (dem->sampled_B == 0) return dem_fail(dem, BPOSD_ERR_INVALID, "no batch has run yet");
-    if (what >= BPOSD_DEM_OBS_BP && dem->scored_B == 0)
+    if (what == BPOSD_DEM_LOGW && dem->logw_B != dem->sampled_B)
+        return dem_fail(dem, BPOSD_ERR_INVALID, "item %d needs a batch sampled since bposd_dem_set_sampling", what);
+    if (what >= BPOSD_DEM_OBS_BP && what <= BPOSD_DEM_OBS_FAIL && dem->scored_B == 0)
         return dem_fail(dem, BPOSD_ERR_INVALID, "item %d needs bposd_dem_run: the last batch was sampled only", what);
     const void* src = nullptr;
     size_t row = 0, rows = (size_t)dem->sampled_B;
@@ -342,6 +392,7 @@ int bposd_dem_fetch(bposd_dem* dem, int32_t what, void* host_dst, size_t bytes) 
     case BPOSD_DEM_FLAGS: src = dem->d_flags; row = 1; break;
     case BPOSD_DEM_CONVERGED: src = dem->d_conv; row = 1; break;
     case BPOSD_DEM_ITERS: src = dem->d_iters; row = sizeof(int32_t); break;
+    case BPOSD_DEM_LOGW: src = dem->d_logw; row = sizeof(int64_t); break;
     default: src = dem->d_obs_fail; row = sizeof(int32_t) * (size_t)dem->k; rows = 1; break;  // BPOSD_DEM_OBS_FAIL: one row per batch
     }
     const size_t want = row * rows;

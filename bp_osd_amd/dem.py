@@ -12,19 +12,25 @@ five integers.  It needs no torch.  ``engine="numpy"`` is the same loop on the h
 ``decode_batch``.  Both draw from the project's counter-based Philox stream (``sim.philox_uniforms``), indexed by (shot,
 fault): they see the same shots whatever their batch sizes, and a CPU run reproduces a GPU run shot for shot.
 
+Importance sampling (``sample_priors`` / ``sample_scale``) draws the faults from a harsher row ``q`` while
+the decoder keeps ``priors`` as its channel, and weighs every shot by its likelihood ratio: logical error rates far below one
+over the number of shots become measurable.  The per-shot log-weight is an integer sum (``importance_table``), so it is
+bit-exact on both engines like everything else of a shot.
+
 ``phenomenological_dem`` builds ``(H, L, priors)`` of the repeated-measurement model of a code, so that the engine can be
 used with no circuit simulator at hand; INTEGRATION.md says how the three come out of a detector-error-model file.
 """
 from __future__ import annotations
 
 import json
+import math
 
 import numpy as np
 import scipy.sparse as sp
 
 from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
 
-__all__ = ["dem_decode_sim", "phenomenological_dem", "phenomenological_detector_times"]
+__all__ = ["dem_decode_sim", "importance_table", "phenomenological_dem", "phenomenological_detector_times"]
 
 _COUNTS = ("bp_converge_count", "bp_success_count", "osd0_success_count", "osdw_success_count", "trivial_count")
 
@@ -89,6 +95,47 @@ def _pack(rows):
     return out.view("<u8")
 
 
+LOGW_ONE = 2 ** 32  # units of a log-weight increment per nat
+
+
+def importance_table(priors, sample_priors):
+    """``(incr int64 [N], c0 float)`` of drawing the faults from ``q = sample_priors`` in place of ``p = priors``: the one
+    place that turns probabilities into the integers both engines sum.  The likelihood ratio of a shot with fault row f is
+
+        w = exp(c0 + sum_{i: f_i = 1} a_i),  a_i = log(p_i / q_i) - log((1 - p_i) / (1 - q_i)),  c0 = sum_i log((1 - p_i) / (1 - q_i))
+
+    and ``incr[i] = round(a_i * 2**32)``, so that ``w = exp(c0 + logw / 2**32)`` with the integer ``logw = f @ incr`` (the
+    rounding moves w by at most 2^-33 relative per fired fault).  Terms with ``p_i == q_i`` are exactly 0, at 0 and 1 too.
+    ``q_i == 0`` is allowed only where ``p_i == 0`` and ``q_i == 1`` only where ``p_i == 1``; ``|a_i| > 64`` (which takes in
+    p_i = 0 or 1 against another q_i) and ``sum |incr| >= 2**62`` are refused: no shot can overflow.  Every refusal is a
+    ValueError naming the fault.  Scalar ``math.log`` / ``math.log1p`` and ``math.fsum``: the same bits on every build."""
+    p = np.ascontiguousarray(priors, dtype=np.float64)
+    q = np.ascontiguousarray(sample_priors, dtype=np.float64)
+    if p.ndim != 1 or q.shape != p.shape:
+        raise ValueError(f"priors and sample_priors must be two vectors of one length, not {p.shape} and {q.shape}")
+    incr = np.zeros(p.shape[0], np.int64)
+    c_terms, total = [], 0
+    for i, (pi, qi) in enumerate(zip(p.tolist(), q.tolist())):
+        if not 0.0 <= pi <= 1.0:
+            raise ValueError(f"the prior of fault {i} ({pi}) is not a probability")
+        if not 0.0 <= qi <= 1.0:
+            raise ValueError(f"the sampling probability of fault {i} ({qi}) is not a probability")
+        if pi == qi:
+            continue
+        if qi == 0.0 or qi == 1.0:
+            raise ValueError(f"fault {i} is sampled with probability {qi:g} but has prior {pi}: the weight of a shot would be unbounded")
+        lb = math.log1p(-pi) - math.log1p(-qi) if pi < 1.0 else -math.inf  # log((1 - p) / (1 - q))
+        a = (math.log(pi / qi) if pi > 0.0 else -math.inf) - lb
+        if not abs(a) <= 64.0:  # (an infinite a: p_i is 0 or 1 and q_i is not)
+            raise ValueError(f"the likelihood ratio of fault {i} (prior {pi}, sampled with {qi}) is beyond e^64")
+        incr[i] = int(round(a * LOGW_ONE))
+        total += abs(int(incr[i]))
+        if total >= 2 ** 62:
+            raise ValueError(f"the increments up to fault {i} sum to 2^62 or more: a shot's log-weight could overflow")
+        c_terms.append(lb)
+    return incr, math.fsum(c_terms)
+
+
 class dem_decode_sim:
     """See the module docstring.
 
@@ -102,14 +149,25 @@ class dem_decode_sim:
         mapping with "osdw", "osd0", "bp", "converged", "iters", or the osdw rows with the rest left as ``batch_osd0``,
         ``batch_bp``, ``batch_converge``, ``batch_iter``
     run_sim : run at once (default) or wait for :meth:`run_decode_sim`
+    sample_priors, sample_scale : importance sampling, at most one of the two.  ``sample_priors`` = q, N floats in [0, 1] the
+        faults are drawn against (``u(s, i) < q_i``: the same stream and counter) while the decoder keeps ``priors``;
+        ``sample_scale`` = beta >= 1 is ``q_i = p_i`` where ``p_i >= 0.5``, else ``min(beta * p_i, 0.5)``.  See below
 
     Results: ``run_count``, ``bp_converge_count``, ``bp_success_count`` (converged and observables right),
     ``osd0_success_count``, ``osdw_success_count``, ``trivial_count`` (no detector fired), ``*_logical_error_rate`` with
     ``*_logical_error_rate_eb = sqrt(L (1 - L) / runs)`` as css_decode_sim has them, ``osdw_observable_error_rates``
-    (float [k]), :meth:`output_dict` and :meth:`last_batch`."""
+    (float [k]), :meth:`output_dict` and :meth:`last_batch`.
+
+    With importance sampling every shot has the weight ``w = exp(c0 + logw / 2**32)`` of :func:`importance_table`, and the
+    rates become ``*_logical_error_rate = sum(w fail) / n`` with ``*_logical_error_rate_eb = sqrt(max(sum(w^2 fail) / n -
+    rate^2, 0) / n)`` (fail of bp: not converged or observables wrong).  ``weight_mean = sum(w) / n`` has expectation 1 and
+    ``effective_sample_fraction = sum(w)^2 / (n sum(w^2))`` says how many plain shots the weighted ones are worth; both and
+    ``sample_scale`` appear in :meth:`output_dict` only then.  The ``*_count`` attributes stay unweighted counts of the shots
+    as sampled, and ``osdw_observable_error_rates`` stays unweighted too (failures per sampled shot, not a rate under
+    ``priors``).  ``last_batch("logw")`` is the int64 log-weight of every shot of the last batch."""
 
     def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=100, decoder_factory=None, run_sim=True,
-                 **decoder_kwargs):
+                 sample_priors=None, sample_scale=None, **decoder_kwargs):
         if engine not in ("native", "numpy"):
             raise ValueError("engine must be 'native' or 'numpy'")
         if engine == "native" and decoder_factory is not None:
@@ -129,6 +187,23 @@ class dem_decode_sim:
         if bad.size:
             raise ValueError(f"the prior of fault {int(bad[0])} ({p[bad[0]]}) is not a probability")
         self._priors = p
+        if sample_priors is not None and sample_scale is not None:
+            raise ValueError("give sample_priors or sample_scale, not both")
+        self.sample_scale = None
+        if sample_scale is not None:
+            self.sample_scale = float(sample_scale)
+            if not 1.0 <= self.sample_scale < math.inf:
+                raise ValueError(f"sample_scale must be a finite number >= 1, not {sample_scale}")
+            sample_priors = np.where(p >= 0.5, p, np.minimum(self.sample_scale * p, 0.5))
+        self._tilted = sample_priors is not None
+        if self._tilted:
+            q = np.ascontiguousarray(sample_priors, dtype=np.float64)
+            if q.shape != (self.N,):
+                raise ValueError(f"sample_priors must have length {self.N}, not {q.shape}")
+            self._incr, self._c0 = importance_table(p, q)
+            self._sample_priors = q
+            self._wsum = dict.fromkeys(("w", "w2", "bp", "bp2", "osd0", "osd02", "osdw", "osdw2"), 0.0)
+            self.weight_mean = self.effective_sample_fraction = 0.0
         self._batch_size = int(batch_size)
         if self._batch_size < 1:
             raise ValueError("batch_size must be >= 1")
@@ -173,6 +248,8 @@ class dem_decode_sim:
         self._dem = dem
         self.decoder._observables_installed(self.K)  # bposd_dem_create has set the decoder's table
         self._last_B = 0
+        if self._tilted:
+            _lib.check_dem(lib, dem, lib.bposd_dem_set_sampling(dem, self._sample_priors.ctypes.data, self._incr.ctypes.data))
 
     def _run_batch_native(self, B):
         import ctypes as C
@@ -183,6 +260,8 @@ class dem_decode_sim:
         _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_run(self._dem, int(self.run_count), int(B), c))
         self._last_B = B
         self._accumulate(B, [int(v) for v in c], self.last_batch("obs_fail"))
+        if self._tilted:
+            self._accumulate_weighted(self.last_batch("flags"), self.last_batch("converged"), self.last_batch("logw"))
 
     def device_bytes(self):
         """engine="native": bytes of device memory the engine holds for its batches (the decoder's workspaces are its own)."""
@@ -209,7 +288,8 @@ class dem_decode_sim:
 
     # ------------------------------------------------------------------ the host loop
     def _run_batch_numpy(self, B):
-        faults = (philox_uniforms(self.seed, self.run_count, B, self.N) < self._priors).astype(np.uint8)
+        drawn = self._sample_priors if self._tilted else self._priors
+        faults = (philox_uniforms(self.seed, self.run_count, B, self.N) < drawn).astype(np.uint8)
         detectors = _mod2_mul(self._H, faults)
         truth = _mod2_mul(self._L, faults)
         r = self.decoder.decode_batch(detectors)
@@ -233,6 +313,9 @@ class dem_decode_sim:
         counters = [int(conv.sum()), int((conv & ~wrong["bp"]).sum()), int((~wrong["osd0"]).sum()), int((~wrong["osdw"]).sum()),
                     int(quiet.sum())]
         self._accumulate(B, counters, obs_fail)
+        if self._tilted:
+            self._last["logw"] = faults.astype(np.int64) @ self._incr
+            self._accumulate_weighted(flags, self._last["converged"], self._last["logw"])
 
     # ------------------------------------------------------------------ common
     def _accumulate(self, B, counters, obs_fail):
@@ -247,6 +330,26 @@ class dem_decode_sim:
             setattr(self, f"{key}_logical_error_rate_eb", float(np.sqrt((1 - ler) * ler / n)))
         self.osdw_observable_error_rates = self._obs_fail / n
 
+    def _accumulate_weighted(self, flags, converged, logw):
+        """The weighted sums of one batch (after ``_accumulate``, whose plain rates it replaces) from the batch's per-shot flags,
+        convergence and integer log-weights: the same arithmetic on either engine."""
+        w = np.exp(self._c0 + np.asarray(logw, dtype=np.int64) / LOGW_ONE)
+        w2 = w * w
+        flags = np.asarray(flags)
+        fail = {"bp": ((flags & 1) != 0) | (np.asarray(converged) == 0), "osd0": (flags & 2) != 0, "osdw": (flags & 4) != 0}
+        S = self._wsum
+        S["w"] += float(w.sum())
+        S["w2"] += float(w2.sum())
+        n = self.run_count
+        for key, f in fail.items():
+            S[key] += float(w[f].sum())
+            S[key + "2"] += float(w2[f].sum())
+            rate = S[key] / n
+            setattr(self, f"{key}_logical_error_rate", rate)
+            setattr(self, f"{key}_logical_error_rate_eb", math.sqrt(max(S[key + "2"] / n - rate * rate, 0.0) / n))
+        self.weight_mean = S["w"] / n
+        self.effective_sample_fraction = S["w"] * S["w"] / (n * S["w2"])
+
     def run_decode_sim(self):
         while self.run_count < self.target_runs:
             B = min(self._batch_size, self.target_runs - self.run_count)
@@ -260,11 +363,14 @@ class dem_decode_sim:
         """One array of the last batch: "faults", "detectors", "observables" (the true ones), "obs_bp", "obs_osd0", "obs_osdw"
         (bit-packed rows, uint64 [B, ceil(./64)]: ``BpOsdDecoder.unpack_rows`` expands them), "flags" (uint8 [B]: bit 0 bp
         wrong, 1 osd0 wrong, 2 osdw wrong, 3 no detector fired), "converged" (uint8 [B]), "iters" (int32 [B]) or "obs_fail"
-        (int32 [k]: osdw failures per observable in that batch).  engine="native" copies it from the device."""
+        (int32 [k]: osdw failures per observable in that batch), and with importance sampling "logw" (int64 [B]: the shot's
+        log-weight in units of 2^-32).  engine="native" copies it from the device."""
         from . import _lib
 
         if what not in _lib.DEM_ITEMS:
             raise ValueError(f"what must be one of {sorted(_lib.DEM_ITEMS)}")
+        if what == "logw" and not self._tilted:
+            raise ValueError("last_batch('logw') needs importance sampling (sample_priors or sample_scale)")
         if self._engine == "numpy":
             if self._last is None:
                 raise RuntimeError("last_batch needs a batch that has run")
@@ -289,4 +395,8 @@ class dem_decode_sim:
             out[f"{key}_logical_error_rate"] = float(getattr(self, f"{key}_logical_error_rate"))
             out[f"{key}_logical_error_rate_eb"] = float(getattr(self, f"{key}_logical_error_rate_eb"))
         out["osdw_observable_error_rates"] = [float(v) for v in self.osdw_observable_error_rates]
+        if self._tilted:
+            out["sample_scale"] = self.sample_scale
+            out["weight_mean"] = float(self.weight_mean)
+            out["effective_sample_fraction"] = float(self.effective_sample_fraction)
         return json.dumps(out, sort_keys=True, indent=4)

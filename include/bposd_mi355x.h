@@ -450,7 +450,8 @@ enum {
     BPOSD_DEM_FLAGS = 6,       /* uint8[B]: bit 0 bp wrong, bit 1 osd0 wrong, bit 2 osdw wrong, bit 3 no detector fired */
     BPOSD_DEM_CONVERGED = 7,   /* uint8[B]                                                                            */
     BPOSD_DEM_ITERS = 8,       /* int32[B]                                                                            */
-    BPOSD_DEM_OBS_FAIL = 9     /* int32[k]: osdw failures per observable in this batch                                */
+    BPOSD_DEM_OBS_FAIL = 9,    /* int32[k]: osdw failures per observable in this batch                                */
+    BPOSD_DEM_LOGW = 10        /* int64[B]: the shot's log-weight in units of 2^-32 (weighted sampling only, see below) */
 };
 
 /*
@@ -477,8 +478,29 @@ int bposd_dem_create(const bposd_dem_config *cfg, bposd_handle *dec, const int32
                      int32_t M, const int32_t *l_indptr, const int32_t *l_indices, int32_t k, int32_t N,
                      const double *priors, bposd_dem **out);
 
+/*
+ * Importance sampling: draw the faults from a harsher row q = sample_priors[N] while the decoder keeps the model's priors p
+ * as its channel, and leave a per-shot log-likelihood ratio.  Fault i of global shot s then fires iff u(s, i) < q[i] -- the
+ * same stream, the same counter -- and item BPOSD_DEM_LOGW holds, per shot, the sum of incr[i] over the faults that fired:
+ * an integer sum, so it does not depend on the order in which lanes and atomics arrive and is bit-exact on every device,
+ * batch size and host restatement (faults.astype(int64) @ incr).  The caller chooses incr; for the likelihood ratio
+ * w = prod_i (p_i/q_i)^f_i ((1-p_i)/(1-q_i))^(1-f_i) of a shot with fault row f it is
+ *     incr[i] = round(a_i * 2^32),  a_i = log(p_i / q_i) - log((1 - p_i) / (1 - q_i))   (0 where p_i == q_i),
+ *     c0 = sum_i log((1 - p_i) / (1 - q_i)),                  w = exp(c0 + logw / 2^32),
+ * with q_i == 0 only where p_i == 0 and q_i == 1 only where p_i == 1 (bp_osd_amd.dem.importance_table computes exactly
+ * this and refuses the rest).  The rounding moves a weight by at most 2^-33 relative per fired fault.
+ *
+ * Both arrays are copied.  Every q[i] must be in [0, 1] (a NaN is refused, the message names the fault) and the sum of
+ * |incr[i]| must be below 2^62, so that no shot can overflow; NULL for one pointer only is refused; a refusal leaves the
+ * engine in the mode it was in.  NULL, NULL switches back to plain sampling.  Works on sample-only engines too.  The first
+ * call allocates the two tables and int64[capacity] (counted in bposd_dem_device_bytes).  The five counters of
+ * bposd_dem_run stay unweighted counts of the shots as sampled.  A sample-only engine handed to bposd_window_run draws in
+ * the mode it is in; that engine's own results know nothing of weights.
+ */
+int bposd_dem_set_sampling(bposd_dem *dem, const double *sample_priors, const int64_t *incr);
+
 /* The sampler alone: shots first_shot .. first_shot + B - 1 (1 <= B <= capacity); waits for the kernel.  Items 0-2 of
- * bposd_dem_fetch hold the batch afterwards. */
+ * bposd_dem_fetch hold the batch afterwards (and item 10 while weighted sampling is on). */
 int bposd_dem_sample(bposd_dem *dem, uint64_t first_shot, int64_t B);
 
 /*
@@ -486,12 +508,14 @@ int bposd_dem_sample(bposd_dem *dem, uint64_t first_shot, int64_t B);
  * stream.  Returns with the counters on the host -- the one host wait of a batch:
  *   [0] bp converged   [1] bp success (converged AND observables equal the true ones)   [2] osd0 success
  *   [3] osdw success   [4] shots in which no detector fired
- * B outside [1, capacity] is BPOSD_ERR_INVALID.  All ten items of bposd_dem_fetch hold the batch afterwards.
+ * B outside [1, capacity] is BPOSD_ERR_INVALID.  Items 0-9 of bposd_dem_fetch hold the batch afterwards (and item 10 while
+ * weighted sampling is on).
  */
 int bposd_dem_run(bposd_dem *dem, uint64_t first_shot, int64_t B, int64_t counters[5]);
 
 /* Copy one item (BPOSD_DEM_FAULTS ...) of the last batch to host memory; bytes must be that item's size for the last B.
- * After bposd_dem_sample only items 0-2 are there.  BPOSD_DEM_OBS_FAIL came down with the counters: no device call. */
+ * After bposd_dem_sample only items 0-2 are there.  BPOSD_DEM_OBS_FAIL came down with the counters: no device call.
+ * BPOSD_DEM_LOGW needs a batch sampled while weighted sampling is on: BPOSD_ERR_INVALID otherwise. */
 int bposd_dem_fetch(bposd_dem *dem, int32_t what, void *host_dst, size_t bytes);
 
 /* Device memory the engine holds (the sum of its own allocations; the decoder's workspaces are its own). */

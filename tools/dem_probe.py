@@ -11,7 +11,12 @@ Per model, ``--rounds`` rounds, alternating, of ``--steps`` calls each:
       time, as the engine issues it): the engine's overhead over it is (a) - (b), with its spread over the rounds;
   (c) once, the loop the engine replaces on ``--host-shots`` of the same shots: host Philox draw, ``_mod2_mul``,
       ``decode_batch_observables``, numpy compare -- and its counters against the engine's on those shots.
-Prints one line per figure; ``--out FILE`` appends them there (profiles/dem_rates.txt)."""
+Prints one line per figure; ``--out FILE`` appends them there (profiles/dem_rates.txt).
+
+``--sample-scale BETA`` measures importance sampling instead (profiles/dem_weight_rates.txt): three engines on the model --
+plain, weighted with q = p (the same faults: what the weighted instance of the sampler costs by itself) and weighted with
+``sample_scale=BETA`` (more faults fire, and the decoder gets harder shots) -- alternating over the rounds, whole batches:
+the sampler's HIP-event time, the ``bposd_dem_run`` call, and the batch as ``dem_decode_sim`` runs it with its fetches."""
 import argparse
 import os
 import sys
@@ -37,6 +42,53 @@ def model(name):
     return phenomenological_dem(code.hz, code.lz, 3, 0.02, 0.02), kw, "hgp(mkmn_16_4_6) hz, R = 3, p = q = 0.02; min-sum, osd_cs 7"
 
 
+def weighted_probe(a, say):
+    """--sample-scale: the weighted sampler against the plain one."""
+    import ctypes as C
+
+    from bp_osd_amd import dem_decode_sim
+
+    (H, L, priors), kw, what = model(a.model)
+    B, seed = a.batch, 5
+    say(f"# tools/dem_probe.py --sample-scale {a.sample_scale:g} on one MI355X: {what}; H {H.shape[0]} x {H.shape[1]}, k = {L.shape[0]}, B = {B}; "
+        f"{a.rounds} rounds of {a.steps} batches per engine, alternating")
+    make = lambda **tilt: dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=0, run_sim=False, **tilt, **kw)
+    sims = {"plain": make(), "weighted, q = p": make(sample_priors=priors.copy()), f"weighted, scale {a.sample_scale:g}": make(sample_scale=a.sample_scale)}
+    for sim in sims.values():
+        for _ in range(2):  # warm-up: workspaces, the kernels' first launch
+            sim._run_batch_native(B)
+    t = {name: dict(sample=[], call=[], batch=[]) for name in sims}
+    c5 = (C.c_int64 * 5)()
+    for _ in range(a.rounds):
+        for name, sim in sims.items():
+            call = batch = 0.0
+            for _ in range(a.steps):
+                t0 = time.perf_counter()
+                rc = sim._lib.bposd_dem_run(sim._dem, sim.run_count, B, c5)
+                t1 = time.perf_counter()
+                assert rc == 0, sim._lib.bposd_dem_last_error(sim._dem)
+                sim._last_B = B
+                sim._accumulate(B, [int(v) for v in c5], sim.last_batch("obs_fail"))
+                if sim._tilted:
+                    sim._accumulate_weighted(sim.last_batch("flags"), sim.last_batch("converged"), sim.last_batch("logw"))
+                t2 = time.perf_counter()
+                call += t1 - t0
+                batch += t2 - t0
+                t[name]["sample"].append(sim.kernel_ms()[0])
+            t[name]["call"].append(call / a.steps * 1e3)
+            t[name]["batch"].append(batch / a.steps * 1e3)
+    fmt = lambda v: " / ".join(f"{x:.2f}" for x in v)
+    base = np.mean(t["plain"]["sample"])
+    for name, sim in sims.items():
+        r = t[name]
+        say(f"{name}: dem_sample_kernel, HIP events: mean {np.mean(r['sample']):.3f} ms (min {min(r['sample']):.3f}, max {max(r['sample']):.3f}, "
+            f"{len(r['sample'])} batches) = {np.mean(r['sample']) / base:.2f} x plain; bposd_dem_run, ms per batch and round: {fmt(r['call'])}; "
+            f"whole batch with its fetches: {fmt(r['batch'])} ({B / np.mean(r['batch']) * 1e3:,.0f} runs/s); device {sim.device_bytes() / B:.1f} B per shot")
+        extra = f", weight_mean {sim.weight_mean:.4f}, effective sample fraction {sim.effective_sample_fraction:.3f}" if sim._tilted else ""
+        say(f"    after {sim.run_count} shots: osdw logical error rate {sim.osdw_logical_error_rate:.3e} +- {sim.osdw_logical_error_rate_eb:.1e}, "
+            f"osdw failures among the shots as sampled {1 - sim.osdw_success_count / sim.run_count:.5f}{extra}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("h1922", "hgp400r3"), default="h1922")
@@ -45,7 +97,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--host-shots", type=int, default=16384)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sample-scale", type=float, default=None, help="measure the weighted sampler against the plain one at this sample_scale")
     a = ap.parse_args()
+    if a.sample_scale is not None:
+        lines = []
+
+        def say(s):
+            print(s, flush=True)
+            lines.append(s)
+
+        weighted_probe(a, say)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n\n")
+        return
 
     import torch  # (plumbing of (b) only: a device buffer for the bare decode call)
     torch.cuda.init()  # torch's HIP runtime before libbposd_mi355x.so pulls in the system one
