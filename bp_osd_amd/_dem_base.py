@@ -1,0 +1,159 @@
+"""What the two detector-error-model harnesses share (``dem.dem_decode_sim`` and ``window.windowed_dem_decode_sim``): the
+model's validation, the run loop over batches, the counters and rates of a run, and the native engine's plumbing (creating a
+``bposd_dem``, fetching an item of the last batch, device bytes and kernel times).  A harness keeps its constructor, its two
+``_run_batch_*`` and what is its own in ``last_batch`` and ``output_dict``."""
+from __future__ import annotations
+
+import numpy as np
+import scipy.sparse as sp
+
+
+def _gf2_csr(a, what):
+    """scipy CSR over GF(2) with sorted indices and no stored zeros."""
+    if sp.issparse(a):
+        m = sp.csr_matrix(a).astype(np.int64)
+    else:
+        arr = np.asarray(a)
+        if arr.ndim != 2:
+            raise ValueError(f"{what} must be a 2-D array or scipy.sparse matrix")
+        m = sp.csr_matrix(arr.astype(np.int64) & 1)
+    m.sum_duplicates()
+    m.data %= 2
+    m.eliminate_zeros()
+    m.sort_indices()
+    return m.astype(np.uint8)
+
+
+def checked_model(H, L, priors):
+    """``(H, L, priors)`` as GF(2) CSR (M x N), (k x N) and float64 [N], or the ValueError that says what is wrong."""
+    H, L = _gf2_csr(H, "H"), _gf2_csr(L, "L")
+    N, K = H.shape[1], L.shape[0]
+    if L.shape[1] != N:
+        raise ValueError(f"L must have shape (k, {N}), not {L.shape}")
+    if not 1 <= K <= 4096:
+        raise ValueError(f"the number of observables k = {K} is outside 1 .. 4096")
+    p = np.ascontiguousarray(priors, dtype=np.float64)
+    if p.shape != (N,):
+        raise ValueError(f"priors must have length {N}, not {p.shape}")
+    bad = np.flatnonzero(~((p >= 0) & (p <= 1)))
+    if bad.size:
+        raise ValueError(f"the prior of fault {int(bad[0])} ({p[bad[0]]}) is not a probability")
+    return H, L, p
+
+
+def create_dem(lib, device, seed, capacity, H, L, priors, decoder_handle):
+    """bposd_dem_create over the model; ``decoder_handle`` None makes a sample-only engine.  Returns the engine pointer."""
+    import ctypes as C
+
+    from . import _lib
+
+    cfg = _lib.BposdDemConfig(device=int(device), seed=seed, capacity=int(capacity))
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    keep = [i32(H.indptr), i32(H.indices), i32(L.indptr), i32(L.indices)]
+    dem = C.c_void_p()
+    rc = lib.bposd_dem_create(C.byref(cfg), decoder_handle, keep[0].ctypes.data, keep[1].ctypes.data, H.shape[0], keep[2].ctypes.data,
+                              keep[3].ctypes.data, L.shape[0], H.shape[1], priors.ctypes.data, C.byref(dem))
+    _lib.check_dem(lib, None, rc)
+    return dem
+
+
+class DemSimBase:
+    """The run of a harness.  A subclass sets ``_COUNTS`` (the counters of a batch, in the library's order), ``_RATES`` (the
+    keys whose ``<key>_success_count`` gets a ``<key>_logical_error_rate`` and ``..._eb``), ``M``, ``N`` and ``K``, and has
+    ``_run_batch_native(B)`` and ``_run_batch_numpy(B)``, which end in :meth:`_accumulate`."""
+
+    _COUNTS = ()
+    _RATES = ()
+    _lib = None
+
+    def _check_engine(self, engine, decoder_factory, drives):
+        if engine not in ("native", "numpy"):
+            raise ValueError("engine must be 'native' or 'numpy'")
+        if engine == "native" and decoder_factory is not None:
+            raise ValueError(f"engine='native' drives the MI355X {drives} through device pointers; decoder_factory must be None")
+        self._engine = self.engine = engine
+
+    def _init_run(self, batch_size, seed, target_runs):
+        self._batch_size = int(batch_size)
+        if self._batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.target_runs = int(target_runs)
+        self.run_count = 0
+        for key in self._COUNTS:
+            setattr(self, key, 0)
+        for key in self._RATES:
+            setattr(self, f"{key}_logical_error_rate", 0.0)
+            setattr(self, f"{key}_logical_error_rate_eb", 0.0)
+        self._obs_fail = np.zeros(self.K, np.int64)
+        self.osdw_observable_error_rates = np.zeros(self.K, np.float64)
+        self._last = None  # engine="numpy": the items of the last batch
+        self._last_B = 0   # engine="native": its size
+
+    def run_decode_sim(self):
+        while self.run_count < self.target_runs:
+            B = min(self._batch_size, self.target_runs - self.run_count)
+            if self._engine == "native":
+                self._run_batch_native(B)
+            else:
+                self._run_batch_numpy(B)
+        return self.output_dict()
+
+    def _accumulate(self, B, counters, obs_fail):
+        self.run_count += B
+        for key, v in zip(self._COUNTS, counters):
+            setattr(self, key, getattr(self, key) + v)
+        self._obs_fail += np.asarray(obs_fail, dtype=np.int64)
+        n = self.run_count
+        for key in self._RATES:  # css_decode_sim's formulas
+            ler = 1 - getattr(self, f"{key}_success_count") / n
+            setattr(self, f"{key}_logical_error_rate", ler)
+            setattr(self, f"{key}_logical_error_rate_eb", float(np.sqrt((1 - ler) * ler / n)))
+        self.osdw_observable_error_rates = self._obs_fail / n
+
+    def _results(self):
+        """The part of ``output_dict`` every harness has: the run, its counters, rates and failures per observable."""
+        out = {"N": self.N, "M": self.M, "K": self.K, "seed": self.seed, "engine": self.engine, "target_runs": self.target_runs,
+               "run_count": self.run_count}
+        for key in self._COUNTS:
+            out[key] = int(getattr(self, key))
+        for key in self._RATES:
+            out[f"{key}_logical_error_rate"] = float(getattr(self, f"{key}_logical_error_rate"))
+            out[f"{key}_logical_error_rate_eb"] = float(getattr(self, f"{key}_logical_error_rate_eb"))
+        out["osdw_observable_error_rates"] = [float(v) for v in self.osdw_observable_error_rates]
+        return out
+
+    # ------------------------------------------------------------------ the library's engine
+    def _device_bytes(self, handle, fn):
+        if handle is None:
+            raise RuntimeError("device_bytes needs engine='native'")
+        return int(getattr(self._lib, fn)(handle))
+
+    def _kernel_ms(self, handle, fn, check):
+        import ctypes as C
+
+        if handle is None:
+            raise RuntimeError("kernel_ms needs engine='native'")
+        a, b = C.c_double(), C.c_double()
+        check(self._lib, handle, getattr(self._lib, fn)(handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _last_batch(self, what, fetch):
+        """Item ``what`` (a name the subclass has checked) of the last batch: the numpy engine's array, or ``fetch()``."""
+        if self._engine == "numpy":
+            if self._last is None:
+                raise RuntimeError("last_batch needs a batch that has run")
+            return self._last[what]
+        if not self._last_B:
+            raise RuntimeError("last_batch needs a batch that has run")
+        return fetch()
+
+    def _fetch(self, items, handle, fetch_fn, check_fn, what):
+        """Entry ``what`` of a ``_lib.*_ITEMS`` table from the engine ``handle``: its shape for the last batch, and the copy."""
+        item, dtype, cols = items[what]
+        B = self._last_B
+        width = {"N": self.N, "M": self.M, "k": self.K}
+        shape = (B,) if cols is None else (self.K,) if cols == "k32" else (B, (width[cols] + 63) // 64)
+        out = np.empty(shape, dtype=np.dtype(dtype))
+        check_fn(self._lib, handle, fetch_fn(handle, item, out.ctypes.data, out.nbytes))
+        return out

@@ -372,45 +372,32 @@ def load():
     return lib
 
 
-def check_dem(lib, dem, rc):
-    """check() for the detector-error-model engine's calls (dem None: a failed bposd_dem_create / bposd_dem_tables)."""
+def _raise(last_error_fn, obj, rc):
+    """Map a C-ABI return code to the exception the reference's users would expect (obj None: a failed create)."""
     if rc == BPOSD_OK:
         return
-    msg = lib.bposd_dem_last_error(dem)
+    msg = last_error_fn(obj)
     msg = msg.decode() if msg else f"error {rc}"
     if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
         raise ValueError(msg)
     raise RuntimeError(msg)
+
+
+def check_dem(lib, dem, rc):
+    """check() for the detector-error-model engine's calls (dem None: a failed bposd_dem_create / bposd_dem_tables)."""
+    _raise(lib.bposd_dem_last_error, dem, rc)
 
 
 def check_window(lib, win, rc):
     """check() for the sliding-window engine's calls (win None: a failed bposd_window_create / bposd_debug_window_step)."""
-    if rc == BPOSD_OK:
-        return
-    msg = lib.bposd_window_last_error(win)
-    msg = msg.decode() if msg else f"error {rc}"
-    if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
-        raise ValueError(msg)
-    raise RuntimeError(msg)
+    _raise(lib.bposd_window_last_error, win, rc)
 
 
 def check_mc(lib, mc, rc):
     """check() for the Monte-Carlo engine's calls (mc None: a failed bposd_mc_create)."""
-    if rc == BPOSD_OK:
-        return
-    msg = lib.bposd_mc_last_error(mc)
-    msg = msg.decode() if msg else f"error {rc}"
-    if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
-        raise ValueError(msg)
-    raise RuntimeError(msg)
+    _raise(lib.bposd_mc_last_error, mc, rc)
 
 
 def check(lib, handle, rc):
-    """Map a C-ABI return code to the exception the reference's users would expect."""
-    if rc == BPOSD_OK:
-        return
-    msg = lib.bposd_last_error(handle)
-    msg = msg.decode() if msg else f"error {rc}"
-    if rc in (BPOSD_ERR_INVALID, BPOSD_ERR_UNSUPPORTED):
-        raise ValueError(msg)
-    raise RuntimeError(msg)
+    """check() for a decoder handle's calls (handle None: a failed bposd_create)."""
+    _raise(lib.bposd_last_error, handle, rc)

@@ -1,19 +1,15 @@
 // dem_engine.h -- the state of a detector-error-model engine (bposd_dem of include/bposd_mi355x.h), shared by launch_dem.hip,
 // which owns it, and launch_window.hip, whose Monte-Carlo run samples on a sample-only engine and reads its rows.
 #pragma once
-#include "internal.h"
+#include "engine_common.h"
 
-struct bposd_dem {
+struct bposd_dem : EngineBase {
     bposd_dem_config cfg{};
     bposd_handle* dec = nullptr;  // NULL: a sample-only engine
     int N = 0, M = 0, k = 0, fw = 0, dw = 0, ow = 0;
-    long long capacity = 0;
     long long sampled_B = 0, scored_B = 0;  // rows of the last batch that items 0-2 / items 3-9 hold
     long long logw_B = 0;                   // rows of the last batch that item 10 holds: sampled_B if it was drawn weighted, else 0
     bool weighted = false;                  // bposd_dem_set_sampling: draw against d_sample_priors and sum d_incr per shot
-    int num_cu = 0;
-    size_t device_bytes = 0;
-    Stream stream;
     Event ev_sampled, ev_decoded;
     Event ev_t[4];  // around the two kernels of the last batch (bposd_debug_dem_timing)
     // device tables
@@ -25,10 +21,9 @@ struct bposd_dem {
     DevArray<unsigned long long> d_faults, d_detectors, d_observables;
     DevArray<unsigned long long> d_obs_bp, d_obs_osd0, d_obs_osdw;
     DevArray<uint8_t> d_flags, d_conv;
-    DevArray<int> d_iters, d_counters, d_obs_fail;
+    DevArray<int> d_iters;
     DevArray<long long> d_logw;
-    PinnedBuf h_counters;  // 8 ints (5 counters), and behind them the k ints of obs_fail: both come down in front of the batch's one host wait
-    std::string err;
+    CounterBlock counters;  // 5 counters
 };
 
 namespace bposd_host {

@@ -3,15 +3,9 @@
 //
 // A batch is nwin + 1 step kernels with a decode between every two of them: step w commits window w - 1 and gathers the
 // syndrome of window w, window w's decoder takes that syndrome through its plain device-pointer call on its next lane, and
-// the engine's stream and that lane are ordered against each other by events (the pattern of bposd_dem_run).  The engine
+// the engine's stream and that lane are ordered against each other by events (decode_behind of engine_common.h).  The engine
 // owns the tables of every step and the rows of a batch; the decoders stay the caller's.  The host waits once per
 // Monte-Carlo batch, for the counters.
-#include "internal.h"
-
-#include <cstdarg>
-#include <cstring>
-#include <memory>
-
 #include "dem_engine.h"
 #include "window_kernels.hip.h"
 
@@ -55,20 +49,16 @@ struct StepDev {  // where a step's lists start in the engine's device tables
 
 }  // namespace
 
-struct bposd_window {
+struct bposd_window : EngineBase {
     bposd_window_config cfg{};
     int M = 0, N = 0, k = 0, dw = 0, ow = 0, fw = 0, nwin = 0;
-    long long capacity = 0;
     long long run_B = 0;      // rows of the last bposd_window_run that bposd_window_fetch holds
     bool timed_steps = false, timed_score = false;
-    int num_cu = 0;
-    size_t device_bytes = 0;
     std::vector<bposd_handle*> decs;  // [nwin], the caller's
     std::vector<int> n_det, n_fault;  // [nwin]
     std::vector<char> packed;         // [nwin]: the decoder's kernels took packed rows when the engine was made (the row buffers are sized for that form)
     std::vector<StepPlan> steps;      // [nwin + 1] (lists are kept for the launch parameters' counts)
     std::vector<StepDev> at;          // [nwin + 1]
-    Stream stream;
     std::vector<Event> ev_step, ev_decoded;  // [nwin]: the syndrome of window w is gathered / its rows are decoded
     std::vector<Event> ev_t;                 // 2 (nwin + 1) around the step kernels, 2 around the scorer (bposd_debug_window_timing)
     // device tables
@@ -78,45 +68,13 @@ struct bposd_window {
     DevArray<unsigned long long> d_running, d_obs, d_truth, d_corr;
     DevBuf d_synd, d_dec;  // the current window's syndrome and decoded rows, in its decoder's form
     DevArray<uint8_t> d_conv_all, d_wconv, d_flags;
-    DevArray<int> d_iters, d_witers, d_counters, d_obs_fail;
-    PinnedBuf h_counters;  // 8 ints (4 counters), and behind them the k ints of obs_fail
-    std::string err;
+    DevArray<int> d_iters, d_witers;
+    CounterBlock counters;  // 4 counters
 };
 
 namespace {
 
-int win_fail(bposd_window* win, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int win_fail(bposd_window* win, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (win) win->err = buf;
-    else bposd_host::fail(nullptr, code, "%s", buf);  // read back through bposd_last_error(NULL), like a failed bposd_create
-    return code;
-}
-
-#define WIN_TRY(win, expr)                                                                                             \
-    do {                                                                                                               \
-        hipError_t _e = (expr);                                                                                        \
-        if (_e != hipSuccess)                                                                                          \
-            return win_fail(win, BPOSD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-template <class B>
-int win_alloc(bposd_window* win, B& p, size_t bytes) {
-    bytes = std::max<size_t>(bytes, 256);
-    WIN_TRY(win, p.alloc(bytes));
-    if (win) win->device_bytes += bytes;
-    return 0;
-}
-
-int win_upload(bposd_window* win, DevArray<int>& p, const std::vector<int>& v) {
-    if (const int rc = win_alloc(win, p, v.size() * sizeof(int))) return rc;
-    if (!v.empty()) WIN_TRY(win, hipMemcpy(p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
-    return 0;
-}
+int upload(EngineBase* e, DevArray<int>& p, const std::vector<int>& v) { return engine_upload(e, p, v.data(), v.size()); }
 
 size_t row_bytes(int cols, bool packed) { return packed ? 8 * (size_t)((cols + 63) / 64) : (size_t)cols; }
 
@@ -124,59 +82,60 @@ size_t step_lds(const StepPlan& s, int ow) { return window_step_lds_bytes(s.w_lo
 
 unsigned step_grid(long long B, int num_cu) { return (unsigned)std::min<long long>(B, (long long)num_cu * 8); }
 
-// The stacked CSC of H and L (validated by bposd_dem_tables, whose message is passed on).
-int stacked_csc(const int32_t* h_rp, const int32_t* h_ci, int M, const int32_t* l_rp, const int32_t* l_ci, int k, int N,
-                std::vector<int32_t>* col_ptr, std::vector<int32_t>* col_bits) {
-    if (M < 1 || N < 1 || !h_rp || !l_rp) return win_fail(nullptr, BPOSD_ERR_INVALID, "bad shape or missing matrix: M %d, N %d", M, N);
-    col_ptr->assign((size_t)N + 1, 0);
-    col_bits->clear();
-    if (k >= 1 && k <= bposd_host::obs_max_k() && h_rp[0] == 0 && l_rp[0] == 0 && h_rp[M] >= 0 && l_rp[k] >= 0)
-        col_bits->resize((size_t)h_rp[M] + (size_t)l_rp[k]);
-    return bposd_dem_tables(h_rp, h_ci, M, l_rp, l_ci, k, N, col_ptr->data(), col_bits->data());  // (its text is bposd_last_error(NULL) too)
-}
-
 struct Rows {  // the rows a chain of windows works on (device)
     unsigned long long *running, *obs, *corr;  // corr null: not wanted
     uint8_t* conv;
     int* iters;
 };
 
-WindowStepParams step_params(const bposd_window* win, int s, long long B, const Rows& r) {
-    const StepPlan& sp = win->steps[s];
-    const StepDev& a = win->at[s];
+struct StepTables {  // the model's stacked CSC and one step's lists (device)
+    const int *col_ptr, *col_bits, *commit_pos, *commit_fault, *commit_slot, *corr_words, *gather;
+};
+
+// A step's launch parameters but for the two decodes around it (decoded / prev_* and syndrome), which the caller adds.
+WindowStepParams step_params(const StepPlan& sp, long long B, int dw, int ow, int fw, const StepTables& t, const Rows& r) {
     WindowStepParams P{};
     P.B = B;
-    P.dw = win->dw;
-    P.ow = win->ow;
-    P.fw = win->fw;
+    P.dw = dw;
+    P.ow = ow;
+    P.fw = fw;
     P.w_lo = sp.w_lo;
     P.w_hi = sp.w_hi;
-    P.col_ptr = win->d_col_ptr;
-    P.col_bits = win->d_col_bits;
+    P.col_ptr = t.col_ptr;
+    P.col_bits = t.col_bits;
     P.n_commit = (int)sp.fault.size();
     P.n_corr = (int)sp.corr_words.size();
-    P.commit_pos = win->d_commit_pos + a.commit;
-    P.commit_fault = win->d_commit_fault + a.commit;
-    P.commit_slot = win->d_commit_slot + a.commit;
-    P.corr_words = win->d_corr_words + a.corr;
+    P.commit_pos = t.commit_pos;
+    P.commit_fault = t.commit_fault;
+    P.commit_slot = t.commit_slot;
+    P.corr_words = t.corr_words;
     P.decoded_cols = sp.decoded_cols;
+    P.n_gather = (int)sp.gather.size();
+    P.gather_det = t.gather;
+    P.running = r.running;
+    P.observables = r.obs;
+    P.correction = r.corr;
+    P.conv_all = r.conv;
+    P.iters = r.iters;
+    return P;
+}
+
+// Step s of the engine: its lists in the engine's tables, the decode of window s - 1 behind it and of window s ahead.
+WindowStepParams step_params(const bposd_window* win, int s, long long B, const Rows& r) {
+    const StepDev& a = win->at[s];
+    const StepTables t{win->d_col_ptr, win->d_col_bits, win->d_commit_pos + a.commit, win->d_commit_fault + a.commit, win->d_commit_slot + a.commit,
+                       win->d_corr_words + a.corr, win->d_gather + a.gather};
+    WindowStepParams P = step_params(win->steps[s], B, win->dw, win->ow, win->fw, t, r);
     if (s > 0) {
         P.decoded = win->d_dec.p;
         P.decoded_packed = win->packed[s - 1];
         P.prev_conv = win->d_wconv;
         P.prev_iters = win->d_witers;
     }
-    P.n_gather = (int)sp.gather.size();
-    P.gather_det = win->d_gather + a.gather;
     if (s < win->nwin) {
         P.syndrome = win->d_synd.p;
         P.syndrome_packed = win->packed[s];
     }
-    P.running = r.running;
-    P.observables = r.obs;
-    P.correction = r.corr;
-    P.conv_all = r.conv;
-    P.iters = r.iters;
     return P;
 }
 
@@ -186,47 +145,39 @@ int enqueue_windows(bposd_window* win, long long B, const Rows& r) {
     hipStream_t st = win->stream;
     for (int w = 0; w < win->nwin; ++w)
         if ((native_packed(win->decs[w]) ? 1 : 0) != win->packed[w])
-            return win_fail(win, BPOSD_ERR_INVALID, "window %d: the decoder's kernel variant was changed after the engine was made (its rows are %s now)", w,
+            return engine_fail(win, BPOSD_ERR_INVALID, "window %d: the decoder's kernel variant was changed after the engine was made (its rows are %s now)", w,
                             win->packed[w] ? "bytes" : "packed");
-    WIN_TRY(win, hipMemsetAsync(r.obs, 0, sizeof(unsigned long long) * (size_t)B * win->ow, st));
-    if (r.corr) WIN_TRY(win, hipMemsetAsync(r.corr, 0, sizeof(unsigned long long) * (size_t)B * win->fw, st));
-    WIN_TRY(win, hipMemsetAsync(r.conv, 1, (size_t)B, st));
-    WIN_TRY(win, hipMemsetAsync(r.iters, 0, sizeof(int) * (size_t)B, st));
+    ENGINE_TRY(win, hipMemsetAsync(r.obs, 0, sizeof(unsigned long long) * (size_t)B * win->ow, st));
+    if (r.corr) ENGINE_TRY(win, hipMemsetAsync(r.corr, 0, sizeof(unsigned long long) * (size_t)B * win->fw, st));
+    ENGINE_TRY(win, hipMemsetAsync(r.conv, 1, (size_t)B, st));
+    ENGINE_TRY(win, hipMemsetAsync(r.iters, 0, sizeof(int) * (size_t)B, st));
     win->timed_steps = win->timed_score = false;
     for (int s = 0; s <= win->nwin; ++s) {
         const WindowStepParams P = step_params(win, s, B, r);
-        WIN_TRY(win, hipEventRecord(win->ev_t[2 * s], st));
+        ENGINE_TRY(win, hipEventRecord(win->ev_t[2 * s], st));
         hipLaunchKernelGGL(window_step_kernel, dim3(step_grid(B, win->num_cu)), dim3(WIN_THREADS), step_lds(win->steps[s], win->ow), st, P);
-        WIN_TRY(win, hipGetLastError());
-        WIN_TRY(win, hipEventRecord(win->ev_t[2 * s + 1], st));
+        ENGINE_TRY(win, hipGetLastError());
+        ENGINE_TRY(win, hipEventRecord(win->ev_t[2 * s + 1], st));
         if (s == win->nwin) break;
         // window s on its decoder's next lane, ordered behind the gather; ev_decoded is recorded on that lane behind the call
         bposd_handle* const dec = win->decs[s];
-        WIN_TRY(win, hipEventRecord(win->ev_step[s], st));
-        WIN_TRY(win, hipStreamWaitEvent(dec->lanes[dec->next_lane].stream, win->ev_step[s], 0));
-        const int rc = win->packed[s]
-                           ? bposd_decode_batch_device_packed(dec, (const uint64_t*)win->d_synd.p, B, (uint64_t*)win->d_dec.p, nullptr, nullptr, win->d_wconv, win->d_witers)
-                           : bposd_decode_batch_device(dec, (const uint8_t*)win->d_synd.p, B, (uint8_t*)win->d_dec.p, nullptr, nullptr, win->d_wconv, win->d_witers, nullptr);
-        if (rc) {
-            (void)hipStreamSynchronize(st);  // leave nothing running behind the error
-            return win_fail(win, rc, "window %d: decode failed: %s", s, bposd_last_error(dec));
-        }
-        WIN_TRY(win, hipEventRecord(win->ev_decoded[s], dec->lanes[dec->last_lane].stream));
-        WIN_TRY(win, hipStreamWaitEvent(st, win->ev_decoded[s], 0));
+        ENGINE_TRY(win, hipEventRecord(win->ev_step[s], st));
+        const int rc = decode_behind(win, dec, win->ev_step[s], win->ev_decoded[s], [&] {
+            return win->packed[s]
+                       ? bposd_decode_batch_device_packed(dec, (const uint64_t*)win->d_synd.p, B, (uint64_t*)win->d_dec.p, nullptr, nullptr, win->d_wconv, win->d_witers)
+                       : bposd_decode_batch_device(dec, (const uint8_t*)win->d_synd.p, B, (uint8_t*)win->d_dec.p, nullptr, nullptr, win->d_wconv, win->d_witers, nullptr);
+        });
+        if (rc) return engine_fail(win, rc, "window %d: %s", s, win->err.c_str());
+        ENGINE_TRY(win, hipStreamWaitEvent(st, win->ev_decoded[s], 0));
     }
     win->timed_steps = true;
     return 0;
 }
 
-int check_batch(bposd_window* win, int64_t B) {
-    if (B < 1 || B > win->capacity) return win_fail(win, BPOSD_ERR_INVALID, "batch size %lld outside [1, capacity %lld]", (long long)B, win->capacity);
-    return 0;
-}
-
 int create_device(bposd_window* win, const std::vector<int32_t>& col_ptr, const std::vector<int32_t>& col_bits) {
     int rc;
-    if ((rc = win_upload(win, win->d_col_ptr, col_ptr))) return rc;
-    if ((rc = win_upload(win, win->d_col_bits, col_bits))) return rc;
+    if ((rc = upload(win, win->d_col_ptr, col_ptr))) return rc;
+    if ((rc = upload(win, win->d_col_bits, col_bits))) return rc;
     std::vector<int> pos, fault, slot, corr, gather;
     size_t synd = 0, dec = 0;
     for (int s = 0; s <= win->nwin; ++s) {
@@ -243,33 +194,31 @@ int create_device(bposd_window* win, const std::vector<int32_t>& col_ptr, const 
             dec = std::max(dec, row_bytes(win->n_fault[s], packed));
         }
     }
-    if ((rc = win_upload(win, win->d_commit_pos, pos))) return rc;
-    if ((rc = win_upload(win, win->d_commit_fault, fault))) return rc;
-    if ((rc = win_upload(win, win->d_commit_slot, slot))) return rc;
-    if ((rc = win_upload(win, win->d_corr_words, corr))) return rc;
-    if ((rc = win_upload(win, win->d_gather, gather))) return rc;
+    if ((rc = upload(win, win->d_commit_pos, pos))) return rc;
+    if ((rc = upload(win, win->d_commit_fault, fault))) return rc;
+    if ((rc = upload(win, win->d_commit_slot, slot))) return rc;
+    if ((rc = upload(win, win->d_corr_words, corr))) return rc;
+    if ((rc = upload(win, win->d_gather, gather))) return rc;
     const size_t C = (size_t)win->capacity;
-    if ((rc = win_alloc(win, win->d_running, 8 * C * win->dw))) return rc;
-    if ((rc = win_alloc(win, win->d_obs, 8 * C * win->ow))) return rc;
-    if ((rc = win_alloc(win, win->d_truth, 8 * C * win->ow))) return rc;
-    if ((rc = win_alloc(win, win->d_corr, 8 * C * win->fw))) return rc;
-    if ((rc = win_alloc(win, win->d_synd, C * synd))) return rc;
-    if ((rc = win_alloc(win, win->d_dec, C * dec))) return rc;
-    if ((rc = win_alloc(win, win->d_conv_all, C))) return rc;
-    if ((rc = win_alloc(win, win->d_iters, 4 * C))) return rc;
-    if ((rc = win_alloc(win, win->d_wconv, C))) return rc;
-    if ((rc = win_alloc(win, win->d_witers, 4 * C))) return rc;
-    if ((rc = win_alloc(win, win->d_flags, C))) return rc;
-    if ((rc = win_alloc(win, win->d_counters, 8 * sizeof(int)))) return rc;
-    if ((rc = win_alloc(win, win->d_obs_fail, sizeof(int) * (size_t)win->k))) return rc;
-    WIN_TRY(win, win->h_counters.alloc((8 + (size_t)win->k) * sizeof(int), hipHostMallocDefault));
-    WIN_TRY(win, hipStreamCreateWithFlags(&win->stream.raw, hipStreamNonBlocking));
+    if ((rc = engine_alloc(win, win->d_running, C * win->dw))) return rc;
+    if ((rc = engine_alloc(win, win->d_obs, C * win->ow))) return rc;
+    if ((rc = engine_alloc(win, win->d_truth, C * win->ow))) return rc;
+    if ((rc = engine_alloc(win, win->d_corr, C * win->fw))) return rc;
+    if ((rc = engine_alloc_bytes(win, win->d_synd, C * synd))) return rc;
+    if ((rc = engine_alloc_bytes(win, win->d_dec, C * dec))) return rc;
+    if ((rc = engine_alloc(win, win->d_conv_all, C))) return rc;
+    if ((rc = engine_alloc(win, win->d_iters, C))) return rc;
+    if ((rc = engine_alloc(win, win->d_wconv, C))) return rc;
+    if ((rc = engine_alloc(win, win->d_witers, C))) return rc;
+    if ((rc = engine_alloc(win, win->d_flags, C))) return rc;
+    if ((rc = win->counters.alloc(win, win->k))) return rc;
+    ENGINE_TRY(win, hipStreamCreateWithFlags(&win->stream.raw, hipStreamNonBlocking));
     win->ev_step.resize(win->nwin);
     win->ev_decoded.resize(win->nwin);
     win->ev_t.resize(2 * ((size_t)win->nwin + 1) + 2);
     for (auto* v : {&win->ev_step, &win->ev_decoded})
-        for (Event& e : *v) WIN_TRY(win, hipEventCreateWithFlags(&e.raw, hipEventDisableTiming));
-    for (Event& e : win->ev_t) WIN_TRY(win, hipEventCreate(&e.raw));
+        for (Event& e : *v) ENGINE_TRY(win, hipEventCreateWithFlags(&e.raw, hipEventDisableTiming));
+    for (Event& e : win->ev_t) ENGINE_TRY(win, hipEventCreate(&e.raw));
     return 0;
 }
 
@@ -279,30 +228,30 @@ extern "C" {
 
 const char* bposd_window_last_error(bposd_window* win) { return win ? win->err.c_str() : bposd_last_error(nullptr); }
 
-void bposd_window_destroy(bposd_window* win) {
-    if (!win) return;
-    DeviceGuard guard(win->cfg.device);  // (outlives the delete)
-    if (win->stream) (void)hipStreamSynchronize(win->stream);
-    delete win;
-}
+void bposd_window_destroy(bposd_window* win) { engine_destroy(win); }
 
 int bposd_window_create(const bposd_window_config* cfg, int32_t M, int32_t N, int32_t k, const int32_t* h_indptr, const int32_t* h_indices,
                         const int32_t* l_indptr, const int32_t* l_indices, int32_t nwin, bposd_handle* const* decs, const int32_t* win_det_ptr,
                         const int32_t* win_det, const int32_t* win_fault_ptr, const int32_t* win_fault, const uint8_t* win_commit,
                         bposd_window** out) {
-    if (!out) return win_fail(nullptr, BPOSD_ERR_INVALID, "out is NULL");
+    if (!out) return engine_fail(nullptr, BPOSD_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    if (!cfg) return win_fail(nullptr, BPOSD_ERR_INVALID, "config is required");
-    if (cfg->capacity < 1 || cfg->capacity > 0x7fffffffLL) return win_fail(nullptr, BPOSD_ERR_INVALID, "capacity %lld out of range", (long long)cfg->capacity);
+    if (!cfg) return engine_fail(nullptr, BPOSD_ERR_INVALID, "config is required");
+    if (cfg->capacity < 1 || cfg->capacity > 0x7fffffffLL) return engine_fail(nullptr, BPOSD_ERR_INVALID, "capacity %lld out of range", (long long)cfg->capacity);
     if (nwin < 1 || !decs || !win_det_ptr || !win_det || !win_fault_ptr || !win_fault || !win_commit)
-        return win_fail(nullptr, BPOSD_ERR_INVALID, "at least one window and every window list are required (nwin %d)", nwin);
+        return engine_fail(nullptr, BPOSD_ERR_INVALID, "at least one window and every window list are required (nwin %d)", nwin);
+    std::string why;
     std::vector<int32_t> col_ptr, col_bits;
-    if (const int rc = stacked_csc(h_indptr, h_indices, M, l_indptr, l_indices, k, N, &col_ptr, &col_bits)) return rc;
-    if (win_det_ptr[0] != 0 || win_fault_ptr[0] != 0) return win_fail(nullptr, BPOSD_ERR_INVALID, "win_det_ptr[0] and win_fault_ptr[0] must be 0");
+    if (const int rc = bposd_host::stacked_csc(h_indptr, h_indices, M, l_indptr, l_indices, k, N, &col_ptr, &col_bits, &why))
+        return engine_fail(nullptr, rc, "%s", why.c_str());
+    // the window lists are two more CSR operands: row w holds window w's detectors / faults
+    if (bposd_host::check_csr("win_det", win_det_ptr, win_det, nwin, M, true, &why) || bposd_host::check_csr("win_fault", win_fault_ptr, win_fault, nwin, N, true, &why))
+        return engine_fail(nullptr, BPOSD_ERR_INVALID, "%s", why.c_str());
 
     std::unique_ptr<bposd_window, decltype(&bposd_window_destroy)> owner(new bposd_window(), bposd_window_destroy);
     bposd_window* const win = owner.get();
     win->cfg = *cfg;
+    win->device = cfg->device;
     win->M = M;
     win->N = N;
     win->k = k;
@@ -321,27 +270,18 @@ int bposd_window_create(const bposd_window_config* cfg, int32_t M, int32_t N, in
     std::vector<int> committed_by((size_t)N, -1), pos_of((size_t)N, -1), row;
     for (int w = 0; w < nwin; ++w) {
         const int d0 = win_det_ptr[w], d1 = win_det_ptr[w + 1], f0 = win_fault_ptr[w], f1 = win_fault_ptr[w + 1];
-        if (d1 <= d0 || f1 <= f0) return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: %d detectors and %d faults: a window needs both", w, d1 - d0, f1 - f0);
+        if (d1 <= d0 || f1 <= f0) return engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: %d detectors and %d faults: a window needs both", w, d1 - d0, f1 - f0);
         const int nd = d1 - d0, nf = f1 - f0;
         win->n_det[w] = nd;
         win->n_fault[w] = nf;
-        for (int e = d0; e < d1; ++e) {
-            if (win_det[e] < 0 || win_det[e] >= M) return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: detector %d is outside [0, %d)", w, win_det[e], M);
-            if (e > d0 && win_det[e] <= win_det[e - 1])
-                return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the detectors do not ascend strictly (at detector %d)", w, win_det[e]);
-        }
-        for (int e = f0; e < f1; ++e) {
-            if (win_fault[e] < 0 || win_fault[e] >= N) return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: fault %d is outside [0, %d)", w, win_fault[e], N);
-            if (e > f0 && win_fault[e] <= win_fault[e - 1])
-                return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the faults do not ascend strictly (at fault %d)", w, win_fault[e]);
-            if (win_commit[e] > 1) return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the commit flag of fault %d is %d, not 0 or 1", w, win_fault[e], win_commit[e]);
-        }
+        for (int e = f0; e < f1; ++e)
+            if (win_commit[e] > 1) return engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the commit flag of fault %d is %d, not 0 or 1", w, win_fault[e], win_commit[e]);
         StepPlan& commit = win->steps[(size_t)w + 1];
         commit.decoded_cols = nf;
         for (int e = f0; e < f1; ++e) {
             if (!win_commit[e]) continue;
             const int f = win_fault[e];
-            if (committed_by[f] >= 0) return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: fault %d was committed by window %d already", w, f, committed_by[f]);
+            if (committed_by[f] >= 0) return engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: fault %d was committed by window %d already", w, f, committed_by[f]);
             committed_by[f] = w;
             commit.pos.push_back(e - f0);
             commit.fault.push_back(f);
@@ -349,12 +289,12 @@ int bposd_window_create(const bposd_window_config* cfg, int32_t M, int32_t N, in
         win->steps[w].gather.assign(win_det + d0, win_det + d1);
 
         const bposd_handle* const dec = decs[w];
-        if (!dec) return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the decoder is NULL", w);
+        if (!dec) return engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the decoder is NULL", w);
         if (dec->device != cfg->device)
-            return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the decoder lives on device %d, the engine on device %d", w, dec->device, cfg->device);
+            return engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: the decoder lives on device %d, the engine on device %d", w, dec->device, cfg->device);
         win->packed[w] = native_packed(dec) ? 1 : 0;
         if (dec->m != nd || dec->n != nf)
-            return win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: decoder shape %d x %d does not match the window's %d detectors x %d faults", w, dec->m, dec->n, nd, nf);
+            return engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: decoder shape %d x %d does not match the window's %d detectors x %d faults", w, dec->m, dec->n, nd, nf);
         // the decoder's matrix must be H[D_w][:, F_w]: rows and lists ascend, so the positions of a row ascend too
         for (int e = f0; e < f1; ++e) pos_of[win_fault[e]] = e - f0;
         bool same = true;
@@ -364,7 +304,7 @@ int bposd_window_create(const bposd_window_config* cfg, int32_t M, int32_t N, in
             for (int e = h_indptr[d]; e < h_indptr[d + 1]; ++e)
                 if (pos_of[h_indices[e]] >= 0) row.push_back(pos_of[h_indices[e]]);
             same = (int)row.size() == dec->rp[i + 1] - dec->rp[i] && std::equal(row.begin(), row.end(), dec->ci.begin() + dec->rp[i]);
-            if (!same) win_fail(nullptr, BPOSD_ERR_INVALID, "window %d: row %d of the decoder's matrix is not detector %d of H restricted to the window's faults", w, i, d);
+            if (!same) engine_fail(nullptr, BPOSD_ERR_INVALID, "window %d: row %d of the decoder's matrix is not detector %d of H restricted to the window's faults", w, i, d);
         }
         for (int e = f0; e < f1; ++e) pos_of[win_fault[e]] = -1;
         if (!same) return BPOSD_ERR_INVALID;
@@ -373,16 +313,11 @@ int bposd_window_create(const bposd_window_config* cfg, int32_t M, int32_t N, in
         StepPlan& sp = win->steps[s];
         sp.finish(col_ptr, col_bits, win->dw);
         if (step_lds(sp, win->ow) > 64 * 1024)
-            return win_fail(nullptr, BPOSD_ERR_UNSUPPORTED, "step %d (commit of window %d, gather of window %d) stages %d detector words, %d observable words and %zu correction "
+            return engine_fail(nullptr, BPOSD_ERR_UNSUPPORTED, "step %d (commit of window %d, gather of window %d) stages %d detector words, %d observable words and %zu correction "
                             "words: %zu bytes of LDS per workgroup, more than 65536", s, s - 1, s, sp.w_hi - sp.w_lo, win->ow, sp.corr_words.size(), step_lds(sp, win->ow));
     }
     win->num_cu = decs[0]->num_cu > 0 ? decs[0]->num_cu : 256;
-    int rc;
-    {
-        DeviceGuard guard(cfg->device);
-        rc = guard.err != hipSuccess ? win_fail(win, BPOSD_ERR_HIP, "hipSetDevice(%d) failed", cfg->device) : create_device(win, col_ptr, col_bits);
-    }
-    if (rc) return win_fail(nullptr, rc, "%s", win->err.c_str());
+    if (const int rc = engine_create_on_device(win, [&] { return create_device(win, col_ptr, col_bits); })) return rc;
     *out = owner.release();
     return BPOSD_OK;
 }
@@ -390,10 +325,10 @@ int bposd_window_create(const bposd_window_config* cfg, int32_t M, int32_t N, in
 int bposd_window_decode_device(bposd_window* win, const uint64_t* d_detector_words, int64_t B, uint64_t* d_obs_words, uint64_t* d_correction_words,
                                uint64_t* d_residual_words, uint8_t* d_conv, int32_t* d_iters) {
     if (!win) return BPOSD_ERR_INVALID;
-    if (!d_detector_words || !d_obs_words) return win_fail(win, BPOSD_ERR_INVALID, "detector and observable buffers are required");
-    if (const int rc = check_batch(win, B)) return rc;
-    DeviceGuard guard(win->cfg.device);
-    WIN_TRY(win, guard.err);
+    if (!d_detector_words || !d_obs_words) return engine_fail(win, BPOSD_ERR_INVALID, "detector and observable buffers are required");
+    if (const int rc = engine_check_batch(win, B)) return rc;
+    DeviceGuard guard(win->device);
+    ENGINE_TRY(win, guard.err);
     win->run_B = 0;
     Rows r{};
     r.running = d_residual_words ? (unsigned long long*)d_residual_words : (unsigned long long*)win->d_running;
@@ -401,61 +336,60 @@ int bposd_window_decode_device(bposd_window* win, const uint64_t* d_detector_wor
     r.corr = (unsigned long long*)d_correction_words;
     r.conv = d_conv ? d_conv : (uint8_t*)win->d_conv_all;
     r.iters = d_iters ? d_iters : (int*)win->d_iters;
-    WIN_TRY(win, hipMemcpyAsync(r.running, d_detector_words, 8 * (size_t)B * win->dw, hipMemcpyDeviceToDevice, win->stream));
+    ENGINE_TRY(win, hipMemcpyAsync(r.running, d_detector_words, 8 * (size_t)B * win->dw, hipMemcpyDeviceToDevice, win->stream));
     return enqueue_windows(win, B, r);
 }
 
 int bposd_window_synchronize(bposd_window* win) {
     if (!win) return BPOSD_ERR_INVALID;
-    DeviceGuard guard(win->cfg.device);
-    WIN_TRY(win, guard.err);
-    WIN_TRY(win, hipStreamSynchronize(win->stream));
+    DeviceGuard guard(win->device);
+    ENGINE_TRY(win, guard.err);
+    ENGINE_TRY(win, hipStreamSynchronize(win->stream));
     return BPOSD_OK;
 }
 
 int bposd_window_decode(bposd_window* win, const uint64_t* detector_words, int64_t B, uint64_t* obs_words, uint64_t* correction_words,
                         uint64_t* residual_words, uint8_t* conv, int32_t* iters) {
     if (!win) return BPOSD_ERR_INVALID;
-    if (B < 0 || B > 0x7fffffffLL) return win_fail(win, BPOSD_ERR_INVALID, "batch size %lld out of range", (long long)B);
-    if (B > 0 && (!detector_words || !obs_words)) return win_fail(win, BPOSD_ERR_INVALID, "detector and observable buffers are required");
-    DeviceGuard guard(win->cfg.device);
-    WIN_TRY(win, guard.err);
+    if (B < 0 || B > 0x7fffffffLL) return engine_fail(win, BPOSD_ERR_INVALID, "batch size %lld out of range", (long long)B);
+    if (B > 0 && (!detector_words || !obs_words)) return engine_fail(win, BPOSD_ERR_INVALID, "detector and observable buffers are required");
+    DeviceGuard guard(win->device);
+    ENGINE_TRY(win, guard.err);
     win->run_B = 0;
     hipStream_t st = win->stream;
     const size_t dw = win->dw, ow = win->ow, fw = win->fw;
     for (int64_t lo = 0; lo < B; lo += win->capacity) {
         const size_t cnt = (size_t)std::min<int64_t>(win->capacity, B - lo);
         Rows r{win->d_running, win->d_obs, correction_words ? (unsigned long long*)win->d_corr : nullptr, win->d_conv_all, win->d_iters};
-        WIN_TRY(win, hipMemcpyAsync(r.running, detector_words + (size_t)lo * dw, 8 * cnt * dw, hipMemcpyHostToDevice, st));
+        ENGINE_TRY(win, hipMemcpyAsync(r.running, detector_words + (size_t)lo * dw, 8 * cnt * dw, hipMemcpyHostToDevice, st));
         if (const int rc = enqueue_windows(win, (long long)cnt, r)) return rc;
-        WIN_TRY(win, hipMemcpyAsync(obs_words + (size_t)lo * ow, r.obs, 8 * cnt * ow, hipMemcpyDeviceToHost, st));
-        if (correction_words) WIN_TRY(win, hipMemcpyAsync(correction_words + (size_t)lo * fw, r.corr, 8 * cnt * fw, hipMemcpyDeviceToHost, st));
-        if (residual_words) WIN_TRY(win, hipMemcpyAsync(residual_words + (size_t)lo * dw, r.running, 8 * cnt * dw, hipMemcpyDeviceToHost, st));
-        if (conv) WIN_TRY(win, hipMemcpyAsync(conv + lo, r.conv, cnt, hipMemcpyDeviceToHost, st));
-        if (iters) WIN_TRY(win, hipMemcpyAsync(iters + lo, r.iters, sizeof(int) * cnt, hipMemcpyDeviceToHost, st));
-        WIN_TRY(win, hipStreamSynchronize(st));  // the next chunk reuses the engine's rows
+        ENGINE_TRY(win, hipMemcpyAsync(obs_words + (size_t)lo * ow, r.obs, 8 * cnt * ow, hipMemcpyDeviceToHost, st));
+        if (correction_words) ENGINE_TRY(win, hipMemcpyAsync(correction_words + (size_t)lo * fw, r.corr, 8 * cnt * fw, hipMemcpyDeviceToHost, st));
+        if (residual_words) ENGINE_TRY(win, hipMemcpyAsync(residual_words + (size_t)lo * dw, r.running, 8 * cnt * dw, hipMemcpyDeviceToHost, st));
+        if (conv) ENGINE_TRY(win, hipMemcpyAsync(conv + lo, r.conv, cnt, hipMemcpyDeviceToHost, st));
+        if (iters) ENGINE_TRY(win, hipMemcpyAsync(iters + lo, r.iters, sizeof(int) * cnt, hipMemcpyDeviceToHost, st));
+        ENGINE_TRY(win, hipStreamSynchronize(st));  // the next chunk reuses the engine's rows
     }
     return BPOSD_OK;
 }
 
 int bposd_window_run(bposd_window* win, bposd_dem* sampler, uint64_t first_shot, int64_t B, int64_t counters[4]) {
     if (!win) return BPOSD_ERR_INVALID;
-    if (!sampler || !counters) return win_fail(win, BPOSD_ERR_INVALID, "sampler and counters are required");
-    if (sampler->dec) return win_fail(win, BPOSD_ERR_INVALID, "the sampler must be a sample-only engine (created without a decoder)");
-    if (sampler->M != win->M || sampler->N != win->N || sampler->k != win->k || sampler->cfg.device != win->cfg.device)
-        return win_fail(win, BPOSD_ERR_INVALID, "the sampler's model (%d x %d, k = %d, device %d) is not the engine's (%d x %d, k = %d, device %d)", sampler->M,
-                        sampler->N, sampler->k, sampler->cfg.device, win->M, win->N, win->k, win->cfg.device);
-    if (const int rc = check_batch(win, B)) return rc;
-    DeviceGuard guard(win->cfg.device);
-    WIN_TRY(win, guard.err);
+    if (!sampler || !counters) return engine_fail(win, BPOSD_ERR_INVALID, "sampler and counters are required");
+    if (sampler->dec) return engine_fail(win, BPOSD_ERR_INVALID, "the sampler must be a sample-only engine (created without a decoder)");
+    if (sampler->M != win->M || sampler->N != win->N || sampler->k != win->k || sampler->device != win->device)
+        return engine_fail(win, BPOSD_ERR_INVALID, "the sampler's model (%d x %d, k = %d, device %d) is not the engine's (%d x %d, k = %d, device %d)", sampler->M,
+                        sampler->N, sampler->k, sampler->device, win->M, win->N, win->k, win->device);
+    if (const int rc = engine_check_batch(win, B)) return rc;
+    DeviceGuard guard(win->device);
+    ENGINE_TRY(win, guard.err);
     win->run_B = 0;
     hipStream_t st = win->stream;
-    if (const int rc = bposd_host::dem_sample_async(sampler, first_shot, B, st)) return win_fail(win, rc, "sampler: %s", bposd_dem_last_error(sampler));
+    if (const int rc = bposd_host::dem_sample_async(sampler, first_shot, B, st)) return engine_fail(win, rc, "sampler: %s", bposd_dem_last_error(sampler));
     Rows r{win->d_running, win->d_obs, win->d_corr, win->d_conv_all, win->d_iters};
-    WIN_TRY(win, hipMemcpyAsync(r.running, sampler->d_detectors, 8 * (size_t)B * win->dw, hipMemcpyDeviceToDevice, st));
-    WIN_TRY(win, hipMemcpyAsync(win->d_truth, sampler->d_observables, 8 * (size_t)B * win->ow, hipMemcpyDeviceToDevice, st));
-    WIN_TRY(win, hipMemsetAsync(win->d_counters, 0, 8 * sizeof(int), st));
-    WIN_TRY(win, hipMemsetAsync(win->d_obs_fail, 0, sizeof(int) * (size_t)win->k, st));
+    ENGINE_TRY(win, hipMemcpyAsync(r.running, sampler->d_detectors, 8 * (size_t)B * win->dw, hipMemcpyDeviceToDevice, st));
+    ENGINE_TRY(win, hipMemcpyAsync(win->d_truth, sampler->d_observables, 8 * (size_t)B * win->ow, hipMemcpyDeviceToDevice, st));
+    ENGINE_TRY(win, win->counters.reset(st));
     int rc = enqueue_windows(win, B, r);
     if (rc) {
         (void)hipStreamSynchronize(st);
@@ -472,18 +406,17 @@ int bposd_window_run(bposd_window* win, bposd_dem* sampler, uint64_t first_shot,
     Q.decoded = r.obs;
     Q.conv_all = r.conv;
     Q.flags = win->d_flags;
-    Q.counters = win->d_counters;
-    Q.obs_fail = win->d_obs_fail;
+    Q.counters = win->counters.d_counters;
+    Q.obs_fail = win->counters.d_obs_fail;
     const unsigned grid = (unsigned)std::min<long long>((B + WIN_SCORE_THREADS - 1) / WIN_SCORE_THREADS, (long long)win->num_cu * 8);
     Event* const ev = &win->ev_t[2 * ((size_t)win->nwin + 1)];
-    WIN_TRY(win, hipEventRecord(ev[0], st));
+    ENGINE_TRY(win, hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(window_score_kernel, dim3(grid), dim3(WIN_SCORE_THREADS), 0, st, Q);
-    WIN_TRY(win, hipGetLastError());
-    WIN_TRY(win, hipEventRecord(ev[1], st));
-    WIN_TRY(win, hipMemcpyAsync(win->h_counters.p, win->d_counters, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-    WIN_TRY(win, hipMemcpyAsync(win->h_counters.as<int>() + 8, win->d_obs_fail, sizeof(int) * (size_t)win->k, hipMemcpyDeviceToHost, st));
-    WIN_TRY(win, hipStreamSynchronize(st));  // the batch's one host wait
-    for (int i = 0; i < 4; ++i) counters[i] = win->h_counters.as<int>()[i];
+    ENGINE_TRY(win, hipGetLastError());
+    ENGINE_TRY(win, hipEventRecord(ev[1], st));
+    ENGINE_TRY(win, win->counters.download(st, 4));
+    ENGINE_TRY(win, hipStreamSynchronize(st));  // the batch's one host wait
+    win->counters.read(counters, 4);
     win->timed_score = true;
     win->run_B = B;
     return BPOSD_OK;
@@ -491,47 +424,29 @@ int bposd_window_run(bposd_window* win, bposd_dem* sampler, uint64_t first_shot,
 
 int bposd_window_fetch(bposd_window* win, int32_t what, void* host_dst, size_t bytes) {
     if (!win) return BPOSD_ERR_INVALID;
-    if (!host_dst) return win_fail(win, BPOSD_ERR_INVALID, "destination is NULL");
-    if (what < BPOSD_WINDOW_OBS || what > BPOSD_WINDOW_OBS_FAIL)
-        return win_fail(win, BPOSD_ERR_INVALID, "what = %d is not one of BPOSD_WINDOW_OBS .. BPOSD_WINDOW_OBS_FAIL", what);
-    if (win->run_B == 0) return win_fail(win, BPOSD_ERR_INVALID, "no bposd_window_run has completed since the last decode call");
-    const void* src = nullptr;
-    size_t row = 0, rows = (size_t)win->run_B;
-    switch (what) {
-    case BPOSD_WINDOW_OBS: src = win->d_obs; row = 8 * (size_t)win->ow; break;
-    case BPOSD_WINDOW_OBSERVABLES: src = win->d_truth; row = 8 * (size_t)win->ow; break;
-    case BPOSD_WINDOW_CORRECTION: src = win->d_corr; row = 8 * (size_t)win->fw; break;
-    case BPOSD_WINDOW_RESIDUAL: src = win->d_running; row = 8 * (size_t)win->dw; break;
-    case BPOSD_WINDOW_FLAGS: src = win->d_flags; row = 1; break;
-    case BPOSD_WINDOW_CONVERGED: src = win->d_conv_all; row = 1; break;
-    case BPOSD_WINDOW_ITERS: src = win->d_iters; row = sizeof(int32_t); break;
-    default: src = win->d_obs_fail; row = sizeof(int32_t) * (size_t)win->k; rows = 1; break;  // BPOSD_WINDOW_OBS_FAIL: one row per batch
-    }
-    const size_t want = row * rows;
-    if (bytes != want) return win_fail(win, BPOSD_ERR_INVALID, "the last batch holds %zu bytes of item %d, not %zu", want, what, bytes);
-    if (what == BPOSD_WINDOW_OBS_FAIL) {  // came down with the counters: no device call
-        memcpy(host_dst, win->h_counters.as<int>() + 8, want);
-        return BPOSD_OK;
-    }
-    DeviceGuard guard(win->cfg.device);
-    WIN_TRY(win, guard.err);
-    WIN_TRY(win, hipMemcpy(host_dst, src, want, hipMemcpyDeviceToHost));  // bposd_window_run has waited for the batch
-    return BPOSD_OK;
+    if (win->run_B == 0) return engine_fail(win, BPOSD_ERR_INVALID, "no bposd_window_run has completed since the last decode call");
+    const size_t ow = 8 * (size_t)win->ow;
+    const FetchItem items[] = {{win->d_obs, ow, false},   {win->d_truth, ow, false},    {win->d_corr, 8 * (size_t)win->fw, false},
+                               {win->d_running, 8 * (size_t)win->dw, false},            {win->d_flags, 1, false},
+                               {win->d_conv_all, 1, false}, {win->d_iters, sizeof(int32_t), false},
+                               {nullptr, sizeof(int32_t) * (size_t)win->k, true}};
+    return engine_fetch(win, items, 8, BPOSD_WINDOW_OBS, "BPOSD_WINDOW_OBS .. BPOSD_WINDOW_OBS_FAIL", what, win->run_B, win->counters.obs_fail(), host_dst,
+                        bytes);
 }
 
 int64_t bposd_window_device_bytes(bposd_window* win) { return win ? (int64_t)win->device_bytes : BPOSD_ERR_INVALID; }
 
 int bposd_debug_window_timing(bposd_window* win, double* step_ms, double* score_ms) {
     if (!win) return BPOSD_ERR_INVALID;
-    if (!win->timed_steps) return win_fail(win, BPOSD_ERR_INVALID, "no batch has run yet");
-    DeviceGuard guard(win->cfg.device);
-    WIN_TRY(win, guard.err);
-    WIN_TRY(win, hipStreamSynchronize(win->stream));
+    if (!win->timed_steps) return engine_fail(win, BPOSD_ERR_INVALID, "no batch has run yet");
+    DeviceGuard guard(win->device);
+    ENGINE_TRY(win, guard.err);
+    ENGINE_TRY(win, hipStreamSynchronize(win->stream));
     float ms = 0.f;
     if (step_ms) {
         *step_ms = 0.0;
         for (int s = 0; s <= win->nwin; ++s) {
-            WIN_TRY(win, hipEventElapsedTime(&ms, win->ev_t[2 * s], win->ev_t[2 * s + 1]));
+            ENGINE_TRY(win, hipEventElapsedTime(&ms, win->ev_t[2 * s], win->ev_t[2 * s + 1]));
             *step_ms += ms;
         }
     }
@@ -539,7 +454,7 @@ int bposd_debug_window_timing(bposd_window* win, double* step_ms, double* score_
         *score_ms = 0.0;
         if (win->timed_score) {
             Event* const ev = &win->ev_t[2 * ((size_t)win->nwin + 1)];
-            WIN_TRY(win, hipEventElapsedTime(&ms, ev[0], ev[1]));
+            ENGINE_TRY(win, hipEventElapsedTime(&ms, ev[0], ev[1]));
             *score_ms = ms;
         }
     }
@@ -547,40 +462,42 @@ int bposd_debug_window_timing(bposd_window* win, double* step_ms, double* score_
 }
 
 int bposd_debug_window_step(bposd_window_step_args* a) {
-    if (!a) return win_fail(nullptr, BPOSD_ERR_INVALID, "args is NULL");
+    if (!a) return engine_fail(nullptr, BPOSD_ERR_INVALID, "args is NULL");
     const int M = a->M, N = a->N, k = a->k;
-    if (a->B < 1 || a->B > 0x7fffffffLL) return win_fail(nullptr, BPOSD_ERR_INVALID, "batch size %lld out of range", (long long)a->B);
-    if (a->n_commit < 0 || a->n_gather < 0 || a->decoded_cols < 0) return win_fail(nullptr, BPOSD_ERR_INVALID, "negative count");
-    if (!a->running || !a->observables || !a->conv_all || !a->iters) return win_fail(nullptr, BPOSD_ERR_INVALID, "running, observables, conv_all and iters are required");
-    if (a->n_commit > 0 && (!a->commit_pos || !a->commit_fault || !a->decoded)) return win_fail(nullptr, BPOSD_ERR_INVALID, "a commit needs its lists and the decoded rows");
-    if (a->n_gather > 0 && (!a->gather_det || !a->syndrome)) return win_fail(nullptr, BPOSD_ERR_INVALID, "a gather needs its list and the syndrome rows");
+    if (a->B < 1 || a->B > 0x7fffffffLL) return engine_fail(nullptr, BPOSD_ERR_INVALID, "batch size %lld out of range", (long long)a->B);
+    if (a->n_commit < 0 || a->n_gather < 0 || a->decoded_cols < 0) return engine_fail(nullptr, BPOSD_ERR_INVALID, "negative count");
+    if (!a->running || !a->observables || !a->conv_all || !a->iters) return engine_fail(nullptr, BPOSD_ERR_INVALID, "running, observables, conv_all and iters are required");
+    if (a->n_commit > 0 && (!a->commit_pos || !a->commit_fault || !a->decoded)) return engine_fail(nullptr, BPOSD_ERR_INVALID, "a commit needs its lists and the decoded rows");
+    if (a->n_gather > 0 && (!a->gather_det || !a->syndrome)) return engine_fail(nullptr, BPOSD_ERR_INVALID, "a gather needs its list and the syndrome rows");
+    std::string why;
     std::vector<int32_t> col_ptr, col_bits;
-    if (const int rc = stacked_csc(a->h_indptr, a->h_indices, M, a->l_indptr, a->l_indices, k, N, &col_ptr, &col_bits)) return rc;
+    if (const int rc = bposd_host::stacked_csc(a->h_indptr, a->h_indices, M, a->l_indptr, a->l_indices, k, N, &col_ptr, &col_bits, &why))
+        return engine_fail(nullptr, rc, "%s", why.c_str());
     StepPlan sp;
     sp.decoded_cols = a->decoded_cols;
     for (int c = 0; c < a->n_commit; ++c) {
         const int j = a->commit_pos[c], f = a->commit_fault[c];
         if (j < 0 || j >= a->decoded_cols || f < 0 || f >= N || (c > 0 && (j <= a->commit_pos[c - 1] || f <= a->commit_fault[c - 1])))
-            return win_fail(nullptr, BPOSD_ERR_INVALID, "commit entry %d (position %d, fault %d) is out of range or does not ascend", c, j, f);
+            return engine_fail(nullptr, BPOSD_ERR_INVALID, "commit entry %d (position %d, fault %d) is out of range or does not ascend", c, j, f);
         sp.pos.push_back(j);
         sp.fault.push_back(f);
     }
     for (int r = 0; r < a->n_gather; ++r) {
         const int d = a->gather_det[r];
-        if (d < 0 || d >= M || (r > 0 && d <= a->gather_det[r - 1])) return win_fail(nullptr, BPOSD_ERR_INVALID, "gather entry %d (detector %d) is out of range or does not ascend", r, d);
+        if (d < 0 || d >= M || (r > 0 && d <= a->gather_det[r - 1])) return engine_fail(nullptr, BPOSD_ERR_INVALID, "gather entry %d (detector %d) is out of range or does not ascend", r, d);
         sp.gather.push_back(d);
     }
     const int dw = (M + 63) / 64, ow = (k + 63) / 64, fw = (N + 63) / 64;
     sp.finish(col_ptr, col_bits, dw);
     a->word_range[0] = sp.w_lo;
     a->word_range[1] = sp.w_hi;
-    if (step_lds(sp, ow) > 64 * 1024) return win_fail(nullptr, BPOSD_ERR_UNSUPPORTED, "the step needs %zu bytes of LDS per workgroup, more than 65536", step_lds(sp, ow));
+    if (step_lds(sp, ow) > 64 * 1024) return engine_fail(nullptr, BPOSD_ERR_UNSUPPORTED, "the step needs %zu bytes of LDS per workgroup, more than 65536", step_lds(sp, ow));
 
-    bposd_window* const none = nullptr;
+    EngineBase* const none = nullptr;
     DeviceGuard guard(a->device);
-    WIN_TRY(none, guard.err);
+    ENGINE_TRY(none, guard.err);
     hipDeviceProp_t prop;
-    WIN_TRY(none, hipGetDeviceProperties(&prop, a->device));
+    ENGINE_TRY(none, hipGetDeviceProperties(&prop, a->device));
     const int num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const size_t B = (size_t)a->B;
     DevArray<int> d_col_ptr, d_col_bits, d_pos, d_fault, d_slot, d_corr_words, d_gather, d_iters, d_piters;
@@ -588,9 +505,9 @@ int bposd_debug_window_step(bposd_window_step_args* a) {
     DevArray<uint8_t> d_conv, d_pconv;
     DevBuf d_dec, d_synd;
     int rc;
-    if ((rc = win_upload(none, d_col_ptr, col_ptr)) || (rc = win_upload(none, d_col_bits, col_bits)) || (rc = win_upload(none, d_pos, sp.pos)) ||
-        (rc = win_upload(none, d_fault, sp.fault)) || (rc = win_upload(none, d_slot, sp.slot)) || (rc = win_upload(none, d_corr_words, sp.corr_words)) ||
-        (rc = win_upload(none, d_gather, sp.gather)))
+    if ((rc = upload(nullptr, d_col_ptr, col_ptr)) || (rc = upload(nullptr, d_col_bits, col_bits)) || (rc = upload(nullptr, d_pos, sp.pos)) ||
+        (rc = upload(nullptr, d_fault, sp.fault)) || (rc = upload(nullptr, d_slot, sp.slot)) || (rc = upload(nullptr, d_corr_words, sp.corr_words)) ||
+        (rc = upload(nullptr, d_gather, sp.gather)))
         return rc;
     const size_t dec_bytes = B * row_bytes(a->decoded_cols, a->decoded_packed != 0), synd_bytes = B * row_bytes(a->n_gather, a->syndrome_packed != 0);
     struct Io { DevBuf* dev; void* host; size_t bytes; bool up, down; };
@@ -601,43 +518,22 @@ int bposd_debug_window_step(bposd_window_step_args* a) {
                      {&d_synd, a->syndrome, synd_bytes, false, true}};
     for (const Io& x : io) {
         if (!x.host || !x.bytes) continue;
-        if ((rc = win_alloc(none, *x.dev, x.bytes))) return rc;
-        if (x.up) WIN_TRY(none, hipMemcpy(x.dev->p, x.host, x.bytes, hipMemcpyHostToDevice));
+        if ((rc = engine_alloc_bytes(none, *x.dev, x.bytes))) return rc;
+        if (x.up) ENGINE_TRY(none, hipMemcpy(x.dev->p, x.host, x.bytes, hipMemcpyHostToDevice));
     }
-    WindowStepParams P{};
-    P.B = a->B;
-    P.dw = dw;
-    P.ow = ow;
-    P.fw = fw;
-    P.w_lo = sp.w_lo;
-    P.w_hi = sp.w_hi;
-    P.col_ptr = d_col_ptr;
-    P.col_bits = d_col_bits;
-    P.n_commit = a->n_commit;
-    P.n_corr = (int)sp.corr_words.size();
-    P.commit_pos = d_pos;
-    P.commit_fault = d_fault;
-    P.commit_slot = d_slot;
-    P.corr_words = d_corr_words;
+    const StepTables t{d_col_ptr, d_col_bits, d_pos, d_fault, d_slot, d_corr_words, d_gather};
+    WindowStepParams P = step_params(sp, a->B, dw, ow, fw, t, Rows{d_running, d_obs, d_corr, d_conv, d_iters});
     P.decoded = d_dec.p;
-    P.decoded_cols = a->decoded_cols;
     P.decoded_packed = a->decoded_packed != 0;
     P.prev_conv = d_pconv;
     P.prev_iters = d_piters;
-    P.n_gather = a->n_gather;
-    P.gather_det = d_gather;
     P.syndrome = d_synd.p;
     P.syndrome_packed = a->syndrome_packed != 0;
-    P.running = d_running;
-    P.observables = d_obs;
-    P.correction = d_corr;
-    P.conv_all = d_conv;
-    P.iters = d_iters;
     hipLaunchKernelGGL(window_step_kernel, dim3(step_grid(a->B, num_cu)), dim3(WIN_THREADS), step_lds(sp, ow), nullptr, P);
-    WIN_TRY(none, hipGetLastError());
-    WIN_TRY(none, hipDeviceSynchronize());
+    ENGINE_TRY(none, hipGetLastError());
+    ENGINE_TRY(none, hipDeviceSynchronize());
     for (const Io& x : io)
-        if (x.host && x.bytes && x.down) WIN_TRY(none, hipMemcpy(x.host, x.dev->p, x.bytes, hipMemcpyDeviceToHost));
+        if (x.host && x.bytes && x.down) ENGINE_TRY(none, hipMemcpy(x.host, x.dev->p, x.bytes, hipMemcpyDeviceToHost));
     return BPOSD_OK;
 }
 

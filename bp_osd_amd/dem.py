@@ -28,28 +28,10 @@ import math
 import numpy as np
 import scipy.sparse as sp
 
+from ._dem_base import DemSimBase, _gf2_csr, checked_model, create_dem
 from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
 
 __all__ = ["dem_decode_sim", "importance_table", "phenomenological_dem", "phenomenological_detector_times"]
-
-_COUNTS = ("bp_converge_count", "bp_success_count", "osd0_success_count", "osdw_success_count", "trivial_count")
-
-
-def _gf2_csr(a, what):
-    """scipy CSR over GF(2) with sorted indices and no stored zeros."""
-    if sp.issparse(a):
-        m = sp.csr_matrix(a).astype(np.int64)
-    else:
-        arr = np.asarray(a)
-        if arr.ndim != 2:
-            raise ValueError(f"{what} must be a 2-D array or scipy.sparse matrix")
-        m = sp.csr_matrix(arr.astype(np.int64) & 1)
-    m.sum_duplicates()
-    m.data %= 2
-    m.eliminate_zeros()
-    m.sort_indices()
-    return m.astype(np.uint8)
-
 
 def phenomenological_dem(h, l, rounds, p_data, p_meas):
     """``(H, L, priors)`` of the phenomenological noise model of a code with checks ``h`` (m x n) and logicals ``l`` (k x n)
@@ -136,7 +118,7 @@ def importance_table(priors, sample_priors):
     return incr, math.fsum(c_terms)
 
 
-class dem_decode_sim:
+class dem_decode_sim(DemSimBase):
     """See the module docstring.
 
     H, L, priors : the model (scipy sparse or dense 0/1 matrices of shapes (M, N) and (k, N); N floats in [0, 1])
@@ -166,27 +148,16 @@ class dem_decode_sim:
     as sampled, and ``osdw_observable_error_rates`` stays unweighted too (failures per sampled shot, not a rate under
     ``priors``).  ``last_batch("logw")`` is the int64 log-weight of every shot of the last batch."""
 
+    _COUNTS = ("bp_converge_count", "bp_success_count", "osd0_success_count", "osdw_success_count", "trivial_count")
+    _RATES = ("bp", "osd0", "osdw")
+
     def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=100, decoder_factory=None, run_sim=True,
                  sample_priors=None, sample_scale=None, **decoder_kwargs):
-        if engine not in ("native", "numpy"):
-            raise ValueError("engine must be 'native' or 'numpy'")
-        if engine == "native" and decoder_factory is not None:
-            raise ValueError("engine='native' drives the MI355X decoder through device pointers; decoder_factory must be None")
-        self._engine = engine
-        self._H, self._L = _gf2_csr(H, "H"), _gf2_csr(L, "L")
+        self._check_engine(engine, decoder_factory, "decoder")
+        self._H, self._L, self._priors = checked_model(H, L, priors)
         self.M, self.N = self._H.shape
         self.K = self._L.shape[0]
-        if self._L.shape[1] != self.N:
-            raise ValueError(f"L must have shape (k, {self.N}), not {self._L.shape}")
-        if not 1 <= self.K <= 4096:
-            raise ValueError(f"the number of observables k = {self.K} is outside 1 .. 4096")
-        p = np.ascontiguousarray(priors, dtype=np.float64)
-        if p.shape != (self.N,):
-            raise ValueError(f"priors must have length {self.N}, not {p.shape}")
-        bad = np.flatnonzero(~((p >= 0) & (p <= 1)))
-        if bad.size:
-            raise ValueError(f"the prior of fault {int(bad[0])} ({p[bad[0]]}) is not a probability")
-        self._priors = p
+        p = self._priors
         if sample_priors is not None and sample_scale is not None:
             raise ValueError("give sample_priors or sample_scale, not both")
         self.sample_scale = None
@@ -204,21 +175,7 @@ class dem_decode_sim:
             self._sample_priors = q
             self._wsum = dict.fromkeys(("w", "w2", "bp", "bp2", "osd0", "osd02", "osdw", "osdw2"), 0.0)
             self.weight_mean = self.effective_sample_fraction = 0.0
-        self._batch_size = int(batch_size)
-        if self._batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.target_runs = int(target_runs)
-        self.engine = engine
-        self.run_count = 0
-        for key in _COUNTS:
-            setattr(self, key, 0)
-        for key in ("bp", "osd0", "osdw"):
-            setattr(self, f"{key}_logical_error_rate", 0.0)
-            setattr(self, f"{key}_logical_error_rate_eb", 0.0)
-        self._obs_fail = np.zeros(self.K, np.int64)
-        self.osdw_observable_error_rates = np.zeros(self.K, np.float64)
-        self._last = None
+        self._init_run(batch_size, seed, target_runs)
         self._dem = None
         if engine == "native":
             from .decoder import BpOsdDecoder
@@ -232,22 +189,11 @@ class dem_decode_sim:
 
     # ------------------------------------------------------------------ the library's engine
     def _native_setup(self):
-        import ctypes as C
-
         from . import _lib
 
         lib = self._lib = _lib.load()
-        cfg = _lib.BposdDemConfig(device=int(self.decoder.device), seed=self.seed, capacity=self._batch_size)
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        keep = [i32(self._H.indptr), i32(self._H.indices), i32(self._L.indptr), i32(self._L.indices)]
-        dem = C.c_void_p()
-        rc = lib.bposd_dem_create(C.byref(cfg), self.decoder._h, keep[0].ctypes.data, keep[1].ctypes.data, self.M, keep[2].ctypes.data,
-                                  keep[3].ctypes.data, self.K, self.N, self._priors.ctypes.data, C.byref(dem))
-        if rc != 0:
-            _lib.check_dem(lib, None, rc)
-        self._dem = dem
+        dem = self._dem = create_dem(lib, self.decoder.device, self.seed, self._batch_size, self._H, self._L, self._priors, self.decoder._h)
         self.decoder._observables_installed(self.K)  # bposd_dem_create has set the decoder's table
-        self._last_B = 0
         if self._tilted:
             _lib.check_dem(lib, dem, lib.bposd_dem_set_sampling(dem, self._sample_priors.ctypes.data, self._incr.ctypes.data))
 
@@ -265,21 +211,13 @@ class dem_decode_sim:
 
     def device_bytes(self):
         """engine="native": bytes of device memory the engine holds for its batches (the decoder's workspaces are its own)."""
-        if self._dem is None:
-            raise RuntimeError("device_bytes needs engine='native'")
-        return int(self._lib.bposd_dem_device_bytes(self._dem))
+        return self._device_bytes(self._dem, "bposd_dem_device_bytes")
 
     def kernel_ms(self):
         """engine="native": (dem_sample_kernel, dem_score_kernel) durations of the last batch in ms (HIP events)."""
-        import ctypes as C
-
         from . import _lib
 
-        if self._dem is None:
-            raise RuntimeError("kernel_ms needs engine='native'")
-        a, b = C.c_double(), C.c_double()
-        _lib.check_dem(self._lib, self._dem, self._lib.bposd_debug_dem_timing(self._dem, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._kernel_ms(self._dem, "bposd_debug_dem_timing", _lib.check_dem)
 
     def __del__(self):
         dem, self._dem = getattr(self, "_dem", None), None
@@ -318,18 +256,6 @@ class dem_decode_sim:
             self._accumulate_weighted(flags, self._last["converged"], self._last["logw"])
 
     # ------------------------------------------------------------------ common
-    def _accumulate(self, B, counters, obs_fail):
-        self.run_count += B
-        for key, v in zip(_COUNTS, counters):
-            setattr(self, key, getattr(self, key) + v)
-        self._obs_fail += np.asarray(obs_fail, dtype=np.int64)
-        n = self.run_count
-        for key in ("osdw", "osd0", "bp"):  # css_decode_sim's formulas
-            ler = 1 - getattr(self, f"{key}_success_count") / n
-            setattr(self, f"{key}_logical_error_rate", ler)
-            setattr(self, f"{key}_logical_error_rate_eb", float(np.sqrt((1 - ler) * ler / n)))
-        self.osdw_observable_error_rates = self._obs_fail / n
-
     def _accumulate_weighted(self, flags, converged, logw):
         """The weighted sums of one batch (after ``_accumulate``, whose plain rates it replaces) from the batch's per-shot flags,
         convergence and integer log-weights: the same arithmetic on either engine."""
@@ -350,15 +276,6 @@ class dem_decode_sim:
         self.weight_mean = S["w"] / n
         self.effective_sample_fraction = S["w"] * S["w"] / (n * S["w2"])
 
-    def run_decode_sim(self):
-        while self.run_count < self.target_runs:
-            B = min(self._batch_size, self.target_runs - self.run_count)
-            if self._engine == "native":
-                self._run_batch_native(B)
-            else:
-                self._run_batch_numpy(B)
-        return self.output_dict()
-
     def last_batch(self, what):
         """One array of the last batch: "faults", "detectors", "observables" (the true ones), "obs_bp", "obs_osd0", "obs_osdw"
         (bit-packed rows, uint64 [B, ceil(./64)]: ``BpOsdDecoder.unpack_rows`` expands them), "flags" (uint8 [B]: bit 0 bp
@@ -371,30 +288,11 @@ class dem_decode_sim:
             raise ValueError(f"what must be one of {sorted(_lib.DEM_ITEMS)}")
         if what == "logw" and not self._tilted:
             raise ValueError("last_batch('logw') needs importance sampling (sample_priors or sample_scale)")
-        if self._engine == "numpy":
-            if self._last is None:
-                raise RuntimeError("last_batch needs a batch that has run")
-            return self._last[what]
-        if not self._last_B:
-            raise RuntimeError("last_batch needs a batch that has run")
-        item, dtype, cols = _lib.DEM_ITEMS[what]
-        B = self._last_B
-        width = {"N": self.N, "M": self.M, "k": self.K}
-        shape = (B,) if cols is None else (self.K,) if cols == "k32" else (B, (width[cols] + 63) // 64)
-        out = np.empty(shape, dtype=np.dtype(dtype))
-        _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_fetch(self._dem, item, out.ctypes.data, out.nbytes))
-        return out
+        return self._last_batch(what, lambda: self._fetch(_lib.DEM_ITEMS, self._dem, self._lib.bposd_dem_fetch, _lib.check_dem, what))
 
     def output_dict(self):
         """The counters and rates as a JSON string (as css_decode_sim.output_dict returns one)."""
-        out = {"N": self.N, "M": self.M, "K": self.K, "seed": self.seed, "engine": self.engine, "target_runs": self.target_runs,
-               "run_count": self.run_count}
-        for key in _COUNTS:
-            out[key] = int(getattr(self, key))
-        for key in ("bp", "osd0", "osdw"):
-            out[f"{key}_logical_error_rate"] = float(getattr(self, f"{key}_logical_error_rate"))
-            out[f"{key}_logical_error_rate_eb"] = float(getattr(self, f"{key}_logical_error_rate_eb"))
-        out["osdw_observable_error_rates"] = [float(v) for v in self.osdw_observable_error_rates]
+        out = self._results()
         if self._tilted:
             out["sample_scale"] = self.sample_scale
             out["weight_mean"] = float(self.weight_mean)

@@ -27,12 +27,12 @@ from types import SimpleNamespace
 import numpy as np
 import scipy.sparse as sp
 
-from .dem import _gf2_csr, _pack
+from ._dem_base import DemSimBase, _gf2_csr, checked_model, create_dem
+from .dem import _pack
 from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
 
 __all__ = ["window_plan", "WindowedDemDecoder", "windowed_dem_decode_sim"]
 
-_COUNTS = ("bp_converge_count", "osdw_success_count", "residual_count", "trivial_count")
 _ITEMS = ("faults", "detectors", "observables", "obs_osdw", "correction", "residual", "flags", "converged", "iters", "obs_fail")
 
 
@@ -130,21 +130,10 @@ class _Model:
     """The validated model and its plan: what both classes below start from."""
 
     def __init__(self, H, L, priors, detector_time, window):
-        self.H, self.L = _gf2_csr(H, "H"), _gf2_csr(L, "L")
+        self.H, self.L, self.priors = checked_model(H, L, priors)
         self.M, self.N = self.H.shape
         self.K = self.L.shape[0]
-        if self.L.shape[1] != self.N:
-            raise ValueError(f"L must have shape (k, {self.N}), not {self.L.shape}")
-        if not 1 <= self.K <= 4096:
-            raise ValueError(f"the number of observables k = {self.K} is outside 1 .. 4096")
-        p = np.ascontiguousarray(priors, dtype=np.float64)
-        if p.shape != (self.N,):
-            raise ValueError(f"priors must have length {self.N}, not {p.shape}")
-        bad = np.flatnonzero(~((p >= 0) & (p <= 1)))
-        if bad.size:
-            raise ValueError(f"the prior of fault {int(bad[0])} ({p[bad[0]]}) is not a probability")
-        self.priors = p
-        self.plan = window_plan(self.H, detector_time, window, priors=p)
+        self.plan = window_plan(self.H, detector_time, window, priors=self.priors)
         self.HT = self.H.T.tocsr()  # row i = column i of H
         self.LT = self.L.T.tocsr()
 
@@ -309,7 +298,7 @@ class WindowedDemDecoder:
         return a.value, b.value
 
 
-class windowed_dem_decode_sim:
+class windowed_dem_decode_sim(DemSimBase):
     """Monte-Carlo harness of the windowed decoder; see the module docstring.
 
     H, L, priors, detector_time, window : as ``WindowedDemDecoder`` takes them
@@ -325,30 +314,17 @@ class windowed_dem_decode_sim:
     ``osdw_logical_error_rate`` with ``osdw_logical_error_rate_eb``, ``osdw_observable_error_rates`` (float [k]),
     :meth:`last_batch` and :meth:`output_dict`."""
 
+    _COUNTS = ("bp_converge_count", "osdw_success_count", "residual_count", "trivial_count")
+    _RATES = ("osdw",)
+
     def __init__(self, H, L, priors, detector_time, window, batch_size=4096, engine="native", seed=0, target_runs=100,
                  decoder_factory=None, run_sim=True, **decoder_kwargs):
-        if engine not in ("native", "numpy"):
-            raise ValueError("engine must be 'native' or 'numpy'")
-        if engine == "native" and decoder_factory is not None:
-            raise ValueError("engine='native' drives the MI355X decoders through device pointers; decoder_factory must be None")
+        self._check_engine(engine, decoder_factory, "decoders")
         self._win = self._sampler = None
-        self._engine = self.engine = engine
         self._model = m = _Model(H, L, priors, detector_time, window)
         self.M, self.N, self.K = m.M, m.N, m.K
         self.plan = m.plan
-        self._batch_size = int(batch_size)
-        if self._batch_size < 1:
-            raise ValueError("batch_size must be >= 1")
-        self.seed = int(seed) & (2 ** 64 - 1)
-        self.target_runs = int(target_runs)
-        self.run_count = 0
-        for key in _COUNTS:
-            setattr(self, key, 0)
-        self.osdw_logical_error_rate = self.osdw_logical_error_rate_eb = 0.0
-        self._obs_fail = np.zeros(self.K, np.int64)
-        self.osdw_observable_error_rates = np.zeros(self.K, np.float64)
-        self._last = None
-        self._last_B = 0
+        self._init_run(batch_size, seed, target_runs)
         if engine == "native":
             from .decoder import BpOsdDecoder
 
@@ -361,23 +337,10 @@ class windowed_dem_decode_sim:
 
     # ------------------------------------------------------------------ the library's engine
     def _native_setup(self):
-        import ctypes as C
-
-        from . import _lib
-
         m = self._model
         device = int(self.decoders[0].device)
         self._lib, self._win = _native_engine(m, self.decoders, device, self._batch_size)
-        lib = self._lib
-        cfg = _lib.BposdDemConfig(device=device, seed=self.seed, capacity=self._batch_size)
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        keep = [i32(m.H.indptr), i32(m.H.indices), i32(m.L.indptr), i32(m.L.indices)]
-        dem = C.c_void_p()
-        rc = lib.bposd_dem_create(C.byref(cfg), None, keep[0].ctypes.data, keep[1].ctypes.data, m.M, keep[2].ctypes.data, keep[3].ctypes.data,
-                                  m.K, m.N, m.priors.ctypes.data, C.byref(dem))  # a sample-only engine
-        if rc != 0:
-            _lib.check_dem(lib, None, rc)
-        self._sampler = dem
+        self._sampler = create_dem(self._lib, device, self.seed, self._batch_size, m.H, m.L, m.priors, None)  # a sample-only engine
 
     def _run_batch_native(self, B):
         import ctypes as C
@@ -391,21 +354,13 @@ class windowed_dem_decode_sim:
 
     def device_bytes(self):
         """engine="native": bytes of device memory the window engine holds (sampler and decoders hold their own)."""
-        if self._win is None:
-            raise RuntimeError("device_bytes needs engine='native'")
-        return int(self._lib.bposd_window_device_bytes(self._win))
+        return self._device_bytes(self._win, "bposd_window_device_bytes")
 
     def kernel_ms(self):
         """engine="native": (sum of the window_step_kernel launches, window_score_kernel) of the last batch in ms."""
-        import ctypes as C
-
         from . import _lib
 
-        if self._win is None:
-            raise RuntimeError("kernel_ms needs engine='native'")
-        a, b = C.c_double(), C.c_double()
-        _lib.check_window(self._lib, self._win, self._lib.bposd_debug_window_timing(self._win, C.byref(a), C.byref(b)))
-        return a.value, b.value
+        return self._kernel_ms(self._win, "bposd_debug_window_timing", _lib.check_window)
 
     def __del__(self):
         win, self._win = getattr(self, "_win", None), None
@@ -433,26 +388,6 @@ class windowed_dem_decode_sim:
         self._accumulate(B, [int(conv.sum()), int((~wrong).sum()), int(dirty.sum()), int(quiet.sum())], obs_fail)
 
     # ------------------------------------------------------------------ common
-    def _accumulate(self, B, counters, obs_fail):
-        self.run_count += B
-        for key, v in zip(_COUNTS, counters):
-            setattr(self, key, getattr(self, key) + v)
-        self._obs_fail += np.asarray(obs_fail, dtype=np.int64)
-        n = self.run_count
-        ler = 1 - self.osdw_success_count / n
-        self.osdw_logical_error_rate = ler
-        self.osdw_logical_error_rate_eb = float(np.sqrt((1 - ler) * ler / n))
-        self.osdw_observable_error_rates = self._obs_fail / n
-
-    def run_decode_sim(self):
-        while self.run_count < self.target_runs:
-            B = min(self._batch_size, self.target_runs - self.run_count)
-            if self._engine == "native":
-                self._run_batch_native(B)
-            else:
-                self._run_batch_numpy(B)
-        return self.output_dict()
-
     def last_batch(self, what):
         """One array of the last batch: "faults", "detectors", "observables" (the true ones), "obs_osdw", "correction",
         "residual" (bit-packed rows, uint64 [B, ceil(./64)]), "flags" (uint8 [B]: bit 0 observables wrong, bit 1 residual not
@@ -462,34 +397,11 @@ class windowed_dem_decode_sim:
 
         if what not in _ITEMS:
             raise ValueError(f"what must be one of {sorted(_ITEMS)}")
-        if self._engine == "numpy":
-            if self._last is None:
-                raise RuntimeError("last_batch needs a batch that has run")
-            return self._last[what]
-        if not self._last_B:
-            raise RuntimeError("last_batch needs a batch that has run")
-        B = self._last_B
-        words = lambda c: (B, (c + 63) // 64)
         if what in ("faults", "detectors"):  # the sampler's own rows
-            item, dtype, cols = _lib.DEM_ITEMS[what]
-            out = np.empty(words(self.N if cols == "N" else self.M), dtype=np.dtype(dtype))
-            _lib.check_dem(self._lib, self._sampler, self._lib.bposd_dem_fetch(self._sampler, item, out.ctypes.data, out.nbytes))
-            return out
-        item, dtype, cols = _lib.WINDOW_ITEMS[what]
-        width = {"N": self.N, "M": self.M, "k": self.K}
-        shape = (B,) if cols is None else (self.K,) if cols == "k32" else words(width[cols])
-        out = np.empty(shape, dtype=np.dtype(dtype))
-        _lib.check_window(self._lib, self._win, self._lib.bposd_window_fetch(self._win, item, out.ctypes.data, out.nbytes))
-        return out
+            return self._last_batch(what, lambda: self._fetch(_lib.DEM_ITEMS, self._sampler, self._lib.bposd_dem_fetch, _lib.check_dem, what))
+        return self._last_batch(what, lambda: self._fetch(_lib.WINDOW_ITEMS, self._win, self._lib.bposd_window_fetch, _lib.check_window, what))
 
     def output_dict(self):
         """The counters and rates as a JSON string (as dem_decode_sim.output_dict returns one)."""
-        out = {"N": self.N, "M": self.M, "K": self.K, "T": self.plan.T, "window": [self.plan.W, self.plan.C], "windows": len(self.plan.windows),
-               "decoders": len(self.plan.unique), "seed": self.seed, "engine": self.engine, "target_runs": self.target_runs,
-               "run_count": self.run_count}
-        for key in _COUNTS:
-            out[key] = int(getattr(self, key))
-        out["osdw_logical_error_rate"] = float(self.osdw_logical_error_rate)
-        out["osdw_logical_error_rate_eb"] = float(self.osdw_logical_error_rate_eb)
-        out["osdw_observable_error_rates"] = [float(v) for v in self.osdw_observable_error_rates]
+        out = dict(self._results(), T=self.plan.T, window=[self.plan.W, self.plan.C], windows=len(self.plan.windows), decoders=len(self.plan.unique))
         return json.dumps(out, sort_keys=True, indent=4)

@@ -254,6 +254,44 @@ def test_engine_arguments_are_checked_by_the_library(gpu_ready, surface13, hgp40
     assert gpu_ready.bposd_mc_create(None, None, None, None, None, 0, None, None, 0, 0, None, None, 0, None, None, None, None, C.byref(mc)) \
         == _lib.BPOSD_ERR_INVALID
     assert not mc.value and gpu_ready.bposd_mc_last_error(None)
+    # the rows of hx need not be sorted (css_decode_sim sorts them, so bposd_mc_create is called directly): an engine whose hx
+    # has the column indices of one row reversed is accepted and gives the batch of the sorted one
+    import scipy.sparse as sp
+
+    def one_batch(reversed_row):
+        s = _native(surface13, 64, error_rate=0.1)
+        hx, hz = sp.csr_matrix(s.hx), sp.csr_matrix(s.hz)
+        hx.sort_indices()
+        hz.sort_indices()
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        hx_indices = i32(hx.indices).copy()
+        if reversed_row is not None:
+            lo, hi = hx.indptr[reversed_row], hx.indptr[reversed_row + 1]
+            assert hi - lo >= 2
+            hx_indices[lo:hi] = hx_indices[lo:hi][::-1].copy()
+            assert (np.diff(hx_indices[lo:hi]) < 0).all()
+        keep = [i32(hx.indptr), hx_indices, i32(hz.indptr), i32(hz.indices), BpOsdDecoder.pack_rows(np.asarray(s.lx, dtype=np.uint8) & 1),
+                BpOsdDecoder.pack_rows(np.asarray(s.lz, dtype=np.uint8) & 1), f64(s.channel_probs_x), f64(s.channel_probs_y), f64(s.channel_probs_z)]
+        ptr = [a.ctypes.data for a in keep]
+        cfg = _lib.BposdMcConfig(device=int(s.bpd_x.device), channel_update=_lib.MC_UPDATE[None], seed=5, capacity=64)
+        eng = C.c_void_p()
+        rc = gpu_ready.bposd_mc_create(C.byref(cfg), s.bpd_x._h, s.bpd_z._h, ptr[0], ptr[1], hx.shape[0], ptr[2], ptr[3], hz.shape[0], s.N, ptr[4],
+                                       ptr[5], int(np.asarray(s.lx).shape[0]), ptr[6], ptr[7], ptr[8], None, C.byref(eng))
+        assert rc == 0 and eng.value, gpu_ready.bposd_mc_last_error(None)
+        try:
+            c = (C.c_int64 * 7)()
+            assert gpu_ready.bposd_mc_run(eng, 0, 64, c) == 0, gpu_ready.bposd_mc_last_error(eng)
+            flags = np.empty(64, np.uint8)
+            assert gpu_ready.bposd_mc_fetch(eng, _lib.MC_ITEMS["flags"], flags.ctypes.data, flags.nbytes) == 0
+        finally:
+            gpu_ready.bposd_mc_destroy(eng)
+        return [int(v) for v in c], flags
+
+    (want_counters, want_flags), (got_counters, got_flags) = one_batch(None), one_batch(0)
+    assert got_counters == want_counters and (got_flags == want_flags).all()
+    assert (want_flags == sim.last_batch("flags")).all()  # (and the sorted one is css_decode_sim's own engine: seed 5, shots 0 .. 63)
+    assert want_counters[:5] == [getattr(sim, k) for k in COUNTS]
 
 
 def test_engine_create_destroy_cycles_release_device_memory(gpu_ready, hgp400):
