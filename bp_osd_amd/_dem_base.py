@@ -1,7 +1,9 @@
 """What the two detector-error-model harnesses share (``dem.dem_decode_sim`` and ``window.windowed_dem_decode_sim``): the
 model's validation, the run loop over batches, the counters and rates of a run, and the native engine's plumbing (creating a
-``bposd_dem``, fetching an item of the last batch, device bytes and kernel times).  A harness keeps its constructor, its two
-``_run_batch_*`` and what is its own in ``last_batch`` and ``output_dict``."""
+``bposd_dem``, fetching an item of the last batch, device bytes and kernel times), and the harvest of failing shots: its host
+restatement (``harvest_batch``), which is the definition the device kernels are held against, and what a run accumulates
+from it.  A harness keeps its constructor, its two ``_run_batch_*`` and what is its own in ``last_batch`` and
+``output_dict``."""
 from __future__ import annotations
 
 import numpy as np
@@ -22,6 +24,41 @@ def _gf2_csr(a, what):
     m.eliminate_zeros()
     m.sort_indices()
     return m.astype(np.uint8)
+
+
+def _pack(rows):
+    """uint8 0/1 rows [B, c] -> uint64 [B, ceil(c/64)] (the C-ABI's packed form)."""
+    a = np.ascontiguousarray(rows, dtype=np.uint8)
+    by = np.packbits(a, axis=1, bitorder="little")
+    out = np.zeros((a.shape[0], 8 * ((a.shape[1] + 63) // 64)), np.uint8)
+    out[:, :by.shape[1]] = by
+    return out.view("<u8")
+
+
+HARVEST_ITEMS = ("fail_rows", "fail_weight", "fail_residual", "fail_faults", "min_residual")
+
+
+def harvest_batch(faults, correction, select, max_rows):
+    """The harvest of one batch on the host -- the definition the device is held against bit for bit.
+
+    ``faults`` and ``correction`` are uint8 0/1 rows [B, N] (of the correction bit 0 counts), ``select`` [B] marks the failing
+    shots and ``max_rows`` = K >= 0 caps the rows kept.  With F the selected rows in ascending order and
+    ``r_b = faults[b] ^ correction[b]``: ``fail_count`` = |F|, ``fail_rows`` int32 [|F|], ``fail_weight`` int32 [|F|] (the
+    weight of r_b for all of F), ``fail_residual`` and ``fail_faults`` uint64 [min(|F|, K), ceil(N/64)] (packed, of the first
+    rows of F), ``min_weight`` and ``min_row`` (the least weight over all of F and the lowest row that has it; -1, -1 for an
+    empty F) and ``min_residual`` uint64 [ceil(N/64)] (zeros for an empty F)."""
+    f = np.asarray(faults, dtype=np.uint8) & 1
+    c = np.asarray(correction, dtype=np.uint8) & 1
+    rows = np.flatnonzero(np.asarray(select)).astype(np.int32)
+    r = f[rows] ^ c[rows]
+    weight = r.sum(axis=1, dtype=np.int64).astype(np.int32)
+    keep = min(rows.size, int(max_rows))
+    out = {"fail_count": int(rows.size), "fail_rows": rows, "fail_weight": weight, "fail_residual": _pack(r[:keep]),
+           "fail_faults": _pack(f[rows[:keep]]), "min_weight": -1, "min_row": -1, "min_residual": np.zeros((f.shape[1] + 63) // 64, "<u8")}
+    if rows.size:
+        i = int(np.argmin(weight))  # the first of the least: rows ascend, so the lowest row
+        out.update(min_weight=int(weight[i]), min_row=int(rows[i]), min_residual=_pack(r[i:i + 1])[0])
+    return out
 
 
 def checked_model(H, L, priors):
@@ -90,6 +127,67 @@ class DemSimBase:
         self._last = None  # engine="numpy": the items of the last batch
         self._last_B = 0   # engine="native": its size
 
+    # ------------------------------------------------------------------ the harvest of failing shots
+    def _init_harvest(self, harvest, with_logw=False):
+        """``harvest=K``: an int >= 0.  Sets the results of a harvest (all None while it is off)."""
+        if isinstance(harvest, bool) or not isinstance(harvest, (int, np.integer)) or harvest < 0:
+            raise ValueError(f"harvest must be an int >= 0 (the failing shots to keep; 0: off), not {harvest!r}")
+        self.harvest = int(harvest)
+        self.min_logical_weight = self.min_logical_shot = self.min_logical_fault = None
+        self.failure_weight_counts = self.failures = None
+        self._last_info = None  # (fail_count, min_weight, min_row, rows asked for) of the last batch
+        if self.harvest:
+            fw = (self.N + 63) // 64
+            self.failure_weight_counts = np.zeros(self.N + 1, np.int64)
+            self.failures = {"shot": np.zeros(0, np.uint64), "weight": np.zeros(0, np.int32), "residual": np.zeros((0, fw), "<u8"),
+                             "faults": np.zeros((0, fw), "<u8")}
+            if with_logw:
+                self.failures["logw"] = np.zeros(0, np.int64)
+
+    def _harvest_ask(self):
+        """Rows the next batch is asked to keep: the ones still missing of the run's first K (an engine that is on keeps one)."""
+        return max(1, self.harvest - self.failures["shot"].size)
+
+    def _set_native_harvest(self, handle, set_fn, check, rows):
+        """bposd_*_set_harvest in front of a batch: the engine keeps ``rows`` rows of it."""
+        check(self._lib, handle, getattr(self._lib, set_fn)(handle, int(rows)))
+
+    def _native_harvest_triple(self, handle, info_fn, check):
+        """bposd_*_harvest_info of the batch that ran: [fail_count, min_weight, min_row]."""
+        import ctypes as C
+
+        t = (C.c_int64 * 3)()
+        check(self._lib, handle, getattr(self._lib, info_fn)(handle, t))
+        return [int(v) for v in t]
+
+    def _accumulate_harvest(self, first_shot, info, ask, logw=None):
+        """One batch's harvest into the run's: ``info`` = (fail_count, min_weight, min_row); the items come from
+        ``last_batch``, so both engines take the same path."""
+        count, min_w, min_row = info
+        self._last_info = (count, min_w, min_row, ask)
+        if not count:
+            return
+        rows, weight = self.last_batch("fail_rows"), self.last_batch("fail_weight")
+        self.failure_weight_counts += np.bincount(weight, minlength=self.N + 1)
+        F = self.failures
+        take = min(self.harvest - F["shot"].size, count)
+        if take > 0:
+            sel = rows[:take]
+            F["shot"] = np.concatenate([F["shot"], (np.uint64(first_shot) + sel.astype(np.uint64))])
+            F["weight"] = np.concatenate([F["weight"], weight[:take]])
+            F["residual"] = np.concatenate([F["residual"], self.last_batch("fail_residual")[:take]])
+            F["faults"] = np.concatenate([F["faults"], self.last_batch("fail_faults")[:take]])
+            if logw is not None:
+                F["logw"] = np.concatenate([F["logw"], np.asarray(logw, dtype=np.int64)[sel]])
+        if self.min_logical_weight is None or min_w < self.min_logical_weight:  # (a tie stays with the earlier shot)
+            self.min_logical_weight, self.min_logical_shot = int(min_w), int(first_shot) + int(min_row)
+            words = np.ascontiguousarray(self.last_batch("min_residual")).reshape(1, -1)
+            self.min_logical_fault = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[0, :self.N].copy()
+
+    def _check_harvest_item(self, what):
+        if what in HARVEST_ITEMS and not self.harvest:
+            raise ValueError(f"last_batch({what!r}) needs harvest=K > 0")
+
     def run_decode_sim(self):
         while self.run_count < self.target_runs:
             B = min(self._batch_size, self.target_runs - self.run_count)
@@ -153,7 +251,16 @@ class DemSimBase:
         item, dtype, cols = items[what]
         B = self._last_B
         width = {"N": self.N, "M": self.M, "k": self.K}
-        shape = (B,) if cols is None else (self.K,) if cols == "k32" else (B, (width[cols] + 63) // 64)
+        if cols in ("F", "FN", "1N"):  # of a harvest: sized by the batch's failures
+            if self._last_info is None:
+                raise RuntimeError(f"last_batch({what!r}) needs a batch that ran with the harvest on")
+            count, _, _, ask = self._last_info
+            fw = (self.N + 63) // 64
+            shape = (count,) if cols == "F" else (min(count, ask), fw) if cols == "FN" else (fw,)
+        else:
+            shape = (B,) if cols is None else (self.K,) if cols == "k32" else (B, (width[cols] + 63) // 64)
         out = np.empty(shape, dtype=np.dtype(dtype))
+        if out.nbytes == 0:
+            return out
         check_fn(self._lib, handle, fetch_fn(handle, item, out.ctypes.data, out.nbytes))
         return out

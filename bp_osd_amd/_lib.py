@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "bposd_dem_tables",
     "bposd_dem_create",
     "bposd_dem_set_sampling",
+    "bposd_dem_set_harvest",
+    "bposd_dem_harvest_info",
     "bposd_dem_sample",
     "bposd_dem_run",
     "bposd_dem_fetch",
@@ -78,6 +80,8 @@ EXPORTED_SYMBOLS = (
     "bposd_window_synchronize",
     "bposd_window_decode",
     "bposd_window_run",
+    "bposd_window_set_harvest",
+    "bposd_window_harvest_info",
     "bposd_window_fetch",
     "bposd_window_device_bytes",
     "bposd_window_last_error",
@@ -96,6 +100,8 @@ DEBUG_SYMBOLS = (
     "bposd_debug_last_pair_key",
     "bposd_debug_obs_timing",
     "bposd_debug_dem_timing",
+    "bposd_debug_dem_harvest",
+    "bposd_debug_dem_harvest_timing",
     "bposd_debug_window_step",
     "bposd_debug_window_timing",
     "bposd_debug_class_layout",
@@ -180,13 +186,18 @@ class BposdWindowStep(C.Structure):
 
 # bposd_window_fetch(what): item -> (number, dtype, columns) in the notation of DEM_ITEMS
 WINDOW_ITEMS = {"obs_osdw": (0, "<u8", "k"), "observables": (1, "<u8", "k"), "correction": (2, "<u8", "N"), "residual": (3, "<u8", "M"),
-                "flags": (4, "u1", None), "converged": (5, "u1", None), "iters": (6, "<i4", None), "obs_fail": (7, "<i4", "k32")}
+                "flags": (4, "u1", None), "converged": (5, "u1", None), "iters": (6, "<i4", None), "obs_fail": (7, "<i4", "k32"),
+                "fail_rows": (8, "<i4", "F"), "fail_weight": (9, "<i4", "F"), "fail_residual": (10, "<u8", "FN"),
+                "fail_faults": (11, "<u8", "FN"), "min_residual": (12, "<u8", "1N")}
 
 
-# bposd_dem_fetch(what): item -> (number, dtype, columns: "N" / "M" / "k" packed into words, "k32" = k int32 in one row, None = [B])
+# bposd_dem_fetch(what): item -> (number, dtype, columns: "N" / "M" / "k" packed into words, "k32" = k int32 in one row, None = [B];
+# of a harvest: "F" = one per failing shot, "FN" = packed fault-space rows of the first min(F, K) failing shots, "1N" = one such row)
 DEM_ITEMS = {"faults": (0, "<u8", "N"), "detectors": (1, "<u8", "M"), "observables": (2, "<u8", "k"), "obs_bp": (3, "<u8", "k"),
              "obs_osd0": (4, "<u8", "k"), "obs_osdw": (5, "<u8", "k"), "flags": (6, "u1", None), "converged": (7, "u1", None),
-             "iters": (8, "<i4", None), "obs_fail": (9, "<i4", "k32"), "logw": (10, "<i8", None)}
+             "iters": (8, "<i4", None), "obs_fail": (9, "<i4", "k32"), "logw": (10, "<i8", None),
+             "fail_rows": (11, "<i4", "F"), "fail_weight": (12, "<i4", "F"), "fail_residual": (13, "<u8", "FN"),
+             "fail_faults": (14, "<u8", "FN"), "min_residual": (15, "<u8", "1N")}
 
 
 # bposd_mc_config.channel_update / bposd_mc_fetch(what)
@@ -331,6 +342,18 @@ def load():
     lib.bposd_dem_create.restype = C.c_int
     lib.bposd_dem_set_sampling.argtypes = [vp, vp, vp]
     lib.bposd_dem_set_sampling.restype = C.c_int
+    lib.bposd_dem_set_harvest.argtypes = [vp, C.c_int64]
+    lib.bposd_dem_set_harvest.restype = C.c_int
+    lib.bposd_dem_harvest_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.bposd_dem_harvest_info.restype = C.c_int
+    lib.bposd_debug_dem_harvest.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int64]
+    lib.bposd_debug_dem_harvest.restype = C.c_int
+    lib.bposd_debug_dem_harvest_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.bposd_debug_dem_harvest_timing.restype = C.c_int
+    lib.bposd_window_set_harvest.argtypes = [vp, C.c_int64]
+    lib.bposd_window_set_harvest.restype = C.c_int
+    lib.bposd_window_harvest_info.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.bposd_window_harvest_info.restype = C.c_int
     lib.bposd_dem_sample.argtypes = [vp, C.c_uint64, C.c_int64]
     lib.bposd_dem_sample.restype = C.c_int
     lib.bposd_dem_run.argtypes = [vp, C.c_uint64, C.c_int64, C.POINTER(C.c_int64)]

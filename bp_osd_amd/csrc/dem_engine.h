@@ -1,7 +1,7 @@
 // dem_engine.h -- the state of a detector-error-model engine (bposd_dem of include/bposd_mi355x.h), shared by launch_dem.hip,
 // which owns it, and launch_window.hip, whose Monte-Carlo run samples on a sample-only engine and reads its rows.
 #pragma once
-#include "engine_common.h"
+#include "harvest.h"
 
 struct bposd_dem : EngineBase {
     bposd_dem_config cfg{};
@@ -23,7 +23,8 @@ struct bposd_dem : EngineBase {
     DevArray<uint8_t> d_flags, d_conv;
     DevArray<int> d_iters;
     DevArray<long long> d_logw;
-    CounterBlock counters;  // 5 counters
+    CounterBlock counters;  // 5 counters; with the harvest on, ints 5 .. 7 hold its triple
+    Harvest hv;             // bposd_dem_set_harvest (harvest.h)
 };
 
 namespace bposd_host {

@@ -202,11 +202,13 @@ struct CounterBlock {
     const int* obs_fail() const { return h_counters.as<int>() + 8; }
 };
 
-// One item of bposd_*_fetch: device rows of row_bytes each, one per shot of the batch or (per_batch) one for the batch.
+// One item of bposd_*_fetch: device rows of row_bytes each, one per shot of the batch or (per_batch) one for the batch; an
+// item with a row count of its own (the harvest's: as many rows as the batch had failures) says so in `rows`.
 struct FetchItem {
     const void* src;
     size_t row_bytes;
     bool per_batch;
+    long long rows = -1;  // >= 0: the item's own row count in the last batch, whatever the batch's
 };
 
 // bposd_*_fetch behind the engine's own preconditions: item `what` of items[first_id .. first_id + n_items), `rows` shots
@@ -218,7 +220,7 @@ inline int engine_fetch(EngineBase* e, const FetchItem* items, int n_items, int 
     if (what < first_id || what >= first_id + n_items) return engine_fail(e, BPOSD_ERR_INVALID, "what = %d is not one of %s", what, names);
     if (rows == 0) return engine_fail(e, BPOSD_ERR_INVALID, "no batch has run yet");
     const FetchItem& it = items[what - first_id];
-    const size_t want = it.row_bytes * (it.per_batch ? 1 : (size_t)rows);
+    const size_t want = it.row_bytes * (it.per_batch ? 1 : it.rows >= 0 ? (size_t)it.rows : (size_t)rows);
     if (bytes != want) return engine_fail(e, BPOSD_ERR_INVALID, "the last batch holds %zu bytes of item %d, not %zu", want, what, bytes);
     if (want == 0) return BPOSD_OK;
     if (it.per_batch) {

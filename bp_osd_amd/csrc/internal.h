@@ -239,4 +239,18 @@ inline bool native_packed(const bposd_handle* h) {
     return !h->bp_any && h->cfg.schedule == 0 && h->bp_variant != 64 && !(h->bp_variant >= 16 && h->bp_variant <= 26);
 }
 
+// The osdw rows of the last observables decode (bposd_decode_batch_observables_device) and their form: decode_obs_impl
+// leaves them in the buffers of the lane the call took, packed words [B][ceil(n / 64)] where the kernels are packed, bytes
+// [B][n] otherwise.  They are final behind the event the caller records on that lane after the call, and they stay until
+// the next call that takes that lane.
+struct ObsRows {
+    const void* osdw;
+    bool packed;
+};
+inline ObsRows last_obs_rows(const bposd_handle* h) {
+    const Lane& L = h->lanes[h->last_lane];
+    const bool native = native_packed(h);
+    return ObsRows{native ? L.io_posdw.p : L.io_osdw.p, native};
+}
+
 }  // namespace bposd_host

@@ -86,6 +86,7 @@ int bposd_host::dem_sample_async(bposd_dem* dem, uint64_t first_shot, int64_t B,
     DeviceGuard guard(dem->device);
     ENGINE_TRY(dem, guard.err);
     dem->sampled_B = dem->scored_B = 0;
+    dem->hv.last_on = false;
     if (const int rc = enqueue_sample(dem, first_shot, B)) return rc;
     ENGINE_TRY(dem, hipEventRecord(dem->ev_sampled, dem->stream));
     ENGINE_TRY(dem, hipStreamWaitEvent(waiter, dem->ev_sampled, 0));
@@ -196,9 +197,24 @@ int bposd_dem_sample(bposd_dem* dem, uint64_t first_shot, int64_t B) {
     DeviceGuard guard(dem->device);
     ENGINE_TRY(dem, guard.err);
     dem->sampled_B = dem->scored_B = 0;
+    dem->hv.last_on = false;
     if (const int rc = enqueue_sample(dem, first_shot, B)) return rc;
     ENGINE_TRY(dem, hipStreamSynchronize(dem->stream));
     dem->sampled_B = B;
+    return BPOSD_OK;
+}
+
+int bposd_dem_set_harvest(bposd_dem* dem, int64_t max_rows) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (!dem->dec) return engine_fail(dem, BPOSD_ERR_INVALID, "this engine was created without a decoder: it has no failing shots to harvest");
+    return bposd_host::harvest_set(dem, dem->hv, max_rows, dem->fw);
+}
+
+int bposd_dem_harvest_info(bposd_dem* dem, int64_t out[3]) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (!out) return engine_fail(dem, BPOSD_ERR_INVALID, "out is NULL");
+    if (!dem->hv.last_on) return engine_fail(dem, BPOSD_ERR_INVALID, "the last batch ran with the harvest off (bposd_dem_set_harvest)");
+    std::copy(dem->hv.info, dem->hv.info + 3, out);
     return BPOSD_OK;
 }
 
@@ -213,6 +229,7 @@ int bposd_dem_run(bposd_dem* dem, uint64_t first_shot, int64_t B, int64_t counte
     DeviceGuard guard(dem->device);
     ENGINE_TRY(dem, guard.err);
     dem->sampled_B = dem->scored_B = 0;
+    dem->hv.last_on = false;
 
     int rc;
     if ((rc = enqueue_sample(dem, first_shot, B))) return rc;
@@ -246,9 +263,21 @@ int bposd_dem_run(bposd_dem* dem, uint64_t first_shot, int64_t B, int64_t counte
     hipLaunchKernelGGL(dem_score_kernel, dim3(grid), dim3(DEM_SCORE_THREADS), 0, dem->stream, Q);
     ENGINE_TRY(dem, hipGetLastError());
     ENGINE_TRY(dem, hipEventRecord(dem->ev_t[3], dem->stream));
-    ENGINE_TRY(dem, dem->counters.download(dem->stream, 5));
+    const bool harvest = dem->hv.on();
+    if (harvest) {
+        // The osdw rows are the ones the decode left in its lane's buffers.  The engine's stream is behind ev_decoded, so
+        // they are final, and they stay: this call ends in its host wait before anything else can be queued on that lane.
+        const bposd_host::ObsRows rows = bposd_host::last_obs_rows(dec);
+        const HarvestJob job{B, dem->N, dem->fw, /*flag_mask=*/4, /*flag_want=*/4, dem->d_flags, dem->d_faults, rows.osdw, rows.packed};
+        if ((rc = bposd_host::harvest_enqueue(dem, dem->hv, job, dem->counters.d_counters))) {
+            (void)hipStreamSynchronize(dem->stream);
+            return rc;
+        }
+    }
+    ENGINE_TRY(dem, dem->counters.download(dem->stream, harvest ? 8 : 5));
     ENGINE_TRY(dem, hipStreamSynchronize(dem->stream));  // the batch's one host wait
     dem->counters.read(counters, 5);
+    if (harvest) bposd_host::harvest_read(dem->hv, dem->counters.h_counters.as<int>());
     dem->sampled_B = dem->scored_B = B;
     return BPOSD_OK;
 }
@@ -262,13 +291,16 @@ int bposd_dem_fetch(bposd_dem* dem, int32_t what, void* host_dst, size_t bytes) 
         return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs a batch sampled since bposd_dem_set_sampling", what);
     if (what >= BPOSD_DEM_OBS_BP && what <= BPOSD_DEM_OBS_FAIL && dem->sampled_B && dem->scored_B == 0)
         return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs bposd_dem_run: the last batch was sampled only", what);
+    if (what >= BPOSD_DEM_FAIL_ROWS && what <= BPOSD_DEM_MIN_RESIDUAL && !dem->hv.last_on)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs a batch that ran with the harvest on (bposd_dem_set_harvest)", what);
     const size_t fw = 8 * (size_t)dem->fw, dw = 8 * (size_t)dem->dw, ow = 8 * (size_t)dem->ow;
-    const FetchItem items[] = {{dem->d_faults, fw, false},   {dem->d_detectors, dw, false}, {dem->d_observables, ow, false},
+    FetchItem items[16] = {{dem->d_faults, fw, false},   {dem->d_detectors, dw, false}, {dem->d_observables, ow, false},
                                {dem->d_obs_bp, ow, false},   {dem->d_obs_osd0, ow, false},  {dem->d_obs_osdw, ow, false},
                                {dem->d_flags, 1, false},     {dem->d_conv, 1, false},       {dem->d_iters, sizeof(int32_t), false},
                                {nullptr, sizeof(int32_t) * (size_t)dem->k, true},           {dem->d_logw, sizeof(int64_t), false}};
-    return engine_fetch(dem, items, 11, BPOSD_DEM_FAULTS, "BPOSD_DEM_FAULTS .. BPOSD_DEM_LOGW", what, dem->sampled_B, dem->counters.obs_fail(), host_dst,
-                        bytes);
+    bposd_host::harvest_items(dem->hv, dem->fw, items + 11);
+    return engine_fetch(dem, items, 16, BPOSD_DEM_FAULTS, "BPOSD_DEM_FAULTS .. BPOSD_DEM_MIN_RESIDUAL", what, dem->sampled_B, dem->counters.obs_fail(),
+                        host_dst, bytes);
 }
 
 int64_t bposd_dem_device_bytes(bposd_dem* dem) { return dem ? (int64_t)dem->device_bytes : BPOSD_ERR_INVALID; }
@@ -290,6 +322,56 @@ int bposd_debug_dem_timing(bposd_dem* dem, double* sample_ms, double* score_ms) 
             *score_ms = ms;
         }
     }
+    return BPOSD_OK;
+}
+
+int bposd_debug_dem_harvest(bposd_dem* dem, const uint64_t* fault_words, const void* corrections, int32_t packed, const uint8_t* select, int64_t B) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (!dem->hv.on()) return engine_fail(dem, BPOSD_ERR_INVALID, "the harvest is off (bposd_dem_set_harvest)");
+    if (!fault_words || !corrections || !select) return engine_fail(dem, BPOSD_ERR_INVALID, "fault rows, corrections and select are required");
+    if (const int rc = engine_check_batch(dem, B)) return rc;
+    DeviceGuard guard(dem->device);
+    ENGINE_TRY(dem, guard.err);
+    dem->sampled_B = dem->scored_B = dem->logw_B = 0;
+    dem->hv.last_on = false;
+    const size_t rows = (size_t)B;
+    const size_t corr_bytes = packed ? 8 * rows * dem->fw : rows * (size_t)dem->N;
+    std::vector<uint8_t> flags(rows);
+    for (size_t b = 0; b < rows; ++b) flags[b] = select[b] ? 4 : 0;  // what dem_score_kernel leaves for an osdw failure
+    DevBuf d_corr;  // (the engine has no correction rows of its own: a batch reads the decoder's)
+    int rc;
+    if ((rc = engine_alloc_bytes(nullptr, d_corr, corr_bytes))) return engine_fail(dem, rc, "%s", bposd_last_error(nullptr));
+    ENGINE_TRY(dem, hipStreamSynchronize(dem->stream));
+    ENGINE_TRY(dem, hipMemcpy(dem->d_faults, fault_words, 8 * rows * dem->fw, hipMemcpyHostToDevice));
+    ENGINE_TRY(dem, hipMemcpy(dem->d_flags, flags.data(), rows, hipMemcpyHostToDevice));
+    ENGINE_TRY(dem, hipMemcpy(d_corr.p, corrections, corr_bytes, hipMemcpyHostToDevice));
+    ENGINE_TRY(dem, dem->counters.reset(dem->stream));
+    const HarvestJob job{B, dem->N, dem->fw, 4, 4, dem->d_flags, dem->d_faults, d_corr.p, packed != 0};
+    rc = bposd_host::harvest_enqueue(dem, dem->hv, job, dem->counters.d_counters);
+    if (!rc) {
+        const hipError_t err = dem->counters.download(dem->stream, 8);
+        if (err != hipSuccess) rc = engine_fail(dem, BPOSD_ERR_HIP, "the counters' download failed: %s", hipGetErrorString(err));
+    }
+    const hipError_t waited = hipStreamSynchronize(dem->stream);  // (before d_corr goes)
+    if (rc) return rc;
+    ENGINE_TRY(dem, waited);
+    bposd_host::harvest_read(dem->hv, dem->counters.h_counters.as<int>());
+    // Items 0 and 11 .. 15 hold this call's rows.  scored_B stays 0 on purpose: the call has overwritten the engine's flag
+    // bytes with the stand-in for `select` and decoded nothing, so bposd_dem_fetch must go on refusing the flags and every
+    // other decoded item (3 .. 9) until a batch has run.
+    dem->sampled_B = B;
+    return BPOSD_OK;
+}
+
+int bposd_debug_dem_harvest_timing(bposd_dem* dem, double* harvest_ms) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (!harvest_ms) return engine_fail(dem, BPOSD_ERR_INVALID, "harvest_ms is NULL");
+    if (!dem->hv.last_on) return engine_fail(dem, BPOSD_ERR_INVALID, "the last batch ran with the harvest off (bposd_dem_set_harvest)");
+    DeviceGuard guard(dem->device);
+    ENGINE_TRY(dem, guard.err);
+    float ms = 0.f;
+    ENGINE_TRY(dem, hipEventElapsedTime(&ms, dem->hv.ev_t[0], dem->hv.ev_t[1]));
+    *harvest_ms = ms;
     return BPOSD_OK;
 }
 

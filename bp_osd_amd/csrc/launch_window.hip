@@ -69,7 +69,8 @@ struct bposd_window : EngineBase {
     DevBuf d_synd, d_dec;  // the current window's syndrome and decoded rows, in its decoder's form
     DevArray<uint8_t> d_conv_all, d_wconv, d_flags;
     DevArray<int> d_iters, d_witers;
-    CounterBlock counters;  // 4 counters
+    CounterBlock counters;  // 4 counters; with the harvest on, ints 5 .. 7 hold its triple
+    Harvest hv;             // bposd_window_set_harvest (harvest.h)
 };
 
 namespace {
@@ -330,6 +331,7 @@ int bposd_window_decode_device(bposd_window* win, const uint64_t* d_detector_wor
     DeviceGuard guard(win->device);
     ENGINE_TRY(win, guard.err);
     win->run_B = 0;
+    win->hv.last_on = false;
     Rows r{};
     r.running = d_residual_words ? (unsigned long long*)d_residual_words : (unsigned long long*)win->d_running;
     r.obs = (unsigned long long*)d_obs_words;
@@ -356,6 +358,7 @@ int bposd_window_decode(bposd_window* win, const uint64_t* detector_words, int64
     DeviceGuard guard(win->device);
     ENGINE_TRY(win, guard.err);
     win->run_B = 0;
+    win->hv.last_on = false;
     hipStream_t st = win->stream;
     const size_t dw = win->dw, ow = win->ow, fw = win->fw;
     for (int64_t lo = 0; lo < B; lo += win->capacity) {
@@ -384,6 +387,7 @@ int bposd_window_run(bposd_window* win, bposd_dem* sampler, uint64_t first_shot,
     DeviceGuard guard(win->device);
     ENGINE_TRY(win, guard.err);
     win->run_B = 0;
+    win->hv.last_on = false;
     hipStream_t st = win->stream;
     if (const int rc = bposd_host::dem_sample_async(sampler, first_shot, B, st)) return engine_fail(win, rc, "sampler: %s", bposd_dem_last_error(sampler));
     Rows r{win->d_running, win->d_obs, win->d_corr, win->d_conv_all, win->d_iters};
@@ -414,9 +418,20 @@ int bposd_window_run(bposd_window* win, bposd_dem* sampler, uint64_t first_shot,
     hipLaunchKernelGGL(window_score_kernel, dim3(grid), dim3(WIN_SCORE_THREADS), 0, st, Q);
     ENGINE_TRY(win, hipGetLastError());
     ENGINE_TRY(win, hipEventRecord(ev[1], st));
-    ENGINE_TRY(win, win->counters.download(st, 4));
+    const bool harvest = win->hv.on();
+    if (harvest) {
+        // observables wrong (bit 0) on a residual of zero (bit 1 clear); the corrections are the engine's own packed rows, the
+        // fault rows the sampler's, which the engine's stream is ordered behind
+        const HarvestJob job{B, win->N, win->fw, /*flag_mask=*/3, /*flag_want=*/1, win->d_flags, sampler->d_faults, r.corr, true};
+        if ((rc = bposd_host::harvest_enqueue(win, win->hv, job, win->counters.d_counters))) {
+            (void)hipStreamSynchronize(st);
+            return rc;
+        }
+    }
+    ENGINE_TRY(win, win->counters.download(st, harvest ? 8 : 4));
     ENGINE_TRY(win, hipStreamSynchronize(st));  // the batch's one host wait
     win->counters.read(counters, 4);
+    if (harvest) bposd_host::harvest_read(win->hv, win->counters.h_counters.as<int>());
     win->timed_score = true;
     win->run_B = B;
     return BPOSD_OK;
@@ -425,13 +440,29 @@ int bposd_window_run(bposd_window* win, bposd_dem* sampler, uint64_t first_shot,
 int bposd_window_fetch(bposd_window* win, int32_t what, void* host_dst, size_t bytes) {
     if (!win) return BPOSD_ERR_INVALID;
     if (win->run_B == 0) return engine_fail(win, BPOSD_ERR_INVALID, "no bposd_window_run has completed since the last decode call");
+    if (what >= BPOSD_WINDOW_FAIL_ROWS && what <= BPOSD_WINDOW_MIN_RESIDUAL && !win->hv.last_on)
+        return engine_fail(win, BPOSD_ERR_INVALID, "item %d needs a batch that ran with the harvest on (bposd_window_set_harvest)", what);
     const size_t ow = 8 * (size_t)win->ow;
-    const FetchItem items[] = {{win->d_obs, ow, false},   {win->d_truth, ow, false},    {win->d_corr, 8 * (size_t)win->fw, false},
+    FetchItem items[13] = {{win->d_obs, ow, false},   {win->d_truth, ow, false},    {win->d_corr, 8 * (size_t)win->fw, false},
                                {win->d_running, 8 * (size_t)win->dw, false},            {win->d_flags, 1, false},
                                {win->d_conv_all, 1, false}, {win->d_iters, sizeof(int32_t), false},
                                {nullptr, sizeof(int32_t) * (size_t)win->k, true}};
-    return engine_fetch(win, items, 8, BPOSD_WINDOW_OBS, "BPOSD_WINDOW_OBS .. BPOSD_WINDOW_OBS_FAIL", what, win->run_B, win->counters.obs_fail(), host_dst,
-                        bytes);
+    bposd_host::harvest_items(win->hv, win->fw, items + 8);
+    return engine_fetch(win, items, 13, BPOSD_WINDOW_OBS, "BPOSD_WINDOW_OBS .. BPOSD_WINDOW_MIN_RESIDUAL", what, win->run_B, win->counters.obs_fail(),
+                        host_dst, bytes);
+}
+
+int bposd_window_set_harvest(bposd_window* win, int64_t max_rows) {
+    if (!win) return BPOSD_ERR_INVALID;
+    return bposd_host::harvest_set(win, win->hv, max_rows, win->fw);
+}
+
+int bposd_window_harvest_info(bposd_window* win, int64_t out[3]) {
+    if (!win) return BPOSD_ERR_INVALID;
+    if (!out) return engine_fail(win, BPOSD_ERR_INVALID, "out is NULL");
+    if (!win->hv.last_on) return engine_fail(win, BPOSD_ERR_INVALID, "the last batch ran with the harvest off (bposd_window_set_harvest)");
+    std::copy(win->hv.info, win->hv.info + 3, out);
+    return BPOSD_OK;
 }
 
 int64_t bposd_window_device_bytes(bposd_window* win) { return win ? (int64_t)win->device_bytes : BPOSD_ERR_INVALID; }

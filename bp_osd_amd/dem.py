@@ -28,7 +28,7 @@ import math
 import numpy as np
 import scipy.sparse as sp
 
-from ._dem_base import DemSimBase, _gf2_csr, checked_model, create_dem
+from ._dem_base import HARVEST_ITEMS, DemSimBase, _gf2_csr, _pack, checked_model, create_dem, harvest_batch
 from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
 
 __all__ = ["dem_decode_sim", "importance_table", "phenomenological_dem", "phenomenological_detector_times"]
@@ -66,15 +66,6 @@ def phenomenological_detector_times(m, rounds):
     """The time of every detector of ``phenomenological_dem`` for a code with ``m`` checks: detector (t, c) is row t m + c and
     has time t, for t = 0 .. rounds (what ``bp_osd_amd.window`` takes as ``detector_time``)."""
     return np.repeat(np.arange(int(rounds) + 1), int(m))
-
-
-def _pack(rows):
-    """uint8 0/1 rows [B, c] -> uint64 [B, ceil(c/64)] (the C-ABI's packed form)."""
-    a = np.ascontiguousarray(rows, dtype=np.uint8)
-    by = np.packbits(a, axis=1, bitorder="little")
-    out = np.zeros((a.shape[0], 8 * ((a.shape[1] + 63) // 64)), np.uint8)
-    out[:, :by.shape[1]] = by
-    return out.view("<u8")
 
 
 LOGW_ONE = 2 ** 32  # units of a log-weight increment per nat
@@ -134,6 +125,14 @@ class dem_decode_sim(DemSimBase):
     sample_priors, sample_scale : importance sampling, at most one of the two.  ``sample_priors`` = q, N floats in [0, 1] the
         faults are drawn against (``u(s, i) < q_i``: the same stream and counter) while the decoder keeps ``priors``;
         ``sample_scale`` = beta >= 1 is ``q_i = p_i`` where ``p_i >= 0.5``, else ``min(beta * p_i, 0.5)``.  See below
+    harvest : K, an int >= 0 (default 0: off).  With K > 0 the failing shots are harvested: a shot whose osdw
+        observables are wrong leaves the residual ``faults ^ osdw correction``, an undetected logical fault set.  Results:
+        ``min_logical_weight`` (the least residual weight of the run, an upper bound of the model's fault distance; None if
+        nothing failed), ``min_logical_shot`` (its global shot; the earliest of a tie), ``min_logical_fault`` (uint8 [N]),
+        ``failure_weight_counts`` (int64 [N + 1]: every failing shot by residual weight) and ``failures``: the first K
+        failing shots of the run in shot order, a dict of "shot" (uint64), "weight" (int32), "residual" and "faults" (packed
+        rows) and, with importance sampling, "logw" (int64).  engine="native" compacts the failing rows on the device: no batch-sized array
+        crosses to the host for it
 
     Results: ``run_count``, ``bp_converge_count``, ``bp_success_count`` (converged and observables right),
     ``osd0_success_count``, ``osdw_success_count``, ``trivial_count`` (no detector fired), ``*_logical_error_rate`` with
@@ -152,11 +151,12 @@ class dem_decode_sim(DemSimBase):
     _RATES = ("bp", "osd0", "osdw")
 
     def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=100, decoder_factory=None, run_sim=True,
-                 sample_priors=None, sample_scale=None, **decoder_kwargs):
+                 sample_priors=None, sample_scale=None, harvest=0, **decoder_kwargs):
         self._check_engine(engine, decoder_factory, "decoder")
         self._H, self._L, self._priors = checked_model(H, L, priors)
         self.M, self.N = self._H.shape
         self.K = self._L.shape[0]
+        self._init_harvest(harvest, with_logw=sample_priors is not None or sample_scale is not None)
         p = self._priors
         if sample_priors is not None and sample_scale is not None:
             raise ValueError("give sample_priors or sample_scale, not both")
@@ -203,11 +203,19 @@ class dem_decode_sim(DemSimBase):
         from . import _lib
 
         c = (C.c_int64 * 5)()
-        _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_run(self._dem, int(self.run_count), int(B), c))
+        first, ask = self.run_count, None
+        if self.harvest:
+            ask = self._harvest_ask()
+            self._set_native_harvest(self._dem, "bposd_dem_set_harvest", _lib.check_dem, ask)
+        _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_run(self._dem, int(first), int(B), c))
         self._last_B = B
         self._accumulate(B, [int(v) for v in c], self.last_batch("obs_fail"))
+        logw = self.last_batch("logw") if self._tilted else None
         if self._tilted:
-            self._accumulate_weighted(self.last_batch("flags"), self.last_batch("converged"), self.last_batch("logw"))
+            self._accumulate_weighted(self.last_batch("flags"), self.last_batch("converged"), logw)
+        if self.harvest:
+            info = self._native_harvest_triple(self._dem, "bposd_dem_harvest_info", _lib.check_dem)
+            self._accumulate_harvest(first, info, ask, logw)
 
     def device_bytes(self):
         """engine="native": bytes of device memory the engine holds for its batches (the decoder's workspaces are its own)."""
@@ -250,10 +258,16 @@ class dem_decode_sim(DemSimBase):
                       "iters": iters.astype(np.int32), "obs_fail": obs_fail}
         counters = [int(conv.sum()), int((conv & ~wrong["bp"]).sum()), int((~wrong["osd0"]).sum()), int((~wrong["osdw"]).sum()),
                     int(quiet.sum())]
+        first = self.run_count
         self._accumulate(B, counters, obs_fail)
         if self._tilted:
             self._last["logw"] = faults.astype(np.int64) @ self._incr
             self._accumulate_weighted(flags, self._last["converged"], self._last["logw"])
+        if self.harvest:  # the osdw failures, against the osdw rows
+            ask = self._harvest_ask()
+            h = harvest_batch(faults, rows["osdw"], wrong["osdw"], ask)
+            self._last.update({item: h[item] for item in HARVEST_ITEMS})
+            self._accumulate_harvest(first, (h["fail_count"], h["min_weight"], h["min_row"]), ask, self._last.get("logw"))
 
     # ------------------------------------------------------------------ common
     def _accumulate_weighted(self, flags, converged, logw):
@@ -281,13 +295,16 @@ class dem_decode_sim(DemSimBase):
         (bit-packed rows, uint64 [B, ceil(./64)]: ``BpOsdDecoder.unpack_rows`` expands them), "flags" (uint8 [B]: bit 0 bp
         wrong, 1 osd0 wrong, 2 osdw wrong, 3 no detector fired), "converged" (uint8 [B]), "iters" (int32 [B]) or "obs_fail"
         (int32 [k]: osdw failures per observable in that batch), and with importance sampling "logw" (int64 [B]: the shot's
-        log-weight in units of 2^-32).  engine="native" copies it from the device."""
+        log-weight in units of 2^-32).  With ``harvest=K`` also "fail_rows", "fail_weight" (int32, one per failing shot of the
+        batch, rows ascending), "fail_residual", "fail_faults" (packed rows of the first failing shots, as many as the run still
+        missed of its K, at least one) and "min_residual" (one packed row).  engine="native" copies it from the device."""
         from . import _lib
 
         if what not in _lib.DEM_ITEMS:
             raise ValueError(f"what must be one of {sorted(_lib.DEM_ITEMS)}")
         if what == "logw" and not self._tilted:
             raise ValueError("last_batch('logw') needs importance sampling (sample_priors or sample_scale)")
+        self._check_harvest_item(what)
         return self._last_batch(what, lambda: self._fetch(_lib.DEM_ITEMS, self._dem, self._lib.bposd_dem_fetch, _lib.check_dem, what))
 
     def output_dict(self):
@@ -297,4 +314,6 @@ class dem_decode_sim(DemSimBase):
             out["sample_scale"] = self.sample_scale
             out["weight_mean"] = float(self.weight_mean)
             out["effective_sample_fraction"] = float(self.effective_sample_fraction)
+        if self.harvest:
+            out["min_logical_weight"] = self.min_logical_weight
         return json.dumps(out, sort_keys=True, indent=4)

@@ -27,13 +27,12 @@ from types import SimpleNamespace
 import numpy as np
 import scipy.sparse as sp
 
-from ._dem_base import DemSimBase, _gf2_csr, checked_model, create_dem
-from .dem import _pack
+from ._dem_base import HARVEST_ITEMS, DemSimBase, _gf2_csr, _pack, checked_model, create_dem, harvest_batch
 from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
 
 __all__ = ["window_plan", "WindowedDemDecoder", "windowed_dem_decode_sim"]
 
-_ITEMS = ("faults", "detectors", "observables", "obs_osdw", "correction", "residual", "flags", "converged", "iters", "obs_fail")
+_ITEMS = ("faults", "detectors", "observables", "obs_osdw", "correction", "residual", "flags", "converged", "iters", "obs_fail") + HARVEST_ITEMS
 
 
 def window_plan(H, detector_time, window, priors=None, check_rank=True):
@@ -308,6 +307,8 @@ class windowed_dem_decode_sim(DemSimBase):
     seed, target_runs, run_sim : as in ``dem_decode_sim``; the Philox stream is the same one, so both engines and the
         unwindowed harness see the same shots
     decoder_factory : engine="numpy" only; default the MI355X ``BpOsdDecoder``
+    harvest : K >= 0, as in ``dem_decode_sim``; a shot fails here when its observables are wrong and its final residual
+        detector row is zero, and the residual fault set is ``faults ^ correction`` (no "logw": the window run is unweighted)
 
     Results: ``run_count``, ``bp_converge_count`` (BP converged in every window), ``osdw_success_count`` (observables right),
     ``residual_count`` (final detector row not zero: 0 for full-rank windows), ``trivial_count`` (no detector fired),
@@ -318,11 +319,12 @@ class windowed_dem_decode_sim(DemSimBase):
     _RATES = ("osdw",)
 
     def __init__(self, H, L, priors, detector_time, window, batch_size=4096, engine="native", seed=0, target_runs=100,
-                 decoder_factory=None, run_sim=True, **decoder_kwargs):
+                 decoder_factory=None, run_sim=True, harvest=0, **decoder_kwargs):
         self._check_engine(engine, decoder_factory, "decoders")
         self._win = self._sampler = None
         self._model = m = _Model(H, L, priors, detector_time, window)
         self.M, self.N, self.K = m.M, m.N, m.K
+        self._init_harvest(harvest)
         self.plan = m.plan
         self._init_run(batch_size, seed, target_runs)
         if engine == "native":
@@ -348,9 +350,16 @@ class windowed_dem_decode_sim(DemSimBase):
         from . import _lib
 
         c = (C.c_int64 * 4)()
-        _lib.check_window(self._lib, self._win, self._lib.bposd_window_run(self._win, self._sampler, int(self.run_count), int(B), c))
+        first, ask = self.run_count, None
+        if self.harvest:
+            ask = self._harvest_ask()
+            self._set_native_harvest(self._win, "bposd_window_set_harvest", _lib.check_window, ask)
+        _lib.check_window(self._lib, self._win, self._lib.bposd_window_run(self._win, self._sampler, int(first), int(B), c))
         self._last_B = B
         self._accumulate(B, [int(v) for v in c], self.last_batch("obs_fail"))
+        if self.harvest:
+            info = self._native_harvest_triple(self._win, "bposd_window_harvest_info", _lib.check_window)
+            self._accumulate_harvest(first, info, ask)
 
     def device_bytes(self):
         """engine="native": bytes of device memory the window engine holds (sampler and decoders hold their own)."""
@@ -385,18 +394,25 @@ class windowed_dem_decode_sim(DemSimBase):
         self._last = {"faults": _pack(faults), "detectors": _pack(detectors), "observables": _pack(truth), "obs_osdw": _pack(obs),
                       "correction": _pack(corr), "residual": _pack(res), "flags": flags, "converged": conv.astype(np.uint8), "iters": iters,
                       "obs_fail": obs_fail}
+        first = self.run_count
         self._accumulate(B, [int(conv.sum()), int((~wrong).sum()), int(dirty.sum()), int(quiet.sum())], obs_fail)
+        if self.harvest:  # observables wrong on a residual of zero, against the committed correction
+            ask = self._harvest_ask()
+            h = harvest_batch(faults, corr, wrong & ~dirty, ask)
+            self._last.update({item: h[item] for item in HARVEST_ITEMS})
+            self._accumulate_harvest(first, (h["fail_count"], h["min_weight"], h["min_row"]), ask)
 
     # ------------------------------------------------------------------ common
     def last_batch(self, what):
         """One array of the last batch: "faults", "detectors", "observables" (the true ones), "obs_osdw", "correction",
         "residual" (bit-packed rows, uint64 [B, ceil(./64)]), "flags" (uint8 [B]: bit 0 observables wrong, bit 1 residual not
         zero, bit 3 no detector fired), "converged" (uint8 [B]: in every window), "iters" (int32 [B]: summed over the windows)
-        or "obs_fail" (int32 [k])."""
+        or "obs_fail" (int32 [k]); with ``harvest=K`` the five items of a harvest as ``dem_decode_sim.last_batch`` has them."""
         from . import _lib
 
         if what not in _ITEMS:
             raise ValueError(f"what must be one of {sorted(_ITEMS)}")
+        self._check_harvest_item(what)
         if what in ("faults", "detectors"):  # the sampler's own rows
             return self._last_batch(what, lambda: self._fetch(_lib.DEM_ITEMS, self._sampler, self._lib.bposd_dem_fetch, _lib.check_dem, what))
         return self._last_batch(what, lambda: self._fetch(_lib.WINDOW_ITEMS, self._win, self._lib.bposd_window_fetch, _lib.check_window, what))
@@ -404,4 +420,6 @@ class windowed_dem_decode_sim(DemSimBase):
     def output_dict(self):
         """The counters and rates as a JSON string (as dem_decode_sim.output_dict returns one)."""
         out = dict(self._results(), T=self.plan.T, window=[self.plan.W, self.plan.C], windows=len(self.plan.windows), decoders=len(self.plan.unique))
+        if self.harvest:
+            out["min_logical_weight"] = self.min_logical_weight
         return json.dumps(out, sort_keys=True, indent=4)

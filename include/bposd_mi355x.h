@@ -451,7 +451,13 @@ enum {
     BPOSD_DEM_CONVERGED = 7,   /* uint8[B]                                                                            */
     BPOSD_DEM_ITERS = 8,       /* int32[B]                                                                            */
     BPOSD_DEM_OBS_FAIL = 9,    /* int32[k]: osdw failures per observable in this batch                                */
-    BPOSD_DEM_LOGW = 10        /* int64[B]: the shot's log-weight in units of 2^-32 (weighted sampling only, see below) */
+    BPOSD_DEM_LOGW = 10,       /* int64[B]: the shot's log-weight in units of 2^-32 (weighted sampling only, see below) */
+    /* the harvest of the last batch (bposd_dem_set_harvest below): F failing shots, K = max_rows */
+    BPOSD_DEM_FAIL_ROWS = 11,     /* int32[F]: the failing rows, ascending                                            */
+    BPOSD_DEM_FAIL_WEIGHT = 12,   /* int32[F]: weight of the residual, aligned with FAIL_ROWS                         */
+    BPOSD_DEM_FAIL_RESIDUAL = 13, /* uint64[min(F, K)][ceil(N/64)]: faults XOR correction of the first failing rows   */
+    BPOSD_DEM_FAIL_FAULTS = 14,   /* uint64[min(F, K)][ceil(N/64)]: their fault rows                                  */
+    BPOSD_DEM_MIN_RESIDUAL = 15   /* uint64[ceil(N/64)]: the residual of the lightest failing row, zeros when F = 0   */
 };
 
 /*
@@ -513,7 +519,36 @@ int bposd_dem_sample(bposd_dem *dem, uint64_t first_shot, int64_t B);
  */
 int bposd_dem_run(bposd_dem *dem, uint64_t first_shot, int64_t B, int64_t counters[5]);
 
-/* Copy one item (BPOSD_DEM_FAULTS ...) of the last batch to host memory; bytes must be that item's size for the last B.
+/*
+ * Harvest of failing shots: with max_rows = K >= 1 every bposd_dem_run also keeps, on the device and behind its scorer, the
+ * shots whose osdw observables are wrong (flag bit 2).  For such a row b with fault row f_b and osdw correction c_b the
+ * residual r_b = f_b XOR c_b has H r_b = 0 (osdw reproduces a consistent syndrome) and L r_b != 0: an undetected logical
+ * fault set, whose weight w_b = popcount(r_b) bounds the model's fault distance from above.  Per batch:
+ *     items 11 .. 15 of bposd_dem_fetch (above), and bposd_dem_harvest_info: out[0] = F, the number of failing shots,
+ *     out[1] = the least w_b over ALL of them, out[2] = the LOWEST row that has it; -1, -1 when F = 0.
+ * Rows are listed in ascending order by prefix sums and a tie in weight goes to the lowest row: nothing depends on the order
+ * in which waves arrive, and the host restatement (bp_osd_amd._dem_base.harvest_batch) gives the same bits.  bp and osd0
+ * rows are not harvested (a bp row that did not converge does not reproduce the syndrome).
+ *
+ * Three small kernels (csrc/harvest_kernels.hip.h) run on the engine's stream between the scorer and the counters'
+ * download; the triple comes down with the counters, so a batch keeps its one host wait.  The correction rows are read
+ * where the decode left them, in the buffers of the decoder lane it ran on: they stay valid because bposd_dem_run ends in
+ * its host wait before anything else can be queued on that lane.
+ *
+ * max_rows = 0 switches off (the default; the block stays allocated): then a batch launches and allocates nothing more
+ * than it did before.  Negative: BPOSD_ERR_INVALID; so is a sample-only engine.  A refusal leaves the engine as it was.
+ * The first call with K >= 1 (and a later call with a larger K, which replaces the block) allocates one block of
+ *     8 capacity + (2 K + 1) * 8 ceil(N/64) + 256   bytes
+ * -- list and weights, K residual and K fault rows, the lightest residual (it need not be among the first K, so it has a
+ * row of its own), 256 bytes of kernel state (the running minimum and the count between the launches) -- counted in
+ * bposd_dem_device_bytes.  bposd_dem_harvest_info is a host copy (no device call) and, like items 11 .. 15, is refused
+ * unless the last batch ran with the harvest on.
+ */
+int bposd_dem_set_harvest(bposd_dem *dem, int64_t max_rows);
+int bposd_dem_harvest_info(bposd_dem *dem, int64_t out[3]);
+
+/* Copy one item (BPOSD_DEM_FAULTS ...) of the last batch to host memory; bytes must be that item's size for the last B
+ * (for items 11 .. 14: for the last batch's number of failing shots -- 0 bytes is legal and copies nothing).
  * After bposd_dem_sample only items 0-2 are there.  BPOSD_DEM_OBS_FAIL came down with the counters: no device call.
  * BPOSD_DEM_LOGW needs a batch sampled while weighted sampling is on: BPOSD_ERR_INVALID otherwise. */
 int bposd_dem_fetch(bposd_dem *dem, int32_t what, void *host_dst, size_t bytes);
@@ -563,7 +598,13 @@ enum {
     BPOSD_WINDOW_FLAGS = 4,       /* uint8[B]: bit 0 observables wrong, bit 1 residual not zero, bit 3 no detector fired */
     BPOSD_WINDOW_CONVERGED = 5,   /* uint8[B]: BP converged in every window                                           */
     BPOSD_WINDOW_ITERS = 6,       /* int32[B]: BP iterations summed over the windows                                  */
-    BPOSD_WINDOW_OBS_FAIL = 7     /* int32[k]: failures per observable in this batch                                  */
+    BPOSD_WINDOW_OBS_FAIL = 7,    /* int32[k]: failures per observable in this batch                                  */
+    /* the harvest of the last batch (bposd_window_set_harvest below), as items 11 .. 15 of bposd_dem_fetch */
+    BPOSD_WINDOW_FAIL_ROWS = 8,
+    BPOSD_WINDOW_FAIL_WEIGHT = 9,
+    BPOSD_WINDOW_FAIL_RESIDUAL = 10,
+    BPOSD_WINDOW_FAIL_FAULTS = 11,
+    BPOSD_WINDOW_MIN_RESIDUAL = 12
 };
 
 /*
@@ -617,6 +658,15 @@ int bposd_window_decode(bposd_window *win, const uint64_t *detector_words, int64
  * true observables.
  */
 int bposd_window_run(bposd_window *win, bposd_dem *sampler, uint64_t first_shot, int64_t B, int64_t counters[4]);
+
+/*
+ * Harvest of failing shots, as bposd_dem_set_harvest / bposd_dem_harvest_info define it, with the engine's own rows: a shot
+ * fails when its observables are wrong (flag bit 0) and its final residual detector row is zero (bit 1 clear), c_b is the
+ * committed correction row and f_b the sampler's fault row; H (f_b XOR c_b) = 0 is the zero residual.  Same items (8 .. 12),
+ * same block and byte count, same rules for 0, a negative K and the refusals; only bposd_window_run harvests.
+ */
+int bposd_window_set_harvest(bposd_window *win, int64_t max_rows);
+int bposd_window_harvest_info(bposd_window *win, int64_t out[3]);
 
 /* Copy one item (BPOSD_WINDOW_OBS ...) of the last bposd_window_run to host memory; bytes must be that item's size. */
 int bposd_window_fetch(bposd_window *win, int32_t what, void *host_dst, size_t bytes);

@@ -80,6 +80,18 @@ int bposd_debug_obs_timing(bposd_handle *h, int32_t lane, double *obs_ms);
  * stream; the batch has been waited for).  score_ms is 0 after bposd_dem_sample.  Either pointer may be NULL. */
 int bposd_debug_dem_timing(bposd_dem *dem, double *sample_ms, double *score_ms);
 
+/* Diagnostics: the harvest kernels alone (bposd_dem_set_harvest must be on), with no sampler, decoder or scorer involved.
+ * Every pointer is a HOST pointer: fault_words [B][ceil(N/64)] (padding bits zero) go into the engine's fault rows;
+ * corrections are [B][ceil(N/64)] words (packed != 0, padding bits zero) or [B][N] bytes of which bit 0 counts -- the two
+ * forms a decoder leaves its rows in; select[b] != 0 stands in for the flag test.  1 <= B <= capacity.  Waits, and leaves
+ * bposd_dem_harvest_info and items 0 and 11 .. 15 of bposd_dem_fetch as a batch of B shots would. */
+int bposd_debug_dem_harvest(bposd_dem *dem, const uint64_t *fault_words, const void *corrections, int32_t packed,
+                            const uint8_t *select, int64_t B);
+
+/* Diagnostics: duration of the three harvest launches of the engine's last batch (HIP events on the engine's stream; the
+ * batch has been waited for).  Refused unless that batch ran with the harvest on. */
+int bposd_debug_dem_harvest_timing(bposd_dem *dem, double *harvest_ms);
+
 /* Diagnostics: one window_step_kernel launch on rows the caller supplies, with no decoder and no engine involved -- the
  * commit of one window from `decoded` and the gather of the next into `syndrome`.  Every pointer is a HOST pointer; rows
  * go up, the kernel runs on `device`, rows come back.  H, L as bposd_dem_tables takes them.  Commit entry c is position

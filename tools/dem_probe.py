@@ -16,7 +16,12 @@ Prints one line per figure; ``--out FILE`` appends them there (profiles/dem_rate
 ``--sample-scale BETA`` measures importance sampling instead (profiles/dem_weight_rates.txt): three engines on the model --
 plain, weighted with q = p (the same faults: what the weighted instance of the sampler costs by itself) and weighted with
 ``sample_scale=BETA`` (more faults fire, and the decoder gets harder shots) -- alternating over the rounds, whole batches:
-the sampler's HIP-event time, the ``bposd_dem_run`` call, and the batch as ``dem_decode_sim`` runs it with its fetches."""
+the sampler's HIP-event time, the ``bposd_dem_run`` call, and the batch as ``dem_decode_sim`` runs it with its fetches.
+
+``--harvest K`` measures the harvest of failing shots instead (profiles/dem_harvest_rates.txt): two engines on the model, one
+with ``harvest=K``, alternating over the rounds -- the three harvest kernels' time by HIP events, the ``bposd_dem_run`` call and
+the batch as ``dem_decode_sim`` runs it, off and on -- and the kernels' time on one failure-rich batch (every shot of the
+last batch selected through ``bposd_debug_dem_harvest``, against a correction of zeros)."""
 import argparse
 import os
 import sys
@@ -89,6 +94,76 @@ def weighted_probe(a, say):
             f"osdw failures among the shots as sampled {1 - sim.osdw_success_count / sim.run_count:.5f}{extra}")
 
 
+def harvest_probe(a, say):
+    """--harvest: a batch with the harvest on against the same batch with it off."""
+    import ctypes as C
+
+    from bp_osd_amd import _lib, dem_decode_sim
+
+    (H, L, priors), kw, what = model(a.model)
+    B, seed, K = a.batch, 5, a.harvest
+    N = H.shape[1]
+    fw = (N + 63) // 64
+    say(f"# tools/dem_probe.py --harvest {K} on one MI355X: {what}; H {H.shape[0]} x {N}, k = {L.shape[0]}, B = {B}; "
+        f"{a.rounds} rounds of {a.steps} batches per engine, alternating")
+    make = lambda **more: dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=0, run_sim=False, **more, **kw)
+    sims = {"off": make(), "on": make(harvest=K)}
+    for sim in sims.values():
+        for _ in range(2):  # warm-up: workspaces, the kernels' first launch
+            sim._run_batch_native(B)
+    on = sims["on"]
+    lib = on._lib
+    t = {name: dict(call=[], batch=[]) for name in sims}
+    k_ms, fails = [], []
+    c5, ms = (C.c_int64 * 5)(), C.c_double()
+    for _ in range(a.rounds):
+        for name, sim in sims.items():
+            call = 0.0
+            if name == "on":
+                _lib.check_dem(lib, sim._dem, lib.bposd_dem_set_harvest(sim._dem, K))
+            for _ in range(a.steps):  # the C call alone
+                t0 = time.perf_counter()
+                rc = lib.bposd_dem_run(sim._dem, sim.run_count, B, c5)
+                call += time.perf_counter() - t0
+                assert rc == 0, lib.bposd_dem_last_error(sim._dem)
+                sim._last_B = B
+                sim._accumulate(B, [int(v) for v in c5], sim.last_batch("obs_fail"))
+                if name == "on":
+                    _lib.check_dem(lib, sim._dem, lib.bposd_debug_dem_harvest_timing(sim._dem, C.byref(ms)))
+                    k_ms.append(ms.value)
+                    fails.append(B - int(c5[3]))
+            t0 = time.perf_counter()
+            for _ in range(a.steps):  # the batch as dem_decode_sim runs it: with the fetches of a harvest
+                sim._run_batch_native(B)
+            t[name]["call"].append(call / a.steps * 1e3)
+            t[name]["batch"].append((time.perf_counter() - t0) / a.steps * 1e3)
+    fmt = lambda v: " / ".join(f"{x:.2f}" for x in v)
+    say(f"harvest kernels (list + rows + min), HIP events: mean {np.mean(k_ms):.4f} ms (min {min(k_ms):.4f}, max {max(k_ms):.4f}, {len(k_ms)} batches); "
+        f"failing shots per batch: mean {np.mean(fails):.1f} (min {min(fails)}, max {max(fails)}); bytes moved per batch: {B} flag bytes + "
+        f"{2 * 8 * fw} B read per failing shot = {B + 2 * 8 * fw * np.mean(fails):,.0f} B, up to {2 * 8 * fw} B written per kept row")
+    for name in sims:
+        say(f"harvest {name}: bposd_dem_run, ms per batch and round: {fmt(t[name]['call'])}; whole batch as dem_decode_sim runs it: {fmt(t[name]['batch'])}; "
+            f"device {sims[name].device_bytes() / B:.1f} B per shot")
+    say(f"harvest kernels / bposd_dem_run with the harvest on: {100 * np.mean(k_ms) / np.mean(t['on']['call']):.3f} %; "
+        f"on minus off, mean of the rounds: call {np.mean(t['on']['call']) - np.mean(t['off']['call']):+.3f} ms, whole batch "
+        f"{np.mean(t['on']['batch']) - np.mean(t['off']['batch']):+.3f} ms")
+    say(f"after {on.run_count} shots: min_logical_weight {on.min_logical_weight} at shot {on.min_logical_shot}, {int(on.failure_weight_counts.sum())} failing shots "
+        f"weighed ({int(on.failure_weight_counts[on.min_logical_weight])} of that weight), {on.failures['shot'].size} kept")
+    # ---- one failure-rich batch: every shot of the last batch selected, against a correction of zeros
+    faults = np.ascontiguousarray(on.last_batch("faults"))
+    zeros, ones = np.zeros_like(faults), np.ones(B, np.uint8)
+    _lib.check_dem(lib, on._dem, lib.bposd_dem_set_harvest(on._dem, K))
+    rich = []
+    for _ in range(a.rounds):
+        _lib.check_dem(lib, on._dem, lib.bposd_debug_dem_harvest(on._dem, faults.ctypes.data, zeros.ctypes.data, 1, ones.ctypes.data, B))
+        _lib.check_dem(lib, on._dem, lib.bposd_debug_dem_harvest_timing(on._dem, C.byref(ms)))
+        rich.append(ms.value)
+    info = (C.c_int64 * 3)()
+    _lib.check_dem(lib, on._dem, lib.bposd_dem_harvest_info(on._dem, info))
+    say(f"failure-rich batch (all {int(info[0])} shots selected, K = {K}): harvest kernels, HIP events, ms: {' / '.join(f'{x:.4f}' for x in rich)}; "
+        f"{B + 2 * 8 * fw * B:,} B read; batch time with such a batch: not measured (the decode of a batch that fails everywhere is another workload)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("h1922", "hgp400r3"), default="h1922")
@@ -98,15 +173,16 @@ def main():
     ap.add_argument("--host-shots", type=int, default=16384)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sample-scale", type=float, default=None, help="measure the weighted sampler against the plain one at this sample_scale")
+    ap.add_argument("--harvest", type=int, default=None, help="measure the harvest of failing shots (this many rows kept) against a plain engine")
     a = ap.parse_args()
-    if a.sample_scale is not None:
+    if a.sample_scale is not None or a.harvest is not None:
         lines = []
 
         def say(s):
             print(s, flush=True)
             lines.append(s)
 
-        weighted_probe(a, say)
+        (weighted_probe if a.sample_scale is not None else harvest_probe)(a, say)
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n\n")
