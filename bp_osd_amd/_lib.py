@@ -67,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "bposd_dem_tables",
     "bposd_dem_create",
     "bposd_dem_set_sampling",
+    "bposd_dem_set_subset",
     "bposd_dem_set_harvest",
     "bposd_dem_harvest_info",
     "bposd_dem_sample",
@@ -199,6 +200,9 @@ DEM_ITEMS = {"faults": (0, "<u8", "N"), "detectors": (1, "<u8", "M"), "observabl
              "fail_rows": (11, "<i4", "F"), "fail_weight": (12, "<i4", "F"), "fail_residual": (13, "<u8", "FN"),
              "fail_faults": (14, "<u8", "FN"), "min_residual": (15, "<u8", "1N")}
 
+
+# bposd_dem_set_subset(mode)
+DEM_SUBSET = {None: 0, "enumerate": 1, "random": 2}
 
 # bposd_mc_config.channel_update / bposd_mc_fetch(what)
 MC_UPDATE = {None: 0, "x->z": 1, "z->x": 2}
@@ -342,6 +346,8 @@ def load():
     lib.bposd_dem_create.restype = C.c_int
     lib.bposd_dem_set_sampling.argtypes = [vp, vp, vp]
     lib.bposd_dem_set_sampling.restype = C.c_int
+    lib.bposd_dem_set_subset.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
+    lib.bposd_dem_set_subset.restype = C.c_int
     lib.bposd_dem_set_harvest.argtypes = [vp, C.c_int64]
     lib.bposd_dem_set_harvest.restype = C.c_int
     lib.bposd_dem_harvest_info.argtypes = [vp, C.POINTER(C.c_int64)]

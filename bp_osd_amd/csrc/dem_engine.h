@@ -10,6 +10,15 @@ struct bposd_dem : EngineBase {
     long long sampled_B = 0, scored_B = 0;  // rows of the last batch that items 0-2 / items 3-9 hold
     long long logw_B = 0;                   // rows of the last batch that item 10 holds: sampled_B if it was drawn weighted, else 0
     bool weighted = false;                  // bposd_dem_set_sampling: draw against d_sample_priors and sum d_incr per shot
+    // bposd_dem_set_subset: shots are fault sets of a fixed weight (dem_subset_kernel).  One block holds the tables of the
+    // mode that is on: binomials (enumerate), increments (if given), support; a switch replaces it.
+    int subset_mode = 0, subset_w = 0, subset_n = 0;
+    unsigned long long subset_count = 0;  // enumerate: C(n, w), the ranks there are
+    bool subset_incr = false;             // an increment table was given: item 10 is valid
+    DevBuf subset_block;
+    const unsigned long long* d_binom = nullptr;
+    const long long* d_subset_incr = nullptr;
+    const int* d_support = nullptr;
     Event ev_sampled, ev_decoded;
     Event ev_t[4];  // around the two kernels of the last batch (bposd_debug_dem_timing)
     // device tables

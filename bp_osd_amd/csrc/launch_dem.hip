@@ -1,6 +1,6 @@
 // launch_dem.hip -- the detector-error-model Monte-Carlo engine of libbposd_mi355x.so: bposd_dem_* of include/bposd_mi355x.h.
-// One translation unit: both instances of dem_sample_kernel and dem_score_kernel (dem_kernels.hip.h) are instantiated here and
-// nowhere else.
+// One translation unit: both instances of dem_sample_kernel and dem_score_kernel (dem_kernels.hip.h) and dem_subset_kernel
+// (dem_subset_kernel.hip.h) are instantiated here and nowhere else.
 //
 // A batch is sample faults -> detectors and true observables -> one decode straight to observables -> compare -> five
 // integers.  The engine owns every buffer of it and a stream of its own; the decode goes through the decoder's
@@ -8,6 +8,7 @@
 // other by events; the host waits once per batch, for the counters.  What it shares with the other engines is engine_common.h.
 #include "dem_engine.h"
 #include "dem_kernels.hip.h"
+#include "dem_subset_kernel.hip.h"
 
 using namespace bposd_dem_dev;
 
@@ -47,8 +48,67 @@ size_t sample_lds_bytes(const bposd_dem* dem, bool weighted) {
     return 2 * sizeof(unsigned long long) * (size_t)(dem->dw + dem->ow + (weighted ? 1 : 0));
 }
 
-// dem_sample_kernel for rows [0, B) on the engine's stream, between ev_t[0] and ev_t[1]
+// every wave of a workgroup has a row of its own: accumulator words, then the fault words
+size_t subset_lds_bytes(const bposd_dem* dem) { return DEM_WAVES * sizeof(unsigned long long) * (size_t)(dem->dw + dem->ow + dem->fw); }
+
+// binom[(j - 1) * (n + 1) + c] = C(c, j) for j = 1 .. w and c = 0 .. n by Pascal's rule; an addition that overflows, and
+// every sum it enters, is 2^64 - 1.  Returns C(n, w) (saturated likewise).
+unsigned long long binomial_table(int n, int w, std::vector<unsigned long long>* out) {
+    const unsigned long long SAT = ~0ull;
+    const size_t cols = (size_t)n + 1;
+    out->assign((size_t)w * cols, 0);
+    for (int j = 1; j <= w; ++j) {
+        unsigned long long* row = out->data() + (size_t)(j - 1) * cols;
+        const unsigned long long* up = j > 1 ? row - cols : nullptr;  // C(., j - 1); row 0 is all ones
+        for (int c = 1; c <= n; ++c) {
+            const unsigned long long a = row[c - 1], b = up ? up[c - 1] : 1ull;
+            unsigned long long sum;
+            row[c] = (a == SAT || b == SAT || __builtin_add_overflow(a, b, &sum)) ? SAT : sum;
+        }
+    }
+    return w == 0 ? 1ull : (*out)[(size_t)(w - 1) * cols + (size_t)n];
+}
+
+// dem_subset_kernel for rows [0, B) on the engine's stream, between ev_t[0] and ev_t[1]
+int enqueue_subset(bposd_dem* dem, uint64_t first_shot, long long B) {
+    if (dem->subset_mode == DEM_SUBSET_ENUMERATE && (first_shot > dem->subset_count || (unsigned long long)B > dem->subset_count - first_shot))
+        return engine_fail(dem, BPOSD_ERR_INVALID, "ranks %llu .. %llu: there are only %llu sets of weight %d on %d faults", (unsigned long long)first_shot,
+                           (unsigned long long)first_shot + (unsigned long long)B - 1, dem->subset_count, dem->subset_w, dem->subset_n);
+    DemSubsetParams S{};
+    S.B = B;
+    S.first_shot = first_shot;
+    S.key0 = (uint32_t)dem->cfg.seed;
+    S.key1 = (uint32_t)(dem->cfg.seed >> 32);
+    S.mode = dem->subset_mode;
+    S.w = dem->subset_w;
+    S.n = dem->subset_n;
+    S.N = dem->N;
+    S.fw = dem->fw;
+    S.dw = dem->dw;
+    S.ow = dem->ow;
+    S.support = dem->d_support;
+    S.binom = dem->d_binom;
+    S.col_ptr = dem->d_col_ptr;
+    S.col_bits = dem->d_col_bits;
+    S.faults = dem->d_faults;
+    S.detectors = dem->d_detectors;
+    S.observables = dem->d_observables;
+    S.incr = dem->subset_incr ? dem->d_subset_incr : nullptr;
+    S.logw = dem->d_logw;
+    const unsigned grid = (unsigned)std::min<long long>((B + DEM_WAVES - 1) / DEM_WAVES, (long long)dem->num_cu * 8);
+    dem->logw_B = 0;
+    ENGINE_TRY(dem, hipEventRecord(dem->ev_t[0], dem->stream));
+    hipLaunchKernelGGL(dem_subset_kernel, dim3(grid), dim3(DEM_THREADS), subset_lds_bytes(dem), dem->stream, S);
+    ENGINE_TRY(dem, hipGetLastError());
+    ENGINE_TRY(dem, hipEventRecord(dem->ev_t[1], dem->stream));
+    if (dem->subset_incr) dem->logw_B = B;
+    return 0;
+}
+
+// the batch's sampler for rows [0, B) on the engine's stream, between ev_t[0] and ev_t[1]: dem_subset_kernel while a subset
+// mode is on, else the dem_sample_kernel instance of the engine's mode
 int enqueue_sample(bposd_dem* dem, uint64_t first_shot, long long B) {
+    if (dem->subset_mode) return enqueue_subset(dem, first_shot, B);
     DemSampleParams S{};
     S.B = B;
     S.first_shot = first_shot;
@@ -162,9 +222,11 @@ int bposd_dem_set_sampling(bposd_dem* dem, const double* sample_priors, const in
         return engine_fail(dem, BPOSD_ERR_INVALID, "sample_priors and incr go together: give both, or NULL for both to sample plainly");
     if (!sample_priors) {  // back to the model's own priors; the tables stay allocated for the next switch
         dem->weighted = false;
-        dem->logw_B = 0;
+        if (!dem->subset_mode) dem->logw_B = 0;
         return BPOSD_OK;
     }
+    if (dem->subset_mode)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "the engine draws fault sets of a fixed weight (bposd_dem_set_subset): switch that off before weighted sampling");
     // everything is validated before anything changes: a refusal leaves the engine in the mode it was in
     if (const int64_t bad = bposd_host::first_bad_prob(sample_priors, dem->N))
         return engine_fail(dem, BPOSD_ERR_INVALID, "the sampling probability of fault %d (%g) is not a probability", (int)bad - 1, sample_priors[bad - 1]);
@@ -188,6 +250,79 @@ int bposd_dem_set_sampling(bposd_dem* dem, const double* sample_priors, const in
     ENGINE_TRY(dem, hipMemcpy(dem->d_sample_priors, sample_priors, sizeof(double) * (size_t)dem->N, hipMemcpyHostToDevice));
     ENGINE_TRY(dem, hipMemcpy(dem->d_incr, incr, sizeof(int64_t) * (size_t)dem->N, hipMemcpyHostToDevice));
     dem->weighted = true;
+    return BPOSD_OK;
+}
+
+int bposd_dem_set_subset(bposd_dem* dem, int32_t mode, int32_t weight, const int32_t* support, int32_t n_support, const int64_t* incr) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (mode == BPOSD_DEM_SUBSET_OFF) {  // back to Bernoulli rows; the tables stay until the next switch replaces them
+        if (dem->subset_mode) dem->logw_B = 0;
+        dem->subset_mode = 0;
+        return BPOSD_OK;
+    }
+    // everything is validated before anything changes: a refusal leaves the engine in the mode it was in
+    if (mode != BPOSD_DEM_SUBSET_ENUMERATE && mode != BPOSD_DEM_SUBSET_RANDOM)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "mode = %d is not BPOSD_DEM_SUBSET_OFF, _ENUMERATE or _RANDOM", mode);
+    if (dem->weighted)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "weighted sampling is on (bposd_dem_set_sampling): switch that off before drawing fault sets of a fixed weight");
+    const int n = support ? n_support : dem->N;
+    if (n < 0 || n > dem->N) return engine_fail(dem, BPOSD_ERR_INVALID, "n_support = %d is outside [0, %d]", n, dem->N);
+    for (int c = 0; support && c < n; ++c) {
+        if (support[c] < 0 || support[c] >= dem->N)
+            return engine_fail(dem, BPOSD_ERR_INVALID, "support[%d] = %d is outside [0, %d)", c, support[c], dem->N);
+        if (c && support[c] <= support[c - 1])
+            return engine_fail(dem, BPOSD_ERR_INVALID, "support[%d] = %d does not ascend strictly (support[%d] = %d)", c, support[c], c - 1, support[c - 1]);
+    }
+    if (weight < 0 || weight > std::min(n, DEM_SUBSET_MAX_WEIGHT))
+        return engine_fail(dem, BPOSD_ERR_INVALID, "weight = %d is outside [0, min(n = %d, %d)]", weight, n, DEM_SUBSET_MAX_WEIGHT);
+    std::vector<unsigned long long> binom;
+    unsigned long long count = 0;
+    if (mode == BPOSD_DEM_SUBSET_ENUMERATE) {
+        count = binomial_table(n, weight, &binom);
+        if (count >= (1ull << 63))
+            return engine_fail(dem, BPOSD_ERR_INVALID, "C(%d, %d) is 2^63 or more: the sets of weight %d cannot be enumerated by a 63-bit rank", n, weight, weight);
+    }
+    if (incr)
+        for (int c = 0; c < n; ++c) {
+            const int i = support ? support[c] : c;
+            const unsigned long long a = incr[i] < 0 ? 0ull - (unsigned long long)incr[i] : (unsigned long long)incr[i];
+            if (weight && a >= ((1ull << 62) + weight - 1) / weight)  // weight * a >= 2^62
+                return engine_fail(dem, BPOSD_ERR_INVALID, "%d times the increment of fault %d is 2^62 or more in magnitude: a shot's log-weight could overflow", weight, i);
+        }
+    if (subset_lds_bytes(dem) > 64 * 1024)
+        return engine_fail(dem, BPOSD_ERR_UNSUPPORTED, "fault sets of a fixed weight need %zu bytes of LDS per workgroup, more than 65536", subset_lds_bytes(dem));
+    DeviceGuard guard(dem->device);
+    ENGINE_TRY(dem, guard.err);
+    ENGINE_TRY(dem, hipStreamSynchronize(dem->stream));  // no sampler is reading the tables
+    // the new block is whole before the engine changes: binomials, increments, support, each from a 256-byte boundary
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_binom = pad(8 * binom.size()), b_incr = pad(incr ? 8 * (size_t)dem->N : 0), b_supp = pad(4 * (size_t)n);
+    std::vector<int32_t> ident;
+    if (!support) {
+        ident.resize((size_t)n);
+        for (int c = 0; c < n; ++c) ident[c] = c;
+        support = ident.data();
+    }
+    DevBuf fresh;
+    ENGINE_TRY(dem, fresh.alloc(std::max<size_t>(b_binom + b_incr + b_supp, 256)));
+    char* const base = (char*)fresh.p;
+    if (!binom.empty()) ENGINE_TRY(dem, hipMemcpy(base, binom.data(), 8 * binom.size(), hipMemcpyHostToDevice));
+    if (incr) ENGINE_TRY(dem, hipMemcpy(base + b_binom, incr, 8 * (size_t)dem->N, hipMemcpyHostToDevice));
+    if (n) ENGINE_TRY(dem, hipMemcpy(base + b_binom + b_incr, support, 4 * (size_t)n, hipMemcpyHostToDevice));
+    int rc;
+    if (incr && !dem->d_logw.p && (rc = engine_alloc(dem, dem->d_logw, (size_t)dem->capacity))) return rc;
+    dem->device_bytes -= dem->subset_block.bytes;
+    dem->device_bytes += fresh.bytes;
+    dem->subset_block = std::move(fresh);  // (what the engine held goes with `fresh`)
+    dem->d_binom = (const unsigned long long*)base;
+    dem->d_subset_incr = (const long long*)(base + b_binom);
+    dem->d_support = (const int*)(base + b_binom + b_incr);
+    dem->subset_mode = mode;
+    dem->subset_w = weight;
+    dem->subset_n = n;
+    dem->subset_count = count;
+    dem->subset_incr = incr != nullptr;
+    dem->logw_B = 0;  // what item 10 held was summed from a table that went
     return BPOSD_OK;
 }
 
@@ -285,10 +420,12 @@ int bposd_dem_run(bposd_dem* dem, uint64_t first_shot, int64_t B, int64_t counte
 int bposd_dem_fetch(bposd_dem* dem, int32_t what, void* host_dst, size_t bytes) {
     if (!dem) return BPOSD_ERR_INVALID;
     // the engine's own preconditions (for a batch that has run: engine_fetch refuses where none has)
-    if (what == BPOSD_DEM_LOGW && !dem->weighted)
+    if (what == BPOSD_DEM_LOGW && dem->subset_mode && !dem->subset_incr)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs an increment table: bposd_dem_set_subset was given none", what);
+    if (what == BPOSD_DEM_LOGW && !dem->weighted && !dem->subset_mode)
         return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs weighted sampling (bposd_dem_set_sampling): this engine samples plainly", what);
     if (what == BPOSD_DEM_LOGW && dem->logw_B != dem->sampled_B)
-        return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs a batch sampled since bposd_dem_set_sampling", what);
+        return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs a batch sampled since bposd_dem_set_sampling / bposd_dem_set_subset", what);
     if (what >= BPOSD_DEM_OBS_BP && what <= BPOSD_DEM_OBS_FAIL && dem->sampled_B && dem->scored_B == 0)
         return engine_fail(dem, BPOSD_ERR_INVALID, "item %d needs bposd_dem_run: the last batch was sampled only", what);
     if (what >= BPOSD_DEM_FAIL_ROWS && what <= BPOSD_DEM_MIN_RESIDUAL && !dem->hv.last_on)

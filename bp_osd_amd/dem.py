@@ -17,6 +17,11 @@ the decoder keeps ``priors`` as its channel, and weighs every shot by its likeli
 over the number of shots become measurable.  The per-shot log-weight is an integer sum (``importance_table``), so it is
 bit-exact on both engines like everything else of a shot.
 
+Fault sets of a fixed weight (``fault_weight`` / ``subset``) replace the Bernoulli row of a shot by a set of
+exactly ``w`` mechanisms: every set of the stratum in turn, or uniformly drawn ones (``fault_subsets`` is the definition).
+``dem_failure_spectrum`` runs the strata of weight 0, 1, ... and returns the weight up to which the decoder corrects every
+fault set, and a logical error rate with a rigorous interval.
+
 ``phenomenological_dem`` builds ``(H, L, priors)`` of the repeated-measurement model of a code, so that the engine can be
 used with no circuit simulator at hand; INTEGRATION.md says how the three come out of a detector-error-model file.
 """
@@ -29,9 +34,10 @@ import numpy as np
 import scipy.sparse as sp
 
 from ._dem_base import HARVEST_ITEMS, DemSimBase, _gf2_csr, _pack, checked_model, create_dem, harvest_batch
-from .sim import _default_decoder_factory, _mod2_mul, philox_uniforms
+from .sim import _default_decoder_factory, _mod2_mul, philox4x32_10, philox_uniforms
 
-__all__ = ["dem_decode_sim", "importance_table", "phenomenological_dem", "phenomenological_detector_times"]
+__all__ = ["dem_decode_sim", "dem_failure_spectrum", "fault_subsets", "importance_table", "phenomenological_dem",
+           "phenomenological_detector_times", "subset_table", "weight_distribution"]
 
 def phenomenological_dem(h, l, rounds, p_data, p_meas):
     """``(H, L, priors)`` of the phenomenological noise model of a code with checks ``h`` (m x n) and logicals ``l`` (k x n)
@@ -109,6 +115,114 @@ def importance_table(priors, sample_priors):
     return incr, math.fsum(c_terms)
 
 
+SUBSET_MODES = ("enumerate", "random")
+SUBSET_MAX_WEIGHT = 64  # one lane of a wave per element of a set
+
+
+def fault_subsets(seed, first_shot, B, n, w, mode):
+    """int64 [B, w]: the fault sets of global shots ``first_shot .. first_shot + B - 1``, each ``w`` ascending positions in
+    ``range(n)`` -- the definition the device sampler (dem_subset_kernel) is held against bit for bit.
+
+    ``mode="enumerate"``: shot s is the set of rank s in colexicographic order (the combinatorial number system): from
+    r = s, for j = w .. 1, c_j = the largest c with C(c, j) <= r and r -= C(c_j, j); the set is {c_1 < ... < c_w}.  Needs
+    C(n, w) < 2^63 and ``first_shot + B <= C(n, w)``.  ``mode="random"``: Floyd's algorithm on the Philox stream.  Step
+    i = 0 .. w - 1 with j = n - w + i draws from counter (s lo, s hi, i >> 1, 1) -- the fourth word 1 keeps it apart from the
+    Bernoulli stream -- u = o[2 (i & 1)] | o[2 (i & 1) + 1] << 32, t = (u (j + 1)) >> 64, and takes j if t is already in the
+    set, else t.  Every w-subset is equally likely up to the multiply-shift bias (j + 1) / 2^64 per step."""
+    n, w, B, first_shot = int(n), int(w), int(B), int(first_shot)
+    if mode not in SUBSET_MODES:
+        raise ValueError(f"mode must be one of {SUBSET_MODES}, not {mode!r}")
+    if not 0 <= w <= min(n, SUBSET_MAX_WEIGHT):
+        raise ValueError(f"the weight {w} is outside [0, min(n = {n}, {SUBSET_MAX_WEIGHT})]")
+    if B < 0 or first_shot < 0:
+        raise ValueError("first_shot and B must be >= 0")
+    out = np.zeros((B, w), np.int64)
+    if mode == "enumerate":
+        count = math.comb(n, w)
+        if count >= 2 ** 63:
+            raise ValueError(f"C({n}, {w}) is 2^63 or more: the sets of weight {w} cannot be enumerated by a 63-bit rank")
+        if first_shot + B > count:
+            raise ValueError(f"ranks {first_shot} .. {first_shot + B - 1}: there are only {count} sets of weight {w} on {n} faults")
+        r = np.arange(B, dtype=np.uint64) + np.uint64(first_shot)
+        for j in range(w, 0, -1):  # (a rank is below 2^63, so an entry clamped to 2^63 compares as the true one would)
+            row = np.array([min(math.comb(c, j), 2 ** 63) for c in range(n + 1)], dtype=np.uint64)
+            c = np.searchsorted(row, r, side="right").astype(np.int64) - 1
+            r = r - row[c]
+            out[:, j - 1] = c
+        return out
+    seed = int(seed) & (2 ** 64 - 1)
+    s = (np.arange(B, dtype=np.uint64) + np.uint64(first_shot & (2 ** 64 - 1)))[:, None]
+    pair = np.arange((w + 1) // 2, dtype=np.uint64)[None, :]
+    o = philox4x32_10((s & np.uint64(0xFFFFFFFF), s >> np.uint64(32), pair, 1), (seed & 0xFFFFFFFF, seed >> 32))
+    o = [np.broadcast_to(x, (B, pair.shape[1])) for x in o]
+    chosen = np.full((B, w), -1, np.int64)
+    for i in range(w):
+        j = n - w + i
+        lo, hi = o[2 * (i & 1)][:, i >> 1], o[2 * (i & 1) + 1][:, i >> 1]
+        m = np.uint64(j + 1)  # (u m) >> 64 from the 32-bit halves of u: every product stays below 2^64 for m < 2^32
+        t = ((hi * m + ((lo * m) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64)
+        taken = (chosen[:, :i] == t[:, None]).any(axis=1)
+        chosen[:, i] = np.where(taken, j, t)
+    return np.sort(chosen, axis=1)
+
+
+def _checked_support(support, N):
+    a = np.asarray(support)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("support must be a vector of fault indices")
+    a = a.astype(np.int64)
+    if a.size and (a[0] < 0 or a[-1] >= N or (np.diff(a) <= 0).any() or a.min() < 0 or a.max() >= N):
+        raise ValueError(f"support must be strictly ascending fault indices in [0, {N})")
+    return a
+
+
+def subset_table(priors, support):
+    """``(incr int64 [N], c0 float)`` of the probability of a fault set under ``priors``: for a set S of the support (and no
+    fault outside S firing) ``P(S) = exp(c0 + sum_{i in S} incr[i] / 2**32)`` with ``incr[i] = round(log(p_i / (1 - p_i)) 2^32)``
+    on the support (0 elsewhere) and ``c0 = sum_support log1p(-p_i)`` -- the integers both engines sum per shot.  A support
+    entry with a prior outside (0, 1) is a ValueError.  Scalar ``math`` and ``fsum``, as :func:`importance_table`."""
+    p = np.ascontiguousarray(priors, dtype=np.float64)
+    if p.ndim != 1:
+        raise ValueError("priors must be a vector")
+    sup = _checked_support(support, p.shape[0])
+    incr = np.zeros(p.shape[0], np.int64)
+    terms = []
+    for i in sup.tolist():
+        pi = float(p[i])
+        if not 0.0 < pi < 1.0:
+            raise ValueError(f"the prior of fault {i} ({pi}) is not inside (0, 1): the fault belongs to no stratum of the support")
+        incr[i] = int(round((math.log(pi) - math.log1p(-pi)) * LOGW_ONE))
+        terms.append(math.log1p(-pi))
+    return incr, math.fsum(terms)
+
+
+def _weight_dp(priors, max_weight, support):
+    """(P(|f| = w) for w = 0 .. max_weight, P(|f| > max_weight)) over the faults of the support, each firing independently."""
+    p = np.ascontiguousarray(priors, dtype=np.float64)
+    if p.ndim != 1 or ((p < 0) | (p > 1) | np.isnan(p)).any():
+        raise ValueError("priors must be a vector of probabilities")
+    if support is not None:
+        p = p[_checked_support(support, p.shape[0])]
+    W = int(max_weight)
+    if W < 0:
+        raise ValueError("max_weight must be >= 0")
+    dist = np.zeros(W + 1, np.float64)
+    dist[0], tail = 1.0, 0.0
+    for pi in p.tolist():  # one more fault: a set keeps its weight or gains one
+        tail += dist[W] * pi
+        dist[1:] = dist[1:] * (1.0 - pi) + dist[:-1] * pi
+        dist[0] *= 1.0 - pi
+    return dist, tail
+
+
+def weight_distribution(priors, max_weight, support=None):
+    """float64 [max_weight + 1]: ``P(|f| = w)`` for w = 0 .. max_weight of the faults of ``support`` (default all) firing
+    independently with ``priors``: ``prod (1 - p_i)`` times the elementary symmetric polynomial ``e_w`` of the odds
+    ``p_i / (1 - p_i)``, by the recurrence over the faults -- O(n max_weight), every term non-negative (kept in probabilities,
+    so that a prior of 0 or 1 needs no special case)."""
+    return _weight_dp(priors, max_weight, support)[0]
+
+
 class dem_decode_sim(DemSimBase):
     """See the module docstring.
 
@@ -125,6 +239,12 @@ class dem_decode_sim(DemSimBase):
     sample_priors, sample_scale : importance sampling, at most one of the two.  ``sample_priors`` = q, N floats in [0, 1] the
         faults are drawn against (``u(s, i) < q_i``: the same stream and counter) while the decoder keeps ``priors``;
         ``sample_scale`` = beta >= 1 is ``q_i = p_i`` where ``p_i >= 0.5``, else ``min(beta * p_i, 0.5)``.  See below
+    fault_weight, subset, support : fault sets of a fixed weight in place of Bernoulli rows (both or neither of the first two;
+        they exclude ``sample_priors`` / ``sample_scale``).  A shot is a set of exactly ``fault_weight`` = w of the n faults of
+        ``support`` (ascending indices; default the faults with 0 < p < 1; a fault with p = 1 belongs to no stratum and is a
+        ValueError): ``subset="enumerate"`` runs the sets in colexicographic order, shot s being rank s -- ``target_runs``
+        then defaults to C(n, w) and may not exceed it -- and ``subset="random"`` draws them uniformly (:func:`fault_subsets`
+        defines both).  See below
     harvest : K, an int >= 0 (default 0: off).  With K > 0 the failing shots are harvested: a shot whose osdw
         observables are wrong leaves the residual ``faults ^ osdw correction``, an undetected logical fault set.  Results:
         ``min_logical_weight`` (the least residual weight of the run, an upper bound of the model's fault distance; None if
@@ -145,19 +265,45 @@ class dem_decode_sim(DemSimBase):
     ``effective_sample_fraction = sum(w)^2 / (n sum(w^2))`` says how many plain shots the weighted ones are worth; both and
     ``sample_scale`` appear in :meth:`output_dict` only then.  The ``*_count`` attributes stay unweighted counts of the shots
     as sampled, and ``osdw_observable_error_rates`` stays unweighted too (failures per sampled shot, not a rate under
-    ``priors``).  ``last_batch("logw")`` is the int64 log-weight of every shot of the last batch."""
+    ``priors``).  ``last_batch("logw")`` is the int64 log-weight of every shot of the last batch.
+
+    With fault sets of a fixed weight the counts and ``*_logical_error_rate`` keep their meaning: the unweighted fraction of
+    the sets that were run.  New are ``stratum_size`` = C(n, w) (a Python int), ``stratum_mass`` = P(|f| = w) under ``priors``
+    (:func:`weight_distribution`) and ``{bp,osd0,osdw}_failure_mass = C(n, w) / runs * sum_fail exp(c0 + logw / 2**32)``
+    with the table of :func:`subset_table` -- the estimate of P(|f| = w and the decoder fails), whose sum over w is the
+    logical error rate -- and ``*_failure_mass_eb = sqrt(max(C(n, w)^2 sum_fail P^2 / runs - mass^2, 0) / runs)``, exactly 0.0
+    once the whole stratum was enumerated.  ``last_batch("logw")`` is the log-probability of every set in units of 2^-32,
+    less c0.  :func:`dem_failure_spectrum` runs the strata one after the other."""
 
     _COUNTS = ("bp_converge_count", "bp_success_count", "osd0_success_count", "osdw_success_count", "trivial_count")
     _RATES = ("bp", "osd0", "osdw")
 
-    def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=100, decoder_factory=None, run_sim=True,
-                 sample_priors=None, sample_scale=None, harvest=0, **decoder_kwargs):
+    def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=None, decoder_factory=None, run_sim=True,
+                 sample_priors=None, sample_scale=None, harvest=0, fault_weight=None, subset=None, support=None, **decoder_kwargs):
         self._check_engine(engine, decoder_factory, "decoder")
         self._H, self._L, self._priors = checked_model(H, L, priors)
         self.M, self.N = self._H.shape
         self.K = self._L.shape[0]
-        self._init_harvest(harvest, with_logw=sample_priors is not None or sample_scale is not None)
+        if (fault_weight is None) != (subset is None):
+            raise ValueError("fault_weight and subset go together: give both, or neither to sample Bernoulli rows")
+        if subset is None and support is not None:
+            raise ValueError("support belongs to fault sets of a fixed weight (fault_weight and subset)")
+        if subset is not None and (sample_priors is not None or sample_scale is not None):
+            raise ValueError("fault sets of a fixed weight exclude sample_priors / sample_scale")
+        self._init_harvest(harvest, with_logw=sample_priors is not None or sample_scale is not None or subset is not None)
         p = self._priors
+        self._subset = self.fault_weight = None
+        self._shot0 = 0  # global shot of the run's first
+        if subset is not None:
+            if support is None:
+                if (p == 1.0).any():
+                    raise ValueError(f"the prior of fault {int(np.flatnonzero(p == 1.0)[0])} is 1: it belongs to no stratum of a fixed weight")
+                support = np.flatnonzero((p > 0.0) & (p < 1.0))
+            self._support = _checked_support(support, self.N)
+            self._subset_incr, self._subset_c0 = subset_table(p, self._support)
+            target_runs = self._init_stratum(fault_weight, subset, target_runs)
+        elif target_runs is None:
+            target_runs = 100
         if sample_priors is not None and sample_scale is not None:
             raise ValueError("give sample_priors or sample_scale, not both")
         self.sample_scale = None
@@ -176,6 +322,8 @@ class dem_decode_sim(DemSimBase):
             self._wsum = dict.fromkeys(("w", "w2", "bp", "bp2", "osd0", "osd02", "osdw", "osdw2"), 0.0)
             self.weight_mean = self.effective_sample_fraction = 0.0
         self._init_run(batch_size, seed, target_runs)
+        if self._subset:
+            self._reset_stratum_sums()
         self._dem = None
         if engine == "native":
             from .decoder import BpOsdDecoder
@@ -196,6 +344,16 @@ class dem_decode_sim(DemSimBase):
         self.decoder._observables_installed(self.K)  # bposd_dem_create has set the decoder's table
         if self._tilted:
             _lib.check_dem(lib, dem, lib.bposd_dem_set_sampling(dem, self._sample_priors.ctypes.data, self._incr.ctypes.data))
+        if self._subset:
+            self._native_set_subset()
+
+    def _native_set_subset(self):
+        from . import _lib
+
+        sup = np.ascontiguousarray(self._support, dtype=np.int32)
+        rc = self._lib.bposd_dem_set_subset(self._dem, _lib.DEM_SUBSET[self._subset], self.fault_weight, sup.ctypes.data, sup.size,
+                                            self._subset_incr.ctypes.data)
+        _lib.check_dem(self._lib, self._dem, rc)
 
     def _run_batch_native(self, B):
         import ctypes as C
@@ -203,16 +361,18 @@ class dem_decode_sim(DemSimBase):
         from . import _lib
 
         c = (C.c_int64 * 5)()
-        first, ask = self.run_count, None
+        first, ask = self._shot0 + self.run_count, None
         if self.harvest:
             ask = self._harvest_ask()
             self._set_native_harvest(self._dem, "bposd_dem_set_harvest", _lib.check_dem, ask)
         _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_run(self._dem, int(first), int(B), c))
         self._last_B = B
         self._accumulate(B, [int(v) for v in c], self.last_batch("obs_fail"))
-        logw = self.last_batch("logw") if self._tilted else None
+        logw = self.last_batch("logw") if self._tilted or self._subset else None
         if self._tilted:
             self._accumulate_weighted(self.last_batch("flags"), self.last_batch("converged"), logw)
+        if self._subset:
+            self._accumulate_stratum(self.last_batch("flags"), self.last_batch("converged"), logw)
         if self.harvest:
             info = self._native_harvest_triple(self._dem, "bposd_dem_harvest_info", _lib.check_dem)
             self._accumulate_harvest(first, info, ask, logw)
@@ -234,8 +394,14 @@ class dem_decode_sim(DemSimBase):
 
     # ------------------------------------------------------------------ the host loop
     def _run_batch_numpy(self, B):
-        drawn = self._sample_priors if self._tilted else self._priors
-        faults = (philox_uniforms(self.seed, self.run_count, B, self.N) < drawn).astype(np.uint8)
+        first = self._shot0 + self.run_count
+        if self._subset:
+            pos = fault_subsets(self.seed, first, B, self._support.size, self.fault_weight, self._subset)
+            faults = np.zeros((B, self.N), np.uint8)
+            faults[np.arange(B)[:, None], self._support[pos]] = 1
+        else:
+            drawn = self._sample_priors if self._tilted else self._priors
+            faults = (philox_uniforms(self.seed, first, B, self.N) < drawn).astype(np.uint8)
         detectors = _mod2_mul(self._H, faults)
         truth = _mod2_mul(self._L, faults)
         r = self.decoder.decode_batch(detectors)
@@ -258,11 +424,13 @@ class dem_decode_sim(DemSimBase):
                       "iters": iters.astype(np.int32), "obs_fail": obs_fail}
         counters = [int(conv.sum()), int((conv & ~wrong["bp"]).sum()), int((~wrong["osd0"]).sum()), int((~wrong["osdw"]).sum()),
                     int(quiet.sum())]
-        first = self.run_count
         self._accumulate(B, counters, obs_fail)
         if self._tilted:
             self._last["logw"] = faults.astype(np.int64) @ self._incr
             self._accumulate_weighted(flags, self._last["converged"], self._last["logw"])
+        if self._subset:
+            self._last["logw"] = faults.astype(np.int64) @ self._subset_incr
+            self._accumulate_stratum(flags, self._last["converged"], self._last["logw"])
         if self.harvest:  # the osdw failures, against the osdw rows
             ask = self._harvest_ask()
             h = harvest_batch(faults, rows["osdw"], wrong["osdw"], ask)
@@ -290,6 +458,71 @@ class dem_decode_sim(DemSimBase):
         self.weight_mean = S["w"] / n
         self.effective_sample_fraction = S["w"] * S["w"] / (n * S["w2"])
 
+    # ------------------------------------------------------------------ fault sets of a fixed weight
+    def _init_stratum(self, fault_weight, subset, target_runs):
+        """Checks the stratum (w, mode) against the support; sets its results and returns the run's ``target_runs``."""
+        n = self._support.size
+        if subset not in SUBSET_MODES:
+            raise ValueError(f"subset must be one of {SUBSET_MODES}, not {subset!r}")
+        if isinstance(fault_weight, bool) or not isinstance(fault_weight, (int, np.integer)) or not 0 <= fault_weight <= min(n, SUBSET_MAX_WEIGHT):
+            raise ValueError(f"fault_weight must be an int in [0, min(n = {n}, {SUBSET_MAX_WEIGHT})], not {fault_weight!r}")
+        w = int(fault_weight)
+        size = math.comb(n, w)
+        if subset == "enumerate":
+            if size >= 2 ** 63:
+                raise ValueError(f"C({n}, {w}) is 2^63 or more: the sets of weight {w} cannot be enumerated by a 63-bit rank")
+            if target_runs is None:
+                target_runs = size
+            if self._shot0 + int(target_runs) > size:
+                raise ValueError(f"target_runs = {target_runs}: there are only {size} sets of weight {w} on {n} faults")
+        elif target_runs is None:
+            target_runs = 100
+        self._subset, self.fault_weight = subset, w
+        self.stratum_size = size
+        self.stratum_mass = float(weight_distribution(self._priors, w, self._support)[w])
+        return target_runs
+
+    def _reset_stratum_sums(self):
+        self._ssum = dict.fromkeys(("bp", "bp2", "osd0", "osd02", "osdw", "osdw2"), 0.0)
+        for key in self._RATES:
+            setattr(self, f"{key}_failure_mass", 0.0)
+            setattr(self, f"{key}_failure_mass_eb", 0.0)
+
+    def set_fault_weight(self, fault_weight, subset, target_runs=None, first_shot=0):
+        """Another stratum on the same model, decoder and engine (a sim made with ``fault_weight`` / ``subset`` only): the run
+        starts over at global shot ``first_shot`` with its counters, sums and harvest reset; :meth:`run_decode_sim` runs it."""
+        if not self._subset:
+            raise ValueError("set_fault_weight needs a sim made with fault_weight and subset")
+        first_shot = int(first_shot)
+        if first_shot < 0:
+            raise ValueError("first_shot must be >= 0")
+        keep, self._shot0 = self._shot0, first_shot
+        try:
+            target_runs = self._init_stratum(fault_weight, subset, target_runs)
+        except ValueError:
+            self._shot0 = keep
+            raise
+        self._init_harvest(self.harvest, with_logw=True)
+        self._init_run(self._batch_size, self.seed, target_runs)
+        self._reset_stratum_sums()
+        if self._dem is not None:
+            self._native_set_subset()
+
+    def _accumulate_stratum(self, flags, converged, logw):
+        """The failure masses of the run so far (after ``_accumulate``) from one more batch's flags, convergence and integer
+        log-probabilities: the same arithmetic on either engine."""
+        pr = np.exp(self._subset_c0 + np.asarray(logw, dtype=np.int64) / LOGW_ONE)  # P(set) under the priors
+        flags = np.asarray(flags)
+        fail = {"bp": ((flags & 1) != 0) | (np.asarray(converged) == 0), "osd0": (flags & 2) != 0, "osdw": (flags & 4) != 0}
+        S, n, C = self._ssum, self.run_count, self.stratum_size
+        whole = self._subset == "enumerate" and n == C
+        for key, f in fail.items():
+            S[key] += float(pr[f].sum())
+            S[key + "2"] += float((pr[f] * pr[f]).sum())
+            mass = (C / n) * S[key]
+            setattr(self, f"{key}_failure_mass", mass)
+            setattr(self, f"{key}_failure_mass_eb", 0.0 if whole else math.sqrt(max((C / n) * C * S[key + "2"] - mass * mass, 0.0) / n))
+
     def last_batch(self, what):
         """One array of the last batch: "faults", "detectors", "observables" (the true ones), "obs_bp", "obs_osd0", "obs_osdw"
         (bit-packed rows, uint64 [B, ceil(./64)]: ``BpOsdDecoder.unpack_rows`` expands them), "flags" (uint8 [B]: bit 0 bp
@@ -302,8 +535,8 @@ class dem_decode_sim(DemSimBase):
 
         if what not in _lib.DEM_ITEMS:
             raise ValueError(f"what must be one of {sorted(_lib.DEM_ITEMS)}")
-        if what == "logw" and not self._tilted:
-            raise ValueError("last_batch('logw') needs importance sampling (sample_priors or sample_scale)")
+        if what == "logw" and not self._tilted and not self._subset:
+            raise ValueError("last_batch('logw') needs importance sampling (sample_priors or sample_scale) or fault sets of a fixed weight")
         self._check_harvest_item(what)
         return self._last_batch(what, lambda: self._fetch(_lib.DEM_ITEMS, self._dem, self._lib.bposd_dem_fetch, _lib.check_dem, what))
 
@@ -314,6 +547,67 @@ class dem_decode_sim(DemSimBase):
             out["sample_scale"] = self.sample_scale
             out["weight_mean"] = float(self.weight_mean)
             out["effective_sample_fraction"] = float(self.effective_sample_fraction)
+        if self._subset:
+            out.update(fault_weight=self.fault_weight, subset=self._subset, stratum_size=self.stratum_size, stratum_mass=self.stratum_mass)
+            for key in self._RATES:
+                out[f"{key}_failure_mass"] = float(getattr(self, f"{key}_failure_mass"))
+                out[f"{key}_failure_mass_eb"] = float(getattr(self, f"{key}_failure_mass_eb"))
         if self.harvest:
             out["min_logical_weight"] = self.min_logical_weight
         return json.dumps(out, sort_keys=True, indent=4)
+
+
+def dem_failure_spectrum(H, L, priors, max_weight, shots_per_weight, batch_size=4096, engine="native", seed=0, support=None,
+                         decoder_factory=None, harvest=0, **decoder_kwargs):
+    """The decoder's failures by fault weight: the strata w = 0 .. ``max_weight`` of fault sets of exactly w of the n faults of
+    ``support`` (default: those with 0 < p < 1), one :class:`dem_decode_sim` run each on one decoder.  A stratum with
+    C(n, w) <= ``shots_per_weight`` is enumerated whole -- no statistical error -- and a larger one is estimated from
+    ``shots_per_weight`` uniformly drawn sets (stratum w draws from global shot ``w << 40`` on, so that the strata do not share
+    draws).  Returns a dict:
+
+    ``strata`` : per weight a dict of ``weight``, ``mode`` ("enumerate" / "random"), ``stratum_size``, ``stratum_mass``,
+        ``runs``, ``{bp,osd0,osdw}_failures`` (failing sets among those run) and ``{bp,osd0,osdw}_failure_mass`` with ``_eb``;
+        with ``harvest=K`` also ``failures`` (the first K failing sets, as ``dem_decode_sim.failures``) and ``min_logical_weight``
+    ``logical_error_rate_lower`` (+ ``_eb``, the drawn strata's error bars in quadrature) : the sum of the osdw failure masses
+    ``tail_mass`` : P(|f| > max_weight).  The osdw logical error rate lies in [lower, lower + tail_mass], up to the error bars
+        of the drawn strata
+    ``corrected_weight`` : the largest t such that every stratum <= t was enumerated whole and none of its sets failed under
+        osdw -- "the decoder, with these settings, corrects every fault set up to weight t", proved; -1 if weight 0 fails
+    ``min_failing_weight`` : the least weight at which a set that was run failed under osdw (None if none did)"""
+    shots = int(shots_per_weight)
+    if shots < 1:
+        raise ValueError("shots_per_weight must be >= 1")
+    max_weight = int(max_weight)
+    sim = dem_decode_sim(H, L, priors, batch_size=batch_size, engine=engine, seed=seed, decoder_factory=decoder_factory, run_sim=False,
+                         harvest=harvest, fault_weight=0, subset="enumerate", support=support, **decoder_kwargs)
+    n = sim._support.size
+    if not 0 <= max_weight <= min(n, SUBSET_MAX_WEIGHT):
+        raise ValueError(f"max_weight must be in [0, min(n = {n}, {SUBSET_MAX_WEIGHT})], not {max_weight}")
+    strata, proved, corrected, first_fail = [], True, -1, None
+    for w in range(max_weight + 1):
+        whole = math.comb(n, w) <= shots
+        if whole:
+            sim.set_fault_weight(w, "enumerate")
+        else:
+            sim.set_fault_weight(w, "random", target_runs=shots, first_shot=w << 40)
+        sim.run_decode_sim()
+        runs = sim.run_count
+        row = {"weight": w, "mode": "enumerate" if whole else "random", "stratum_size": sim.stratum_size, "stratum_mass": sim.stratum_mass,
+               "runs": runs, "bp_failures": runs - sim.bp_success_count, "osd0_failures": runs - sim.osd0_success_count,
+               "osdw_failures": runs - sim.osdw_success_count}
+        for key in sim._RATES:
+            row[f"{key}_failure_mass"] = getattr(sim, f"{key}_failure_mass")
+            row[f"{key}_failure_mass_eb"] = getattr(sim, f"{key}_failure_mass_eb")
+        if sim.harvest:
+            row["failures"] = sim.failures
+            row["min_logical_weight"] = sim.min_logical_weight
+        strata.append(row)
+        if row["osdw_failures"] and first_fail is None:
+            first_fail = w
+        proved = proved and whole and not row["osdw_failures"]
+        if proved:
+            corrected = w
+    return {"strata": strata, "logical_error_rate_lower": math.fsum(r["osdw_failure_mass"] for r in strata),
+            "logical_error_rate_lower_eb": math.sqrt(math.fsum(r["osdw_failure_mass_eb"] ** 2 for r in strata)),
+            "tail_mass": float(_weight_dp(sim._priors, max_weight, sim._support)[1]), "corrected_weight": corrected,
+            "min_failing_weight": first_fail}

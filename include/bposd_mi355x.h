@@ -505,8 +505,49 @@ int bposd_dem_create(const bposd_dem_config *cfg, bposd_handle *dec, const int32
  */
 int bposd_dem_set_sampling(bposd_dem *dem, const double *sample_priors, const int64_t *incr);
 
+/*
+ * Fault sets of a fixed weight: a shot is then not a Bernoulli row but a set of exactly `weight` = w of the n mechanisms of
+ * a support -- every set of a stratum in turn (a proof that the decoder corrects all of them, or the list of those it does
+ * not), or sets drawn uniformly (stratified sampling: LER = sum_w P(|f| = w, fail)).  support[n_support] is an ascending
+ * list of distinct fault indices, NULL stands for all N (n_support is then ignored); position c of a set is fault
+ * support[c]; 0 <= w <= min(n, 64).
+ *
+ *   BPOSD_DEM_SUBSET_ENUMERATE: global shot s is the set of rank s in colexicographic order (the combinatorial number
+ *     system): from r = s, for j = w .. 1, c_j = the largest c with C(c, j) <= r, r -= C(c_j, j); the set is
+ *     {c_1 < ... < c_w}.  Ranks 0 .. 4 of n = 7, w = 3 are (0,1,2), (0,1,3), (0,2,3), (1,2,3), (0,1,4); the last is (4,5,6);
+ *     w = 0 is the one empty set.  C(n, w) must be below 2^63, and a batch with first_shot + B > C(n, w) is refused.
+ *   BPOSD_DEM_SUBSET_RANDOM: Floyd's algorithm on the random stream.  For step i = 0 .. w - 1 with j = n - w + i: counter
+ *     (s lo, s hi, i >> 1, 1), key = seed -- the fourth counter word 1 keeps these draws apart from the Bernoulli stream,
+ *     which uses 0 -- u = o[2 (i & 1)] | o[2 (i & 1) + 1] << 32, t = (u * (j + 1)) >> 64; the step takes j if t is already
+ *     in the set, else t.  Every w-subset is equally likely up to the multiply-shift bias: t takes each of its j + 1 values
+ *     with probability 1 / (j + 1) +- 2^-64, a relative bias below (j + 1) / 2^64 < 2^-49 per step (j < 2^15).  The draw
+ *     does not depend on the batch size or the device.
+ *   BPOSD_DEM_SUBSET_OFF: back to Bernoulli rows (weight, support and incr are ignored); a batch then launches and allocates
+ *     what it did before.
+ *
+ * Items 0-2 of a shot are those of the Bernoulli sampler for that fault row (packed, padding zero; H . f; L . f), and
+ * everything behind the sampler -- decode, scorer, harvest -- runs unchanged.  With incr[N] (may be NULL) item
+ * BPOSD_DEM_LOGW holds the integer sum of incr over the set; the item is valid if and only if incr was given.  For the
+ * probability of a set under the priors, incr[i] = round(log(p_i / (1 - p_i)) * 2^32) and c0 = sum over the support of
+ * log(1 - p_i) give P(set) = exp(c0 + logw / 2^32) (bp_osd_amd.dem.subset_table).
+ *
+ * The arrays are copied (counted in bposd_dem_device_bytes: C(c, j) for j = 1 .. w, c = 0 .. n in enumerate mode, the
+ * increments, the support, and int64[capacity] with the first increment table).  Works on sample-only engines; one in a
+ * subset mode that is handed to bposd_window_run draws that way (that engine's results know nothing of strata).
+ * BPOSD_ERR_INVALID, with a message that names the culprit and the engine left as it was, for: a mode that is none of
+ * the three; a weight outside [0, min(n, 64)]; a support that does not ascend strictly or leaves [0, N); C(n, w) >= 2^63 in
+ * enumerate mode; w * |incr[i]| >= 2^62 for a fault of the support; weighted sampling switched on (and
+ * bposd_dem_set_sampling with a table is refused while a subset mode is on): switch one off first.  BPOSD_ERR_UNSUPPORTED
+ * where four rows of M + k + N bits do not fit the sampler's LDS (64 KB).
+ */
+#define BPOSD_DEM_SUBSET_OFF 0
+#define BPOSD_DEM_SUBSET_ENUMERATE 1
+#define BPOSD_DEM_SUBSET_RANDOM 2
+int bposd_dem_set_subset(bposd_dem *dem, int32_t mode, int32_t weight, const int32_t *support, int32_t n_support,
+                         const int64_t *incr);
+
 /* The sampler alone: shots first_shot .. first_shot + B - 1 (1 <= B <= capacity); waits for the kernel.  Items 0-2 of
- * bposd_dem_fetch hold the batch afterwards (and item 10 while weighted sampling is on). */
+ * bposd_dem_fetch hold the batch afterwards (and item 10 while weighted sampling is on, or a subset mode with increments). */
 int bposd_dem_sample(bposd_dem *dem, uint64_t first_shot, int64_t B);
 
 /*
@@ -550,7 +591,8 @@ int bposd_dem_harvest_info(bposd_dem *dem, int64_t out[3]);
 /* Copy one item (BPOSD_DEM_FAULTS ...) of the last batch to host memory; bytes must be that item's size for the last B
  * (for items 11 .. 14: for the last batch's number of failing shots -- 0 bytes is legal and copies nothing).
  * After bposd_dem_sample only items 0-2 are there.  BPOSD_DEM_OBS_FAIL came down with the counters: no device call.
- * BPOSD_DEM_LOGW needs a batch sampled while weighted sampling is on: BPOSD_ERR_INVALID otherwise. */
+ * BPOSD_DEM_LOGW needs a batch sampled while weighted sampling is on, or a subset mode that was given increments:
+ * BPOSD_ERR_INVALID otherwise. */
 int bposd_dem_fetch(bposd_dem *dem, int32_t what, void *host_dst, size_t bytes);
 
 /* Device memory the engine holds (the sum of its own allocations; the decoder's workspaces are its own). */

@@ -21,7 +21,11 @@ the sampler's HIP-event time, the ``bposd_dem_run`` call, and the batch as ``dem
 ``--harvest K`` measures the harvest of failing shots instead (profiles/dem_harvest_rates.txt): two engines on the model, one
 with ``harvest=K``, alternating over the rounds -- the three harvest kernels' time by HIP events, the ``bposd_dem_run`` call and
 the batch as ``dem_decode_sim`` runs it, off and on -- and the kernels' time on one failure-rich batch (every shot of the
-last batch selected through ``bposd_debug_dem_harvest``, against a correction of zeros)."""
+last batch selected through ``bposd_debug_dem_harvest``, against a correction of zeros).
+
+``--fault-weight W --subset MODE`` measures the fixed-weight sampler instead (profiles/dem_subset_rates.txt): two sample-only
+calls on the model, ``bposd_dem_sample`` with Bernoulli rows and with sets of weight W (``enumerate`` or ``random``),
+alternating over the rounds -- each sampler's HIP-event time -- and one whole ``bposd_dem_run`` batch of the stratum."""
 import argparse
 import os
 import sys
@@ -92,6 +96,46 @@ def weighted_probe(a, say):
         extra = f", weight_mean {sim.weight_mean:.4f}, effective sample fraction {sim.effective_sample_fraction:.3f}" if sim._tilted else ""
         say(f"    after {sim.run_count} shots: osdw logical error rate {sim.osdw_logical_error_rate:.3e} +- {sim.osdw_logical_error_rate_eb:.1e}, "
             f"osdw failures among the shots as sampled {1 - sim.osdw_success_count / sim.run_count:.5f}{extra}")
+
+
+def subset_probe(a, say):
+    """--fault-weight / --subset: dem_subset_kernel against dem_sample_kernel, the samplers alone."""
+    import ctypes as C
+
+    from bp_osd_amd import _lib, dem_decode_sim
+
+    (H, L, priors), kw, what = model(a.model)
+    B, seed = a.batch, 5
+    say(f"# tools/dem_probe.py --fault-weight {a.fault_weight} --subset {a.subset} on one MI355X: {what}; H {H.shape[0]} x {H.shape[1]}, k = {L.shape[0]}, "
+        f"B = {B}; {a.rounds} rounds of {a.steps} bposd_dem_sample calls per engine, alternating")
+    make = lambda **more: dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=B, run_sim=False, **more, **kw)
+    sims = {"Bernoulli rows": make(), f"sets of weight {a.fault_weight}, {a.subset}": make(fault_weight=a.fault_weight, subset=a.subset)}
+    lib = sims["Bernoulli rows"]._lib
+    t = {name: [] for name in sims}
+    for name, sim in sims.items():  # warm-up: the kernels' first launch
+        _lib.check_dem(lib, sim._dem, lib.bposd_dem_sample(sim._dem, 0, B))
+    for r in range(a.rounds):
+        for name, sim in sims.items():
+            for i in range(a.steps):
+                first = (r * a.steps + i) * B
+                if sim._subset == "enumerate":  # stay inside the stratum
+                    first %= sim.stratum_size - B + 1
+                _lib.check_dem(lib, sim._dem, lib.bposd_dem_sample(sim._dem, first, B))
+                sim._last_B = B
+                t[name].append(sim.kernel_ms()[0])
+    base = np.mean(t["Bernoulli rows"])
+    for name, sim in sims.items():
+        v = t[name]
+        kernel = "dem_subset_kernel" if sim._subset else "dem_sample_kernel"
+        say(f"{name}: {kernel}, HIP events: mean {np.mean(v):.3f} ms (min {min(v):.3f}, max {max(v):.3f}, {len(v)} batches) = {np.mean(v) / base:.2f} x Bernoulli; "
+            f"device {sim.device_bytes() / B:.1f} B per shot")
+    sub = sims[f"sets of weight {a.fault_weight}, {a.subset}"]
+    c5 = (C.c_int64 * 5)()
+    t0 = time.perf_counter()
+    _lib.check_dem(lib, sub._dem, lib.bposd_dem_run(sub._dem, 0, B, c5))
+    dt = time.perf_counter() - t0
+    say(f"one bposd_dem_run of {B} such sets (stratum of {sub.stratum_size:.4g}, mass {sub.stratum_mass:.3e}): {dt * 1e3:.1f} ms, "
+        f"osdw failures {B - int(c5[3])}, bp converged {int(c5[0])}")
 
 
 def harvest_probe(a, say):
@@ -174,15 +218,17 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sample-scale", type=float, default=None, help="measure the weighted sampler against the plain one at this sample_scale")
     ap.add_argument("--harvest", type=int, default=None, help="measure the harvest of failing shots (this many rows kept) against a plain engine")
+    ap.add_argument("--fault-weight", type=int, default=None, help="measure the fixed-weight sampler (sets of this weight) against the Bernoulli one")
+    ap.add_argument("--subset", choices=("enumerate", "random"), default="random", help="with --fault-weight: every set in turn, or drawn uniformly")
     a = ap.parse_args()
-    if a.sample_scale is not None or a.harvest is not None:
+    if a.sample_scale is not None or a.harvest is not None or a.fault_weight is not None:
         lines = []
 
         def say(s):
             print(s, flush=True)
             lines.append(s)
 
-        (weighted_probe if a.sample_scale is not None else harvest_probe)(a, say)
+        (weighted_probe if a.sample_scale is not None else harvest_probe if a.harvest is not None else subset_probe)(a, say)
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n\n")
