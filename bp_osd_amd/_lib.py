@@ -96,6 +96,7 @@ DEBUG_SYMBOLS = (
     "bposd_layout_info",
     "bposd_bp_kernel_info",
     "bposd_debug_local_layout",
+    "bposd_debug_host_chunks",
     "bposd_debug_local_keys",
     "bposd_debug_local_waves",
     "bposd_debug_last_pair_key",
@@ -303,6 +304,8 @@ def load():
     lib.bposd_bp_kernel_info.restype = C.c_int
     lib.bposd_debug_local_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
     lib.bposd_debug_local_layout.restype = C.c_int
+    lib.bposd_debug_host_chunks.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    lib.bposd_debug_host_chunks.restype = C.c_int
     lib.bposd_debug_local_keys.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
     lib.bposd_debug_local_keys.restype = C.c_int
     lib.bposd_debug_local_waves.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp]

@@ -1,7 +1,8 @@
 """Build libbposd_mi355x.so in-tree with hipcc for gfx950 (no cmake, no JIT cache).
 
-One translation unit per kernel family (csrc/launch_*.hip) next to the C-ABI with the decode calls (csrc/bposd_capi.hip)
-and table construction with the layout searches (csrc/host_tables.hip): every csrc/*.hip is a unit, the units compile in
+One translation unit per kernel family (csrc/launch_*.hip) next to the C-ABI with the device-pointer decode calls
+(csrc/bposd_capi.hip), the host-pointer decode calls (csrc/decode_host.hip) and table construction with the layout
+searches (csrc/host_tables.hip): every csrc/*.hip is a unit, the units compile in
 parallel and only the stale ones are rebuilt (objects under csrc/_obj/, git-ignored).
 
 Diagnostic / A-B builds (BPOSD_EXTRA_FLAGS="-DBPOSD_OSD_DIAG ...") never touch the product library: their objects go to

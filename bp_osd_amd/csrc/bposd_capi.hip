@@ -1,6 +1,7 @@
 // bposd_capi.hip -- host side of libbposd_mi355x.so: the C-ABI declared in
-// include/bposd_mi355x.h, the decode calls (lanes, streams, events), kernel dispatch, workspace
-// and HIP-event timing; table construction is in host_tables.hip.  gfx950 only; there is no CPU fallback anywhere in this file:
+// include/bposd_mi355x.h -- creation, the one BP + OSD launch pair every decode call ends in (decode_device_impl: lanes,
+// streams, events, kernel dispatch), the device-pointer calls, workspace and HIP-event timing.  The host-pointer calls are in
+// decode_host.hip, table construction in host_tables.hip.  gfx950 only; there is no CPU fallback anywhere in this file:
 // without a HIP device every entry point fails with BPOSD_ERR_NO_DEVICE.
 //
 // Reference interface replaced: the `bposd_decoder` / `BpOsdDecoder` object of the
@@ -22,9 +23,7 @@
 #include <functional>
 #include <map>
 #include <memory>
-#include <chrono>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "internal.h"
@@ -155,10 +154,10 @@ __global__ void unpack_rows_kernel(const unsigned long long* __restrict__ in, lo
     }
 }
 
-namespace {
+namespace bposd_host {
 
 // wg_per_cu caps the grid: 2 inside the decode paths (few, fat workgroups: see launch_unpack), 16 for a stand-alone pack
-int launch_pack(bposd_handle* h, hipStream_t st, const uint8_t* d_bytes, long long B, int n, unsigned long long* d_words, int wg_per_cu = 2) {
+int launch_pack(bposd_handle* h, hipStream_t st, const uint8_t* d_bytes, long long B, int n, unsigned long long* d_words, int wg_per_cu) {
     if (B <= 0) return 0;
     const int wpr = (n + 63) / 64, threads = 256;
     const long long want = ((long long)B * wpr * 64 + threads - 1) / threads;
@@ -180,19 +179,299 @@ int launch_unpack(bposd_handle* h, hipStream_t st, const unsigned long long* d_w
     return 0;
 }
 
-}  // namespace
-
-// [0, count) cut into equal slices for at most min(16, hardware threads) host threads (one below 64 K items); f(lo, hi)
-template <class F>
-static void parallel_slices(size_t count, F f) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t nt = std::max<size_t>(1, std::min<size_t>({(size_t)16, (size_t)(hw ? hw : 1), count / 65536 + 1}));
-    if (nt == 1) { f((size_t)0, count); return; }
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < nt; ++t) pool.emplace_back(f, count * t / nt, count * (t + 1) / nt);
-    f((size_t)0, count / nt);
-    for (auto& th : pool) th.join();
+// ---- what the decode entry points of this file and of decode_host.hip share (declared in internal.h)
+// Does this handle's OSD stage rank candidates by the channel's weights (else per-shot weight rows are never read)?
+bool osd_weighs_candidates(const bposd_handle* h) {
+    return h->cfg.osd_method >= BPOSD_OSD_E && h->cfg.osd_order > 0 && h->cfg.weight_fn == 0;
 }
+
+// What every decode entry point checks before anything is enqueued (B == 0 is a valid call that does nothing).
+int check_batch(bposd_handle* h, int64_t B, const void* synd, const void* osdw) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (B < 0 || B > 0x7fffffffLL) return fail(h, BPOSD_ERR_INVALID, "batch size %lld out of range", (long long)B);
+    if (B > 0 && (!synd || !osdw)) return fail(h, BPOSD_ERR_INVALID, "syndromes and osdw buffers are required");
+    return BPOSD_OK;
+}
+
+// A stand-alone device-pointer call takes the handle's next lane and is record 0 of a new "last call".  The entry point
+// takes the lane once, stages what the call needs on it and hands it to decode_device_impl.
+DecodeCall take_next_lane(bposd_handle* h) {
+    const int lane = h->next_lane;
+    h->next_lane = (lane + 1) % h->nlanes;
+    h->last_lane = lane;
+    h->nrec = 0;
+    h->async_pending = true;
+    Lane& L = h->lanes[lane];
+    return DecodeCall{&L, &h->lane_rec[lane], L.osd_stream};  // stream order on the lane: its previous call has filled the record by now
+}
+
+static int report_osd_debug(bposd_handle* h, const DecodeCall& call);
+
+// One BP launch + one OSD launch on the call's lane, `io` in device memory.
+int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io, int64_t B) {
+    // lean (the small host-pointer call): everything on the lane's own stream in program order -- no events, no second
+    // stream -- so that the call costs a memset, two launches, one 32-byte copy and one synchronisation
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    Lane& L = *call.lane;
+    CallRecord& R = *call.rec;
+    const bool lean = call.lean;
+    const bool osd_on = h->cfg.osd_method != BPOSD_OSD_OFF && !call.bp_only;
+    int rc;
+    if (osd_on) {
+        if ((rc = ensure_lanes(h, &Lane::llr_ws, sizeof(double) * (size_t)B * h->n))) return rc;
+        if ((rc = ensure_lanes(h, &Lane::osd_list, sizeof(int) * (size_t)B))) return rc;
+    }
+    HIP_TRY(h, hipMemsetAsync(L.d_counters, 0, 32, L.stream));
+
+    BpParams P{};
+    P.m = h->m;
+    P.n = h->n;
+    P.B = B;
+    P.max_iter = h->max_iter;
+    P.ms_scaling = h->cfg.ms_scaling_factor;
+    P.ps_clip = h->cfg.ps_clip;
+    P.osd_enabled = osd_on ? 1 : 0;
+    P.synd = io.synd;
+    P.llr0 = h->d_llr0;
+    P.sel = io.sel;
+    P.llr0_alt = call.lane_alt ? L.d_alt : h->d_llr0_alt;
+    P.llr0_rows = io.llr0_rows;
+    P.chk_deg = h->d_chk_deg;
+    P.var_deg = h->d_var_deg;
+    P.var_pos = h->d_var_pos;
+    P.pos_bit = h->d_pos_bit;
+    P.out_bp = io.bp;
+    P.out_osd0 = io.osd0;
+    P.out_osdw = io.osdw;
+    P.out_conv = io.conv;
+    P.out_iters = io.iters;
+    P.out_llr = io.llr;
+    P.llr_ws = (double*)L.llr_ws.p;
+    P.osd_list = (int*)L.osd_list.p;
+    P.counters = L.d_counters;
+    P.iter_total = (unsigned long long*)(L.d_counters + 4);
+    P.tail_flag = call.tail_gate ? L.h_tail.as<int>() : nullptr;
+    P.packed_io = call.packed ? 1 : 0;
+
+    // At most TWO calls have kernels on the device: this call's BP kernel waits for the END of the call two back (its OSD
+    // kernel included).  (i) A third BP kernel that became ready meanwhile would share the slots the first one frees with the
+    // second from the first workgroup on -- both then take twice as long and finish together.  (ii) The OSD kernel needs a
+    // whole CU (131 KB of LDS for H1922); while ANY persistent BP grid is waiting, every slot a draining CU frees goes to a BP
+    // workgroup, which fits, and the eliminations of call k starve until the pipeline runs dry (traced with three and four
+    // asynchronous host calls in flight: completions came in bursts of three).  With this rule OSD(k) gets its CUs at the
+    // start of BP(k + 1)'s tail and BP(k + 2) follows ~1 ms later, whatever the number of calls queued.
+    // (Not where BP is HBM-resident: there both kernels need a whole CU, the OSD stream has the higher priority, and three calls in
+    // flight are what fills the CUs -- see the lane count in bposd_create.  BPOSD_TWO_BACK=0/1 overrides, for probes.)
+    static const char* two_back_env = getenv("BPOSD_TWO_BACK");
+    const bool two_back_rule = two_back_env ? two_back_env[0] == '1' : !h->bp_hbm;
+    if (!lean && !call.tail_gate && h->nlanes >= 3 && two_back_rule) {  // (the chunks of a synchronous host call are released one by one by the host: tail_gate)
+        Lane& two_back = h->lanes[((int)(call.lane - h->lanes) + h->nlanes - 2) % h->nlanes];
+        if (two_back.done_recorded) HIP_TRY(h, hipStreamWaitEvent(L.stream, two_back.ev_done, 0));
+    }
+    if (!lean) HIP_TRY(h, hipEventRecord(R.ev[0], L.stream));
+    if (h->cfg.schedule == 1) {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_SERIAL;
+        if ((rc = launch_bp_serial(h, call, P))) return rc;
+    } else if (h->bp_any || h->bp_variant == 64) {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_ANYDEG;
+        if ((rc = launch_bp_any(h, call, P))) return rc;
+    } else if (h->bp_hbm) {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_LARGE;
+        if ((rc = launch_bp_large(h, call, P))) return rc;
+    } else if (h->local_ok && h->cfg.bp_method == BPOSD_BP_MIN_SUM && (h->bp_variant == 0 || (h->bp_variant >= 16 && h->bp_variant <= 26))) {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_LOCAL;
+        if ((rc = launch_bp_local(h, call, P))) return rc;
+    } else if (h->class_ok && (h->bp_variant == 32 || (h->bp_variant == 0 && class_preferred(h)))) {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_CLASS;
+        if ((rc = launch_bp_class(h, call, P))) return rc;
+    } else {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_LDS;
+        if ((rc = launch_bp(h, call, P))) return rc;
+    }
+    if (!lean) HIP_TRY(h, hipEventRecord(R.ev[1], L.stream));
+    R.ran_osd = false;
+    R.ran_obs = false;
+    if (!lean && (osd_on || call.tail_gate)) HIP_TRY(h, hipEventRecord(L.ev_bp, L.stream));  // the BP kernel has ended
+    if (osd_on) {
+        if (!lean) HIP_TRY(h, hipStreamWaitEvent(L.osd_stream, L.ev_bp, 0));
+        OsdParams Q{};
+        Q.m = h->m;
+        Q.n = h->n;
+        Q.rank = h->rank;
+        Q.osd_method = h->cfg.osd_order == 0 ? BPOSD_OSD_0 : h->cfg.osd_method;
+        Q.osd_order = h->cfg.osd_order;
+        Q.tie_policy = h->cfg.sort_tie_policy;
+        Q.e_msb_first = h->cfg.osd_e_bit_order;
+        Q.synd = io.synd;
+        Q.rp = h->d_rp;
+        Q.ci = h->d_ci;
+        Q.llr_ws = (const double*)L.llr_ws.p;
+        Q.osd_list = (const int*)L.osd_list.p;
+        Q.counters = L.d_counters;
+        Q.out_osd0 = io.osd0;
+        Q.out_osdw = io.osdw;
+        Q.cmp_osd0 = io.osd0 ? call.cmp_osd0 : nullptr;
+        Q.cmp_osdw = call.cmp_osdw;
+        Q.dbg = nullptr;
+        Q.packed_io = call.packed ? 1 : 0;
+        Q.cost = (h->fp_weights || ((io.sel || io.cost_rows) && h->cfg.weight_fn == 0)) ? h->d_cost : nullptr;  // (non-null = the fp64 weight path)
+        Q.cost_rows = h->cfg.weight_fn == 0 ? io.cost_rows : nullptr;
+        Q.sel = io.sel;
+        Q.cost_alt = call.lane_alt ? L.d_alt + h->n : h->d_cost_alt;
+        const char* dbg_env = getenv("BPOSD_OSD_DEBUG");
+        if (dbg_env && dbg_env[0] == '1') {
+            if (!L.d_osd_dbg) HIP_TRY(h, L.d_osd_dbg.alloc(8192 * sizeof(long long)));
+            HIP_TRY(h, hipMemsetAsync(L.d_osd_dbg, 0, 8192 * sizeof(long long), call.osd_stream));
+            Q.dbg = L.d_osd_dbg;
+        }
+        if (h->large) {
+            h->last_osd_kernel = 3;
+            if ((rc = launch_osd_large(h, call, Q, B, nullptr))) return rc;
+        } else if ((rc = launch_osd(h, call, Q, B))) return rc;
+        R.ran_osd = true;
+        if (Q.dbg && (rc = report_osd_debug(h, call))) return rc;
+    }
+    if (osd_on && !lean) {  // whatever follows on the lane's stream comes after the OSD kernel
+        HIP_TRY(h, hipEventRecord(L.ev_osd, L.osd_stream));
+        HIP_TRY(h, hipStreamWaitEvent(L.stream, L.ev_osd, 0));
+    }
+    if (!lean) {
+        HIP_TRY(h, hipEventRecord(R.ev[2], L.stream));
+        HIP_TRY(h, hipEventRecord(L.ev_done, L.stream));  // both kernels of this call have ended
+        L.done_recorded = true;
+    }
+    HIP_TRY(h, hipMemcpyAsync(R.counters(), L.d_counters, 32, hipMemcpyDeviceToHost, L.stream));
+    R.recorded = true;
+    R.timed = !lean;
+    h->have_timing = true;
+    return BPOSD_OK;
+}
+
+// BPOSD_OSD_DEBUG=1: waits for the call's OSD kernel and prints the phase timestamps it left in the lane's d_osd_dbg
+static int report_osd_debug(bposd_handle* h, const DecodeCall& call) {
+    std::vector<long long> all(h->large ? 8192 : 2048);
+    const long long* st = all.data();
+    HIP_TRY(h, hipStreamSynchronize(call.osd_stream));
+    HIP_TRY(h, hipMemcpy(all.data(), call.lane->d_osd_dbg, sizeof(long long) * all.size(), hipMemcpyDeviceToHost));
+    if (!h->large) {
+        if (const char* dump = getenv("BPOSD_OSD_DUMP")) {
+            if (FILE* f = fopen(dump, "wb")) { fwrite(st, sizeof(long long), 2048, f); fclose(f); }
+        }
+        fprintf(stderr, "[bposd osd phases, s_memtime ticks] sort %lld  rowbuild %lld  eliminate %lld  osd0 %lld  sweep %lld  write %lld\n",
+                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5]);
+        fprintf(stderr, "[bposd osd elimination] panel phase %lld (claims + barrier %lld, solve + tables %lld of which the six steps %lld, absorb %lld)  trailing phase %lld (publish %lld, tables %lld)  pivots %lld\n", st[1190], st[1195], st[1196], st[1189], st[1197], st[1191], st[1193], st[1194], st[1192]);
+        return 0;
+    }
+    fprintf(stderr, "[bposd large osd, sparse apply passes %lld: %lld ticks, %lld listed rows, %lld mask bits; word of the last search column %lld]\n", st[12], st[24], st[25], st[26], st[27]);
+    fprintf(stderr, "[bposd large osd, s_memtime ticks, list slot 0] sort %lld  build %lld  E1 %lld  E2 %lld  E3 %lld  apply %lld  "
+            "sweep %lld (back-substitution %lld, column vectors %lld, candidates %lld, write-out %lld) | words %lld groups %lld applies %lld | apply look-ups/thread %lld row-words/thread %lld | apply pass: row walks %lld, wait for the slowest walker %lld, own table build %lld, wait for the builders %lld, list builds %lld\n", st[0], st[1], st[2], st[3], st[4], st[5] + st[17] + st[18] + st[19] + st[20], st[6], st[13], st[14], st[15], st[16], st[7], st[8], st[9], st[10], st[11], st[5], st[19], st[17], st[18], st[20]);
+    // every elimination of the launch (osd_large_kernel writes 16 numbers per list slot behind the first 32)
+    std::vector<std::array<long long, 16>> v;
+    for (int i = 0; i < 500; ++i)
+        if (all[32 + i * 16] > 0) {
+            std::array<long long, 16> a;
+            for (int k = 0; k < 16; ++k) a[k] = all[32 + i * 16 + k];
+            v.push_back(a);
+        }
+    if (v.size() <= 1) return 0;
+    std::sort(v.begin(), v.end());
+    fprintf(stderr, "[bposd large osd, all %zu eliminations of the launch, sorted by ticks] M ticks: total | sort build E2 E3 row-walks sweep | words groups applies | own-table-build E1c E2c-one-wave sparse-apply-passes | wave 0's pivot search alone (E2 column = the rest of the panel phase; E2c-one-wave = the wait for the other waves' share of E3 after it)\n", v.size());
+    for (size_t i = 0; i < v.size(); i += (i + 8 < v.size() ? v.size() / 8 : 1)) {
+        const auto& a = v[i];
+        fprintf(stderr, "  [%3zu] %.0f | %.1f %.1f %.1f %.1f %.1f %.1f | %lld %lld %lld | %.1f %.1f %.1f %.1f | %.1f\n", i, a[0] * 1e-6, a[1] * 1e-6, a[2] * 1e-6, a[4] * 1e-6, a[5] * 1e-6,
+                a[6] * 1e-6, a[7] * 1e-6, a[8], a[9], a[10], a[12] * 1e-6, a[13] * 1e-6, a[14] * 1e-6, a[15] * 1e-6, a[3] * 1e-6);
+    }
+    return 0;
+}
+
+// the alternative channel of the two-valued per-shot form: validated first, then its prior LLRs and OSD-W weights
+int check_alt_channel(bposd_handle* h, const double* alt) {
+    if (!alt) return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt is required");
+    if (const int64_t bad = first_bad_prob(alt, h->n))
+        return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt[%d] = %g is not a probability", (int)(bad - 1), alt[bad - 1]);
+    return 0;
+}
+
+static void alt_channel_tables(int n, const double* alt, double* l0, double* cost) { (void)channel_tables(alt, n, l0, cost); }
+
+int upload_alt_channel(bposd_handle* h, const double* alt) {
+    { int rca = check_alt_channel(h, alt); if (rca) return rca; }
+    std::vector<double> l0(h->n), cost(h->n);
+    alt_channel_tables(h->n, alt, l0.data(), cost.data());
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls may still read the old tables
+    HIP_TRY(h, hipMemcpy(h->d_llr0_alt, l0.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_cost_alt, cost.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int check_observables(bposd_handle* h) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (h->obs_k <= 0) return fail(h, BPOSD_ERR_INVALID, "no observables are set on this handle (bposd_set_observables)");
+    return BPOSD_OK;
+}
+
+// Lane buffers of an observables decode of up to `cap` syndromes: the rows the kernels write (packed where the kernels are,
+// bytes otherwise), the syndromes in the kernels' form where the caller's are in the other one, and for a host-pointer
+// call the syndromes as uploaded and the outputs to download.
+int obs_reserve(bposd_handle* h, size_t cap, const ObsOut& out, bool host, bool synd_packed) {
+    const bool native = native_packed(h);
+    const size_t rs = row_bytes(h->n, native), ob = sizeof(uint64_t) * (size_t)((h->obs_k + 63) / 64);
+    bool drained = false;
+    int rc;
+    if ((rc = grow_lanes(h, native ? &Lane::io_posdw : &Lane::io_osdw, cap * rs, &drained))) return rc;
+    if (out.osd0 && (rc = grow_lanes(h, native ? &Lane::io_posd0 : &Lane::io_osd0, cap * rs, &drained))) return rc;
+    if (out.bp && (rc = grow_lanes(h, native ? &Lane::io_pbp : &Lane::io_bp, cap * rs, &drained))) return rc;
+    if ((host || native != synd_packed) && (rc = grow_lanes(h, native ? &Lane::io_psynd : &Lane::io_synd, cap * row_bytes(h->m, native), &drained))) return rc;
+    if (!host) return 0;
+    if (native != synd_packed && (rc = grow_lanes(h, synd_packed ? &Lane::io_psynd : &Lane::io_synd, cap * row_bytes(h->m, synd_packed), &drained))) return rc;
+    if ((rc = grow_lanes(h, &Lane::io_obsw, cap * ob, &drained))) return rc;
+    if (out.osd0 && (rc = grow_lanes(h, &Lane::io_obs0, cap * ob, &drained))) return rc;
+    if (out.bp && (rc = grow_lanes(h, &Lane::io_obsbp, cap * ob, &drained))) return rc;
+    if ((rc = grow_lanes(h, &Lane::io_conv, cap, &drained))) return rc;
+    return grow_lanes(h, &Lane::io_iters, sizeof(int) * cap, &drained);
+}
+
+// One decode into the lane's own row buffers with obs_kernel behind it, everything on the call's lane: `d_synd` (bytes or
+// packed words) is brought into the kernels' form first where it is in the other one; `out` is device memory.
+int decode_obs_impl(bposd_handle* h, DecodeCall call, const void* d_synd, bool synd_packed, int64_t B, const ObsOut& out) {
+    Lane& L = *call.lane;
+    // the lane's io buffers are also read by its copy stream in the host-pointer decode path
+    if (L.copy_pending) { HIP_TRY(h, hipStreamSynchronize(L.copy_stream)); L.copy_pending = false; }
+    const bool native = native_packed(h);
+    int rc;
+    if (native && !synd_packed) {
+        if ((rc = launch_pack(h, L.stream, (const uint8_t*)d_synd, B, h->m, (unsigned long long*)L.io_psynd.p))) return rc;
+        d_synd = L.io_psynd.p;
+    } else if (!native && synd_packed) {
+        if ((rc = launch_unpack(h, L.stream, (const unsigned long long*)d_synd, B, h->m, (uint8_t*)L.io_synd.p))) return rc;
+        d_synd = L.io_synd.p;
+    }
+    call.packed = native;
+    IoPtrs want;  // (which of the lane's row buffers the call writes: the ones whose observables are asked for)
+    want.osd0 = (uint8_t*)out.osd0;
+    want.bp = (uint8_t*)out.bp;
+    IoPtrs dev = lane_ptrs(L, native, want);
+    dev.synd = (const uint8_t*)d_synd;
+    dev.conv = out.conv;
+    dev.iters = out.iters;
+    if ((rc = decode_device_impl(h, call, dev, B))) return rc;
+    // (decode_device_impl has made the lane's stream wait for the OSD kernel: the rows are final)
+    const void* const rows[3] = {dev.osdw, dev.osd0, dev.bp};
+    uint64_t* const outs[3] = {out.osdw, out.osd0, out.bp};
+    CallRecord& R = *call.rec;  // (bposd_last_timing's events end in front of obs_kernel: it has a pair of its own)
+    for (auto& e : R.ev_obs)
+        if (!e) HIP_TRY(h, hipEventCreate(&e.raw));
+    HIP_TRY(h, hipEventRecord(R.ev_obs[0], L.stream));
+    if ((rc = launch_obs(h, L.stream, rows, native, B, outs))) return rc;
+    HIP_TRY(h, hipEventRecord(R.ev_obs[1], L.stream));
+    R.ran_obs = true;
+    return 0;
+}
+
+}  // namespace bposd_host
 
 // ================================================================================ C-ABI
 extern "C" {
@@ -500,225 +779,6 @@ int bposd_synchronize(bposd_handle* h) {
     return sync_all_lanes(h);
 }
 
-// Device-side I/O of one kernel pair: rows of bytes, or of little-endian 64-bit words where the call is packed.  The same
-// struct names the caller's arrays of a host-pointer call (null: that output is not wanted).
-struct IoPtrs {
-    const uint8_t* synd = nullptr;
-    const uint8_t* sel = nullptr;
-    uint8_t *osdw = nullptr, *osd0 = nullptr, *bp = nullptr, *conv = nullptr;
-    int32_t* iters = nullptr;
-    double* llr = nullptr;
-    // a channel of its own for every syndrome (bposd_decode_batch_rows*): rows [B, n] of prior LLRs and of OSD-W weights
-    // as bposd_channel_tables makes them; cost_rows is null where OSD does not weigh candidates
-    const double* llr0_rows = nullptr;
-    const double* cost_rows = nullptr;
-};
-
-// Does this handle's OSD stage rank candidates by the channel's weights (else per-shot weight rows are never read)?
-static bool osd_weighs_candidates(const bposd_handle* h) {
-    return h->cfg.osd_method >= BPOSD_OSD_E && h->cfg.osd_order > 0 && h->cfg.weight_fn == 0;
-}
-
-// What every decode entry point checks before anything is enqueued (B == 0 is a valid call that does nothing).
-static int check_batch(bposd_handle* h, int64_t B, const void* synd, const void* osdw) {
-    if (!h) return BPOSD_ERR_INVALID;
-    if (B < 0 || B > 0x7fffffffLL) return fail(h, BPOSD_ERR_INVALID, "batch size %lld out of range", (long long)B);
-    if (B > 0 && (!synd || !osdw)) return fail(h, BPOSD_ERR_INVALID, "syndromes and osdw buffers are required");
-    return BPOSD_OK;
-}
-
-// A stand-alone device-pointer call takes the handle's next lane and is record 0 of a new "last call".  The entry point
-// takes the lane once, stages what the call needs on it and hands it to decode_device_impl.
-static DecodeCall take_next_lane(bposd_handle* h) {
-    const int lane = h->next_lane;
-    h->next_lane = (lane + 1) % h->nlanes;
-    h->last_lane = lane;
-    h->nrec = 0;
-    h->async_pending = true;
-    Lane& L = h->lanes[lane];
-    return DecodeCall{&L, &h->lane_rec[lane], L.osd_stream};  // stream order on the lane: its previous call has filled the record by now
-}
-
-static int report_osd_debug(bposd_handle* h, const DecodeCall& call);
-
-// One BP launch + one OSD launch on the call's lane, `io` in device memory.
-static int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io, int64_t B) {
-    // lean (the small host-pointer call): everything on the lane's own stream in program order -- no events, no second
-    // stream -- so that the call costs a memset, two launches, one 32-byte copy and one synchronisation
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dev_guard.err);
-    Lane& L = *call.lane;
-    CallRecord& R = *call.rec;
-    const bool lean = call.lean;
-    const bool osd_on = h->cfg.osd_method != BPOSD_OSD_OFF && !call.bp_only;
-    int rc;
-    if (osd_on) {
-        if ((rc = ensure_lanes(h, &Lane::llr_ws, sizeof(double) * (size_t)B * h->n))) return rc;
-        if ((rc = ensure_lanes(h, &Lane::osd_list, sizeof(int) * (size_t)B))) return rc;
-    }
-    HIP_TRY(h, hipMemsetAsync(L.d_counters, 0, 32, L.stream));
-
-    BpParams P{};
-    P.m = h->m;
-    P.n = h->n;
-    P.B = B;
-    P.max_iter = h->max_iter;
-    P.ms_scaling = h->cfg.ms_scaling_factor;
-    P.ps_clip = h->cfg.ps_clip;
-    P.osd_enabled = osd_on ? 1 : 0;
-    P.synd = io.synd;
-    P.llr0 = h->d_llr0;
-    P.sel = io.sel;
-    P.llr0_alt = call.lane_alt ? L.d_alt : h->d_llr0_alt;
-    P.llr0_rows = io.llr0_rows;
-    P.chk_deg = h->d_chk_deg;
-    P.var_deg = h->d_var_deg;
-    P.var_pos = h->d_var_pos;
-    P.pos_bit = h->d_pos_bit;
-    P.out_bp = io.bp;
-    P.out_osd0 = io.osd0;
-    P.out_osdw = io.osdw;
-    P.out_conv = io.conv;
-    P.out_iters = io.iters;
-    P.out_llr = io.llr;
-    P.llr_ws = (double*)L.llr_ws.p;
-    P.osd_list = (int*)L.osd_list.p;
-    P.counters = L.d_counters;
-    P.iter_total = (unsigned long long*)(L.d_counters + 4);
-    P.tail_flag = call.tail_gate ? L.h_tail.as<int>() : nullptr;
-    P.packed_io = call.packed ? 1 : 0;
-
-    // At most TWO calls have kernels on the device: this call's BP kernel waits for the END of the call two back (its OSD
-    // kernel included).  (i) A third BP kernel that became ready meanwhile would share the slots the first one frees with the
-    // second from the first workgroup on -- both then take twice as long and finish together.  (ii) The OSD kernel needs a
-    // whole CU (131 KB of LDS for H1922); while ANY persistent BP grid is waiting, every slot a draining CU frees goes to a BP
-    // workgroup, which fits, and the eliminations of call k starve until the pipeline runs dry (traced with three and four
-    // asynchronous host calls in flight: completions came in bursts of three).  With this rule OSD(k) gets its CUs at the
-    // start of BP(k + 1)'s tail and BP(k + 2) follows ~1 ms later, whatever the number of calls queued.
-    // (Not where BP is HBM-resident: there both kernels need a whole CU, the OSD stream has the higher priority, and three calls in
-    // flight are what fills the CUs -- see the lane count in bposd_create.  BPOSD_TWO_BACK=0/1 overrides, for probes.)
-    static const char* two_back_env = getenv("BPOSD_TWO_BACK");
-    const bool two_back_rule = two_back_env ? two_back_env[0] == '1' : !h->bp_hbm;
-    if (!lean && !call.tail_gate && h->nlanes >= 3 && two_back_rule) {  // (the chunks of a synchronous host call are released one by one by the host: tail_gate)
-        Lane& two_back = h->lanes[((int)(call.lane - h->lanes) + h->nlanes - 2) % h->nlanes];
-        if (two_back.done_recorded) HIP_TRY(h, hipStreamWaitEvent(L.stream, two_back.ev_done, 0));
-    }
-    if (!lean) HIP_TRY(h, hipEventRecord(R.ev[0], L.stream));
-    if (h->cfg.schedule == 1) {
-        h->last_bp_kernel = BPOSD_BP_KERNEL_SERIAL;
-        if ((rc = launch_bp_serial(h, call, P))) return rc;
-    } else if (h->bp_any || h->bp_variant == 64) {
-        h->last_bp_kernel = BPOSD_BP_KERNEL_ANYDEG;
-        if ((rc = launch_bp_any(h, call, P))) return rc;
-    } else if (h->bp_hbm) {
-        h->last_bp_kernel = BPOSD_BP_KERNEL_LARGE;
-        if ((rc = launch_bp_large(h, call, P))) return rc;
-    } else if (h->local_ok && h->cfg.bp_method == BPOSD_BP_MIN_SUM && (h->bp_variant == 0 || (h->bp_variant >= 16 && h->bp_variant <= 26))) {
-        h->last_bp_kernel = BPOSD_BP_KERNEL_LOCAL;
-        if ((rc = launch_bp_local(h, call, P))) return rc;
-    } else if (h->class_ok && (h->bp_variant == 32 || (h->bp_variant == 0 && class_preferred(h)))) {
-        h->last_bp_kernel = BPOSD_BP_KERNEL_CLASS;
-        if ((rc = launch_bp_class(h, call, P))) return rc;
-    } else {
-        h->last_bp_kernel = BPOSD_BP_KERNEL_LDS;
-        if ((rc = launch_bp(h, call, P))) return rc;
-    }
-    if (!lean) HIP_TRY(h, hipEventRecord(R.ev[1], L.stream));
-    R.ran_osd = false;
-    R.ran_obs = false;
-    if (!lean && (osd_on || call.tail_gate)) HIP_TRY(h, hipEventRecord(L.ev_bp, L.stream));  // the BP kernel has ended
-    if (osd_on) {
-        if (!lean) HIP_TRY(h, hipStreamWaitEvent(L.osd_stream, L.ev_bp, 0));
-        OsdParams Q{};
-        Q.m = h->m;
-        Q.n = h->n;
-        Q.rank = h->rank;
-        Q.osd_method = h->cfg.osd_order == 0 ? BPOSD_OSD_0 : h->cfg.osd_method;
-        Q.osd_order = h->cfg.osd_order;
-        Q.tie_policy = h->cfg.sort_tie_policy;
-        Q.e_msb_first = h->cfg.osd_e_bit_order;
-        Q.synd = io.synd;
-        Q.rp = h->d_rp;
-        Q.ci = h->d_ci;
-        Q.llr_ws = (const double*)L.llr_ws.p;
-        Q.osd_list = (const int*)L.osd_list.p;
-        Q.counters = L.d_counters;
-        Q.out_osd0 = io.osd0;
-        Q.out_osdw = io.osdw;
-        Q.cmp_osd0 = io.osd0 ? call.cmp_osd0 : nullptr;
-        Q.cmp_osdw = call.cmp_osdw;
-        Q.dbg = nullptr;
-        Q.packed_io = call.packed ? 1 : 0;
-        Q.cost = (h->fp_weights || ((io.sel || io.cost_rows) && h->cfg.weight_fn == 0)) ? h->d_cost : nullptr;  // (non-null = the fp64 weight path)
-        Q.cost_rows = h->cfg.weight_fn == 0 ? io.cost_rows : nullptr;
-        Q.sel = io.sel;
-        Q.cost_alt = call.lane_alt ? L.d_alt + h->n : h->d_cost_alt;
-        const char* dbg_env = getenv("BPOSD_OSD_DEBUG");
-        if (dbg_env && dbg_env[0] == '1') {
-            if (!L.d_osd_dbg) HIP_TRY(h, L.d_osd_dbg.alloc(8192 * sizeof(long long)));
-            HIP_TRY(h, hipMemsetAsync(L.d_osd_dbg, 0, 8192 * sizeof(long long), call.osd_stream));
-            Q.dbg = L.d_osd_dbg;
-        }
-        if (h->large) {
-            h->last_osd_kernel = 3;
-            if ((rc = launch_osd_large(h, call, Q, B, nullptr))) return rc;
-        } else if ((rc = launch_osd(h, call, Q, B))) return rc;
-        R.ran_osd = true;
-        if (Q.dbg && (rc = report_osd_debug(h, call))) return rc;
-    }
-    if (osd_on && !lean) {  // whatever follows on the lane's stream comes after the OSD kernel
-        HIP_TRY(h, hipEventRecord(L.ev_osd, L.osd_stream));
-        HIP_TRY(h, hipStreamWaitEvent(L.stream, L.ev_osd, 0));
-    }
-    if (!lean) {
-        HIP_TRY(h, hipEventRecord(R.ev[2], L.stream));
-        HIP_TRY(h, hipEventRecord(L.ev_done, L.stream));  // both kernels of this call have ended
-        L.done_recorded = true;
-    }
-    HIP_TRY(h, hipMemcpyAsync(R.counters(), L.d_counters, 32, hipMemcpyDeviceToHost, L.stream));
-    R.recorded = true;
-    R.timed = !lean;
-    h->have_timing = true;
-    return BPOSD_OK;
-}
-
-// BPOSD_OSD_DEBUG=1: waits for the call's OSD kernel and prints the phase timestamps it left in the lane's d_osd_dbg
-static int report_osd_debug(bposd_handle* h, const DecodeCall& call) {
-    std::vector<long long> all(h->large ? 8192 : 2048);
-    const long long* st = all.data();
-    HIP_TRY(h, hipStreamSynchronize(call.osd_stream));
-    HIP_TRY(h, hipMemcpy(all.data(), call.lane->d_osd_dbg, sizeof(long long) * all.size(), hipMemcpyDeviceToHost));
-    if (!h->large) {
-        if (const char* dump = getenv("BPOSD_OSD_DUMP")) {
-            if (FILE* f = fopen(dump, "wb")) { fwrite(st, sizeof(long long), 2048, f); fclose(f); }
-        }
-        fprintf(stderr, "[bposd osd phases, s_memtime ticks] sort %lld  rowbuild %lld  eliminate %lld  osd0 %lld  sweep %lld  write %lld\n",
-                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5]);
-        fprintf(stderr, "[bposd osd elimination] panel phase %lld (claims + barrier %lld, solve + tables %lld of which the six steps %lld, absorb %lld)  trailing phase %lld (publish %lld, tables %lld)  pivots %lld\n", st[1190], st[1195], st[1196], st[1189], st[1197], st[1191], st[1193], st[1194], st[1192]);
-        return 0;
-    }
-    fprintf(stderr, "[bposd large osd, sparse apply passes %lld: %lld ticks, %lld listed rows, %lld mask bits; word of the last search column %lld]\n", st[12], st[24], st[25], st[26], st[27]);
-    fprintf(stderr, "[bposd large osd, s_memtime ticks, list slot 0] sort %lld  build %lld  E1 %lld  E2 %lld  E3 %lld  apply %lld  "
-            "sweep %lld (back-substitution %lld, column vectors %lld, candidates %lld, write-out %lld) | words %lld groups %lld applies %lld | apply look-ups/thread %lld row-words/thread %lld | apply pass: row walks %lld, wait for the slowest walker %lld, own table build %lld, wait for the builders %lld, list builds %lld\n", st[0], st[1], st[2], st[3], st[4], st[5] + st[17] + st[18] + st[19] + st[20], st[6], st[13], st[14], st[15], st[16], st[7], st[8], st[9], st[10], st[11], st[5], st[19], st[17], st[18], st[20]);
-    // every elimination of the launch (osd_large_kernel writes 16 numbers per list slot behind the first 32)
-    std::vector<std::array<long long, 16>> v;
-    for (int i = 0; i < 500; ++i)
-        if (all[32 + i * 16] > 0) {
-            std::array<long long, 16> a;
-            for (int k = 0; k < 16; ++k) a[k] = all[32 + i * 16 + k];
-            v.push_back(a);
-        }
-    if (v.size() <= 1) return 0;
-    std::sort(v.begin(), v.end());
-    fprintf(stderr, "[bposd large osd, all %zu eliminations of the launch, sorted by ticks] M ticks: total | sort build E2 E3 row-walks sweep | words groups applies | own-table-build E1c E2c-one-wave sparse-apply-passes | wave 0's pivot search alone (E2 column = the rest of the panel phase; E2c-one-wave = the wait for the other waves' share of E3 after it)\n", v.size());
-    for (size_t i = 0; i < v.size(); i += (i + 8 < v.size() ? v.size() / 8 : 1)) {
-        const auto& a = v[i];
-        fprintf(stderr, "  [%3zu] %.0f | %.1f %.1f %.1f %.1f %.1f %.1f | %lld %lld %lld | %.1f %.1f %.1f %.1f | %.1f\n", i, a[0] * 1e-6, a[1] * 1e-6, a[2] * 1e-6, a[4] * 1e-6, a[5] * 1e-6,
-                a[6] * 1e-6, a[7] * 1e-6, a[8], a[9], a[10], a[12] * 1e-6, a[13] * 1e-6, a[14] * 1e-6, a[15] * 1e-6, a[3] * 1e-6);
-    }
-    return 0;
-}
-
 int bposd_decode_batch_device(bposd_handle* h, const uint8_t* d_synd, int64_t B, uint8_t* d_osdw,
                               uint8_t* d_osd0, uint8_t* d_bp, uint8_t* d_conv, int32_t* d_iters,
                               double* d_llr) {
@@ -737,28 +797,6 @@ int bposd_decode_batch_device_packed(bposd_handle* h, const uint64_t* d_synd_wor
     call.packed = true;
     return decode_device_impl(h, call, IoPtrs{(const uint8_t*)d_synd_words, nullptr, (uint8_t*)d_osdw_words, (uint8_t*)d_osd0_words,
                                               (uint8_t*)d_bp_words, d_conv, d_iters, nullptr}, B);
-}
-
-// the alternative channel of the two-valued per-shot form: validated first, then its prior LLRs and OSD-W weights
-static int check_alt_channel(bposd_handle* h, const double* alt) {
-    if (!alt) return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt is required");
-    if (const int64_t bad = first_bad_prob(alt, h->n))
-        return fail(h, BPOSD_ERR_INVALID, "channel_probs_alt[%d] = %g is not a probability", (int)(bad - 1), alt[bad - 1]);
-    return 0;
-}
-
-static void alt_channel_tables(int n, const double* alt, double* l0, double* cost) { (void)channel_tables(alt, n, l0, cost); }
-
-static int upload_alt_channel(bposd_handle* h, const double* alt) {
-    { int rca = check_alt_channel(h, alt); if (rca) return rca; }
-    std::vector<double> l0(h->n), cost(h->n);
-    alt_channel_tables(h->n, alt, l0.data(), cost.data());
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dev_guard.err);
-    { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls may still read the old tables
-    HIP_TRY(h, hipMemcpy(h->d_llr0_alt, l0.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_cost_alt, cost.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
-    return 0;
 }
 
 int bposd_decode_batch_select_device(bposd_handle* h, const uint8_t* d_synd, int64_t B, const uint8_t* d_sel,
@@ -787,9 +825,6 @@ int bposd_decode_batch_select_device(bposd_handle* h, const uint8_t* d_synd, int
     return decode_device_impl(h, call, IoPtrs{d_synd, d_sel, d_osdw, d_osd0, d_bp, d_conv, d_iters, d_llr}, B);
 }
 
-static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed = false, bool bp_only = false,
-                            const double* prob_rows = nullptr);
-
 int bposd_channel_tables(const double* probs, int64_t count, double* prior_llr, double* cost) {
     if (count < 0 || (count > 0 && !probs)) return fail(nullptr, BPOSD_ERR_INVALID, "bposd_channel_tables: probs and a count >= 0 are required");
     if (const int64_t bad = channel_tables(probs, count, prior_llr, cost))
@@ -810,406 +845,6 @@ int bposd_decode_batch_rows_device(bposd_handle* h, const uint8_t* d_synd, int64
     io.llr0_rows = d_prior_llr_rows;
     io.cost_rows = weighs ? d_cost_rows : nullptr;
     return decode_device_impl(h, take_next_lane(h), io, B);
-}
-
-/* The same with host pointers: channel_probs_rows [B, n] are error probabilities, validated before anything is enqueued. */
-int bposd_decode_batch_rows(bposd_handle* h, const uint8_t* synd, int64_t B, const double* channel_probs_rows, uint8_t* osdw,
-                            uint8_t* osd0, uint8_t* bp, uint8_t* conv, int32_t* iters, double* llr) {
-    if (!h) return BPOSD_ERR_INVALID;
-    if (!channel_probs_rows) return fail(h, BPOSD_ERR_INVALID, "channel_probs_rows is required");
-    if (const int rc = check_batch(h, B, synd, osdw); rc || B == 0) return rc;
-    const size_t total = (size_t)B * (size_t)h->n;
-    std::mutex mu;
-    size_t first_bad = total;
-    parallel_slices(total, [&](size_t lo, size_t hi) {
-        if (const int64_t bad = first_bad_prob(channel_probs_rows + lo, (int64_t)(hi - lo))) {
-            std::lock_guard<std::mutex> g(mu);
-            first_bad = std::min(first_bad, lo + (size_t)bad - 1);
-        }
-    });
-    if (first_bad < total)
-        return fail(h, BPOSD_ERR_INVALID, "channel_probs_rows[%lld][%d] = %g is not a probability", (long long)(first_bad / h->n),
-                    (int)(first_bad % h->n), channel_probs_rows[first_bad]);
-    return decode_host_impl(h, IoPtrs{synd, nullptr, osdw, osd0, bp, conv, iters, llr}, B, false, false, channel_probs_rows);
-}
-
-int bposd_decode_batch(bposd_handle* h, const uint8_t* synd, int64_t B, uint8_t* osdw, uint8_t* osd0,
-                       uint8_t* bp, uint8_t* conv, int32_t* iters, double* llr) {
-    return decode_host_impl(h, IoPtrs{synd, nullptr, osdw, osd0, bp, conv, iters, llr}, B);
-}
-
-int bposd_decode_batch_packed(bposd_handle* h, const uint64_t* synd_words, int64_t B, uint64_t* osdw_words, uint64_t* osd0_words,
-                              uint64_t* bp_words, uint8_t* conv, int32_t* iters) {
-    return decode_host_impl(h, IoPtrs{(const uint8_t*)synd_words, nullptr, (uint8_t*)osdw_words, (uint8_t*)osd0_words, (uint8_t*)bp_words,
-                                      conv, iters, nullptr}, B, /*packed=*/true);
-}
-
-int bposd_posterior_llr(bposd_handle* h, const uint8_t* synd, int64_t B, double* llr, uint8_t* bp, uint8_t* conv, int32_t* iters) {
-    if (!h) return BPOSD_ERR_INVALID;
-    if (!llr) return fail(h, BPOSD_ERR_INVALID, "llr buffer is required");
-    std::vector<uint8_t> scratch;
-    if (!bp) { scratch.resize((size_t)std::max<int64_t>(B, 0) * h->n); bp = scratch.data(); }
-    // the osdw slot of the call receives BP's hard decisions (what a decoder with osd_method "osd_off" returns)
-    return decode_host_impl(h, IoPtrs{synd, nullptr, bp, nullptr, nullptr, conv, iters, llr}, B, /*packed=*/false, /*bp_only=*/true);
-}
-
-int bposd_decode_batch_select(bposd_handle* h, const uint8_t* synd, int64_t B, const uint8_t* sel,
-                              const double* alt, uint8_t* osdw, uint8_t* osd0, uint8_t* bp, uint8_t* conv,
-                              int32_t* iters, double* llr) {
-    if (!h) return BPOSD_ERR_INVALID;
-    if (!sel) return fail(h, BPOSD_ERR_INVALID, "select is required");
-    int rc = upload_alt_channel(h, alt);
-    if (rc) return rc;
-    return decode_host_impl(h, IoPtrs{synd, sel, osdw, osd0, bp, conv, iters, llr}, B);
-}
-
-// The host-pointer paths drain what they have enqueued before they return an error: downloads into the caller's buffers,
-// or into a buffer local to a caller of theirs, may be in flight.  Armed from its declaration to the successful return.
-struct DrainOnError {
-    bposd_handle* h;
-    bool armed = true;
-    ~DrainOnError() {
-        if (!armed) return;
-        const std::string first = h->err;  // (the error being returned, not one of the drain)
-        (void)sync_all_lanes(h);
-        h->err = first;
-    }
-};
-
-// Chunks of a synchronous host-pointer call of B syndromes, about `target` each (BPOSD_HOST_CHUNK overrides the target), at
-// most BPOSD_MAX_CHUNKS; an HBM-resident code keeps at least four workgroups per CU in a chunk.
-static int host_chunk_count(const bposd_handle* h, int64_t B, long long target) {
-    if (const char* e = getenv("BPOSD_HOST_CHUNK")) target = std::max(1LL, atoll(e));
-    int nchunks = (int)std::min<long long>(BPOSD_MAX_CHUNKS, std::max<long long>(1, (B + target / 2) / target));
-    if (h->large) nchunks = (int)std::min<long long>(nchunks, std::max<long long>(1, B / (4LL * h->num_cu)));
-    return nchunks;
-}
-
-static size_t row_bytes(int bits, bool packed) { return packed ? ((size_t)bits + 63) / 64 * 8 : (size_t)bits; }
-
-// A lane's staging buffers for a host-pointer call that wants the outputs named in `host`: rows of words or of bytes.
-// The kernels get lane_ptrs(L, native, ...), uploads and downloads use lane_ptrs(L, packed, ...); the two differ for packed
-// rows around kernels that take bytes (an unpack kernel in front of them, pack kernels behind).
-static IoPtrs lane_ptrs(const Lane& L, bool words, const IoPtrs& host) {
-    IoPtrs d;
-    d.synd = (const uint8_t*)(words ? L.io_psynd.p : L.io_synd.p);
-    d.sel = host.sel ? (const uint8_t*)L.io_sel.p : nullptr;
-    d.osdw = (uint8_t*)(words ? L.io_posdw.p : L.io_osdw.p);
-    d.osd0 = host.osd0 ? (uint8_t*)(words ? L.io_posd0.p : L.io_osd0.p) : nullptr;
-    d.bp = host.bp ? (uint8_t*)(words ? L.io_pbp.p : L.io_bp.p) : nullptr;
-    d.conv = host.conv ? (uint8_t*)L.io_conv.p : nullptr;
-    d.iters = host.iters ? (int32_t*)L.io_iters.p : nullptr;
-    d.llr = host.llr ? (double*)L.io_llr.p : nullptr;
-    return d;
-}
-
-// The result rows (osdw, osd0, bp) of `cnt` syndromes from the lane to row `row0` of the caller's arrays on stream `st`,
-// packed on the way where the kernels wrote bytes (dev) and the caller takes words (wire).
-static int download_rows(bposd_handle* h, hipStream_t st, const IoPtrs& host, size_t row0, const IoPtrs& dev, const IoPtrs& wire,
-                         long long cnt, size_t rsn) {
-    const struct { uint8_t* host; const uint8_t* dev; uint8_t* wire; } outs[3] = {{host.osdw, dev.osdw, wire.osdw}, {host.osd0, dev.osd0, wire.osd0}, {host.bp, dev.bp, wire.bp}};
-    for (auto& o : outs) {
-        if (!o.host) continue;
-        // (the pack kernels wait for a free workgroup slot like any kernel: with the next chunk's persistent BP grid
-        // resident that is that chunk's tail -- the rows then leave one eighth as large)
-        if (o.wire != o.dev) { int rc = launch_pack(h, st, o.dev, cnt, h->n, (unsigned long long*)o.wire); if (rc) return rc; }
-        HIP_TRY(h, hipMemcpyAsync(o.host + row0 * rsn, o.wire, (size_t)cnt * rsn, hipMemcpyDeviceToHost, st));
-    }
-    return 0;
-}
-
-// Host-pointer decode: the batch is cut into chunks that alternate between the handle's lanes, so that the upload of
-// chunk c + 1, the kernels of chunk c and the download of chunk c - 1 overlap, and the BP workgroups of chunk c + 1 take
-// over the CUs that chunk c's stragglers and OSD kernel leave idle.  Within a lane everything is stream-ordered
-// (upload, BP, OSD, downloads), so a lane's staging buffers are reused safely two chunks later.  Page-locked host
-// buffers (bposd_host_alloc) make the copies asynchronous; with pageable memory the host thread blocks inside each
-// copy while the other lane's kernels keep running.
-// packed: synd / osdw / osd0 / bp are rows of ceil(m / 64) resp. ceil(n / 64) little-endian 64-bit words (bit i & 63 of
-// word i >> 6 = entry i) -- one eighth of the bytes over PCIe; the device unpacks the syndromes in front of the BP kernel and
-// packs the result rows behind it (sel and llr are not offered in this form).
-// bp_only (bposd_posterior_llr): no OSD stage, no OSD list, on the small path and on every chunk alike.
-// prob_rows (bposd_decode_batch_rows; validated by the caller): [B, n] error probabilities, a channel per syndrome.  Each
-// chunk's rows are converted on the host (bposd_channel_tables' routine, a few threads) into the lane's page-locked block
-// and uploaded next to the syndromes; the weight rows only where the OSD stage reads them.
-static int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed, bool bp_only, const double* prob_rows) {
-    const bool rows_cost = prob_rows && !bp_only && h->cfg.osd_method != BPOSD_OSD_OFF && osd_weighs_candidates(h);
-    auto convert_rows = [&](const double* src, size_t count, double* l0, double* cost) {
-        parallel_slices(count, [&](size_t lo, size_t hi) { (void)channel_tables(src + lo, (int64_t)(hi - lo), l0 + lo, cost ? cost + lo : nullptr); });
-    };
-    if (const int rc0 = check_batch(h, B, host.synd, host.osdw); rc0 || B == 0) return rc0;
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dev_guard.err);
-    // the records and lanes are about to be reused: earlier asynchronous calls must have drained
-    if (h->async_pending) { int rcs = sync_all_lanes(h); if (rcs) return rcs; }
-    // ---- small calls (the reference's one-syndrome `.decode()`): no copy commands at all.  The kernels read the
-    // syndromes from, and write every result to, a page-locked staging area that the device addresses directly; the call
-    // costs two host memcpys, the launches and one stream synchronisation.
-    {
-        static const bool zero_copy = !(getenv("BPOSD_ZERO_COPY") && getenv("BPOSD_ZERO_COPY")[0] == '0');
-        const size_t n8 = (size_t)h->n, m8 = (size_t)h->m, b8 = (size_t)B;
-        auto a64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-        const size_t o_syn = 0, o_sel = o_syn + a64(b8 * m8), o_osdw = o_sel + (host.sel ? a64(b8 * n8) : 0),
-                     o_osd0 = o_osdw + a64(b8 * n8), o_bp = o_osd0 + (host.osd0 ? a64(b8 * n8) : 0),
-                     o_conv = o_bp + (host.bp ? a64(b8 * n8) : 0), o_it = o_conv + a64(b8), o_llr = o_it + a64(b8 * 4),
-                     o_r0 = o_llr + (host.llr ? a64(b8 * n8 * 8) : 0), o_rc = o_r0 + (prob_rows ? a64(b8 * n8 * 8) : 0),
-                     total = o_rc + (rows_cost ? a64(b8 * n8 * 8) : 0);
-        if (zero_copy && !packed && total <= (size_t)1 << 20) {
-            Lane& L = h->lanes[0];
-            if (const int rcs = ensure_pinned(h, L.h_stage, std::max<size_t>(total, (size_t)1 << 16), hipHostMallocMapped)) return rcs;
-            unsigned char* st = L.h_stage.as<unsigned char>();
-            memcpy(st + o_syn, host.synd, b8 * m8);
-            if (host.sel) memcpy(st + o_sel, host.sel, b8 * n8);
-            if (prob_rows) convert_rows(prob_rows, b8 * n8, (double*)(st + o_r0), rows_cost ? (double*)(st + o_rc) : nullptr);
-            DecodeCall call{&L, &h->rec[0]};
-            call.bp_only = bp_only;
-            call.lean = !getenv("BPOSD_OSD_DEBUG");
-            call.osd_stream = call.lean ? L.stream : L.osd_stream;
-            IoPtrs zio{st + o_syn, host.sel ? st + o_sel : nullptr, st + o_osdw, host.osd0 ? st + o_osd0 : nullptr,
-                       host.bp ? st + o_bp : nullptr, st + o_conv, (int32_t*)(st + o_it), host.llr ? (double*)(st + o_llr) : nullptr};
-            if (prob_rows) zio.llr0_rows = (const double*)(st + o_r0);
-            if (rows_cost) zio.cost_rows = (const double*)(st + o_rc);
-            int rcz = decode_device_impl(h, call, zio, B);
-            if (rcz) { (void)sync_all_lanes(h); return rcz; }
-            h->nrec = 1;
-            if (!call.lean) { rcz = sync_all_lanes(h); if (rcz) return rcz; }
-            else HIP_TRY(h, hipStreamSynchronize(L.stream));
-            memcpy(host.osdw, st + o_osdw, b8 * n8);
-            if (host.osd0) memcpy(host.osd0, st + o_osd0, b8 * n8);
-            if (host.bp) memcpy(host.bp, st + o_bp, b8 * n8);
-            if (host.conv) memcpy(host.conv, st + o_conv, b8);
-            if (host.iters) memcpy(host.iters, st + o_it, b8 * 4);
-            if (host.llr) memcpy(host.llr, st + o_llr, b8 * n8 * 8);
-            return BPOSD_OK;
-        }
-    }
-    // Chunks of ~32768 syndromes (measured on the headline workload, 131072 syndromes: 4 chunks on the 4 lanes 31.9 ms,
-    // 8 chunks 35.6 ms -- a lane's next chunk waits for the previous one's OSD kernel and download, and every chunk pays
-    // its own straggler tail -- 2 chunks 33.0 ms), at most BPOSD_MAX_CHUNKS; BPOSD_HOST_CHUNK overrides the target size.
-    long long target = 32768;
-    // (a channel row per shot is 16 n bytes next to the syndrome's m: chunks of ~64 MB of rows bound what a lane stages)
-    if (prob_rows) target = std::min<long long>(target, std::max<long long>(1024, ((long long)64 << 20) / (16LL * h->n)));
-    int nchunks = host_chunk_count(h, B, target);
-    long long CH = (B + nchunks - 1) / nchunks;  // capacity of a lane's io buffers = the largest chunk
-    nchunks = (int)((B + CH - 1) / CH);
-    // chunk boundaries: equal sizes, except that a four-chunk call (one chunk per lane) tapers 7 : 7 : 6 : 4 -- what
-    // stays exposed at the end of the call is the LAST chunk's download and straggler tail
-    std::vector<long long> clo(nchunks + 1);
-    for (int c = 0; c <= nchunks; ++c) clo[c] = std::min<long long>((long long)B, (long long)c * CH);
-    static const bool taper = !(getenv("BPOSD_HOST_TAPER") && getenv("BPOSD_HOST_TAPER")[0] == '0');
-    if (taper && nchunks == 4 && h->nlanes >= 4 && B >= 4096) {
-        const long long w[4] = {7, 7, 6, 4};
-        long long acc = 0;
-        for (int c = 0; c < 4; ++c) { clo[c] = acc; acc += (B * w[c] / 24 + 63) / 64 * 64; }
-        clo[4] = B;
-        for (int c = 0; c < 4; ++c) clo[c] = std::min<long long>(clo[c], (long long)B);
-        CH = 0;
-        for (int c = 0; c < 4; ++c) CH = std::max(CH, clo[c + 1] - clo[c]);
-    }
-    const size_t n = (size_t)h->n, m = (size_t)h->m;
-    const size_t rsn = row_bytes(h->n, packed), rsm = row_bytes(h->m, packed);  // host row strides in bytes
-    const bool native = packed && native_packed(h);  // the kernels read packed syndromes / write packed rows themselves
-    int rc;
-    static const bool gate_env = !(getenv("BPOSD_HOST_GATE") && getenv("BPOSD_HOST_GATE")[0] == '0');
-    const bool gate = gate_env && nchunks > 1 && h->cfg.schedule == 0;  // (the serial-schedule kernel does not report its tail)
-    const bool osd_on = h->cfg.osd_method != BPOSD_OSD_OFF && !bp_only;
-    // rows of chunk c that the OSD kernel rewrote: from the compact copies into the caller's arrays (the lane is idle)
-    auto patch_osd_rows = [&](int c) -> int {
-        Lane& L = h->lanes[c % h->nlanes];
-        HIP_TRY(h, hipStreamSynchronize(L.stream));       // chunk c's kernels and its counter copy
-        HIP_TRY(h, hipStreamSynchronize(L.copy_stream));  // its bulk downloads (the patched rows must land after them)
-        L.copy_pending = false;
-        if (!osd_on || !h->rec[c].ran_osd) return 0;
-        const long long lo = clo[c];
-        const int count = h->rec[c].counters()[1];
-        if (count <= 0) return 0;
-        std::vector<uint8_t> rows((size_t)count * rsn);
-        for (int which = 0; which < 2; ++which) {
-            uint8_t* dst = which ? host.osd0 : host.osdw;
-            if (!dst) continue;
-            const void* src = which ? L.io_cmp0.p : L.io_cmpw.p;
-            if (packed && !native) {  // the compact rows, packed on the (idle) lane's stream
-                int rcp = launch_pack(h, L.stream, (const uint8_t*)src, count, (int)n, (unsigned long long*)L.io_pcmp.p);
-                if (rcp) return rcp;
-                HIP_TRY(h, hipMemcpyAsync(rows.data(), L.io_pcmp.p, rows.size(), hipMemcpyDeviceToHost, L.stream));
-                HIP_TRY(h, hipStreamSynchronize(L.stream));
-            } else {
-                HIP_TRY(h, hipMemcpy(rows.data(), src, rows.size(), hipMemcpyDeviceToHost));
-            }
-            for (int k = 0; k < count; ++k) memcpy(dst + ((size_t)lo + (size_t)L.h_list.as<int>()[k]) * rsn, rows.data() + (size_t)k * rsn, rsn);
-        }
-        return 0;
-    };
-    DrainOnError drain{h};
-    for (int c = 0; c < nchunks; ++c) {
-        const long long lo = clo[c], cnt = clo[c + 1] - clo[c];
-        if (cnt <= 0) { h->rec[c].recorded = false; h->rec[c].ran_osd = false; continue; }
-        Lane& L = h->lanes[c % h->nlanes];
-        const size_t bn = (size_t)cnt * n;
-        if (c >= h->nlanes && (rc = patch_osd_rows(c - h->nlanes))) return rc;  // the lane's previous chunk
-        if ((rc = ensure(h, L.io_synd, (size_t)CH * m))) return rc;
-        if ((rc = ensure(h, L.io_osdw, (size_t)CH * n))) return rc;
-        if (host.osd0 && (rc = ensure(h, L.io_osd0, (size_t)CH * n))) return rc;
-        if (host.bp && (rc = ensure(h, L.io_bp, (size_t)CH * n))) return rc;
-        if (host.conv && (rc = ensure(h, L.io_conv, (size_t)CH))) return rc;
-        if (host.iters && (rc = ensure(h, L.io_iters, sizeof(int) * (size_t)CH))) return rc;
-        if (host.llr && (rc = ensure(h, L.io_llr, sizeof(double) * (size_t)CH * n))) return rc;
-        if (osd_on) {
-            if ((rc = ensure(h, L.io_cmpw, (size_t)CH * n))) return rc;
-            if (host.osd0 && (rc = ensure(h, L.io_cmp0, (size_t)CH * n))) return rc;
-            if ((rc = ensure_pinned(h, L.h_list, sizeof(int) * (size_t)CH, hipHostMallocDefault))) return rc;
-        }
-        if (c > 0) HIP_TRY(h, hipStreamWaitEvent(L.stream, h->lanes[(c - 1) % h->nlanes].ev_up, 0));
-        if (packed) {
-            if ((rc = ensure(h, L.io_psynd, (size_t)CH * rsm))) return rc;
-            if ((rc = ensure(h, L.io_posdw, (size_t)CH * rsn))) return rc;
-            if (host.osd0 && (rc = ensure(h, L.io_posd0, (size_t)CH * rsn))) return rc;
-            if (host.bp && (rc = ensure(h, L.io_pbp, (size_t)CH * rsn))) return rc;
-            if (osd_on && (rc = ensure(h, L.io_pcmp, (size_t)CH * rsn))) return rc;
-        }
-        HIP_TRY(h, hipMemcpyAsync(packed ? L.io_psynd.p : L.io_synd.p, host.synd + (size_t)lo * rsm, (size_t)cnt * rsm, hipMemcpyHostToDevice, L.stream));
-        if (host.sel) {
-            if ((rc = ensure(h, L.io_sel, (size_t)CH * n))) return rc;
-            HIP_TRY(h, hipMemcpyAsync(L.io_sel.p, host.sel + (size_t)lo * n, bn, hipMemcpyHostToDevice, L.stream));
-        }
-        if (prob_rows) {  // (the lane's previous chunk has been drained above: its staging block is free)
-            const size_t cap = (size_t)CH * n, want = cap * (rows_cost ? 2 : 1);
-            if ((rc = ensure(h, L.io_l0rows, sizeof(double) * cap))) return rc;
-            if (rows_cost && (rc = ensure(h, L.io_costrows, sizeof(double) * cap))) return rc;
-            if ((rc = ensure_pinned(h, L.h_rows, sizeof(double) * want, hipHostMallocDefault))) return rc;
-            double* const rows = L.h_rows.as<double>();
-            convert_rows(prob_rows + (size_t)lo * n, bn, rows, rows_cost ? rows + cap : nullptr);
-            HIP_TRY(h, hipMemcpyAsync(L.io_l0rows.p, rows, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
-            if (rows_cost) HIP_TRY(h, hipMemcpyAsync(L.io_costrows.p, rows + cap, sizeof(double) * bn, hipMemcpyHostToDevice, L.stream));
-        }
-        HIP_TRY(h, hipEventRecord(L.ev_up, L.stream));
-        IoPtrs dev = lane_ptrs(L, native, host);
-        const IoPtrs wire = lane_ptrs(L, packed, host);
-        if (prob_rows) {
-            dev.llr0_rows = (const double*)L.io_l0rows.p;
-            dev.cost_rows = rows_cost ? (const double*)L.io_costrows.p : nullptr;
-        }
-        if (wire.synd != dev.synd && (rc = launch_unpack(h, L.stream, (const unsigned long long*)wire.synd, cnt, (int)m, (uint8_t*)dev.synd))) return rc;
-        // Chunk c's kernels are released when chunk c - 1's BP kernel has handed out its last syndrome (its tail begins; the
-        // flag is written by that kernel into page-locked memory) or has ended: the chunks then run in order, each filling
-        // the previous one's tail, instead of sharing the CUs from the start and all finishing at the end of the call.
-        if (c > 0 && gate) {
-            Lane& Pv = h->lanes[(c - 1) % h->nlanes];
-            // poll the flag (a plain load from page-locked memory); the runtime is asked only every so often and the
-            // thread backs off after a short spin -- a chunk's BP kernel runs for milliseconds
-            hipError_t qe = hipErrorNotReady;
-            for (unsigned spins = 0; *Pv.h_tail.as<volatile int>() == 0; ++spins) {
-                if ((spins & 63) == 63) {
-                    qe = hipEventQuery(Pv.ev_bp);
-                    if (qe != hipErrorNotReady) break;
-                }
-                if (spins < 2000) __builtin_ia32_pause();
-                else std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-            if (qe != hipErrorNotReady && qe != hipSuccess)
-                return fail(h, BPOSD_ERR_HIP, "hipEventQuery failed while waiting for chunk %d: %s", c - 1, hipGetErrorString(qe));
-        }
-        *L.h_tail.as<volatile int>() = 0;
-        DecodeCall call{&L, &h->rec[c], L.osd_stream};
-        call.batch_hint = B;  // kernel variants are chosen for the call, not for a chunk
-        call.cmp_osdw = osd_on ? (uint8_t*)L.io_cmpw.p : nullptr;
-        call.cmp_osd0 = (osd_on && host.osd0) ? (uint8_t*)L.io_cmp0.p : nullptr;
-        call.bp_only = bp_only;
-        call.packed = native;
-        call.tail_gate = true;  // (also makes the call record ev_bp, which the downloads below wait for)
-        if ((rc = decode_device_impl(h, call, dev, cnt))) return rc;
-        // Downloads: everything the BP kernel wrote is final when it ends, except the osdw / osd0 rows of its non-converged
-        // syndromes -- those are patched from the compact copies once the OSD kernel has run.  (Queued behind the OSD kernel
-        // on the lane's stream, as in the first version, a chunk's downloads started a whole chunk late: the OSD kernel
-        // needs a drained CU and the next chunk's persistent BP workgroups take every slot that frees up.)
-        hipStream_t cs = L.copy_stream;
-        HIP_TRY(h, hipStreamWaitEvent(cs, L.ev_bp, 0));
-        if ((rc = download_rows(h, cs, host, (size_t)lo, dev, wire, cnt, rsn))) return rc;
-        if (host.conv) HIP_TRY(h, hipMemcpyAsync(host.conv + lo, dev.conv, (size_t)cnt, hipMemcpyDeviceToHost, cs));
-        if (host.iters) HIP_TRY(h, hipMemcpyAsync(host.iters + lo, dev.iters, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, cs));
-        if (host.llr) HIP_TRY(h, hipMemcpyAsync(host.llr + (size_t)lo * n, dev.llr, sizeof(double) * bn, hipMemcpyDeviceToHost, cs));
-        if (osd_on) HIP_TRY(h, hipMemcpyAsync(L.h_list.p, L.osd_list.p, sizeof(int) * (size_t)cnt, hipMemcpyDeviceToHost, cs));
-        L.copy_pending = true;
-    }
-    for (int c = std::max(0, nchunks - h->nlanes); c < nchunks; ++c)
-        if ((rc = patch_osd_rows(c))) return rc;
-    h->nrec = nchunks;
-    drain.armed = false;
-    return sync_all_lanes(h);
-}
-
-// Asynchronous host-pointer decode: ONE lane, everything in stream order -- upload (packed rows: + unpack kernel), BP,
-// OSD, (pack kernels,) downloads -- and the call returns once that is enqueued.  Consecutive calls take consecutive lanes,
-// so call k + 1's BP workgroups fill the straggler tail of call k and call k's OSD kernel, packing and downloads run
-// under call k + 1's BP kernel: the host-to-host rate of a stream of batches approaches the device-resident one (a lone
-// synchronous call always pays its own upload, its 1922-iteration tail and its download).  The caller's buffers must be
-// page-locked (bposd_host_alloc) for the copies to be asynchronous, and stay untouched until bposd_synchronize_lane().
-static int decode_host_async_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed) {
-    if (const int rc0 = check_batch(h, B, host.synd, host.osdw); rc0 || B == 0) return rc0;
-    if (packed && host.llr) return fail(h, BPOSD_ERR_INVALID, "the packed form has no LLR output");
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dev_guard.err);
-    // a synchronous host-pointer call leaves no work behind, but its per-chunk records and staging are per lane too: nothing
-    // to drain here.  Buffers grow on every lane at once (no allocation inside a later call of the same size).
-    const size_t n = (size_t)h->n, m = (size_t)h->m, b8 = (size_t)B;
-    const size_t rsn = row_bytes(h->n, packed), rsm = row_bytes(h->m, packed);
-    int rc;
-    bool grew = false;
-    auto need = [&](DevBuf Lane::*member, size_t bytes) -> int { return grow_lanes(h, member, bytes, &grew); };
-    if ((rc = need(&Lane::io_synd, b8 * m))) return rc;
-    if ((rc = need(&Lane::io_osdw, b8 * n))) return rc;
-    if (host.osd0 && (rc = need(&Lane::io_osd0, b8 * n))) return rc;
-    if (host.bp && (rc = need(&Lane::io_bp, b8 * n))) return rc;
-    if ((rc = need(&Lane::io_conv, b8))) return rc;
-    if ((rc = need(&Lane::io_iters, sizeof(int) * b8))) return rc;
-    if (host.llr && (rc = need(&Lane::io_llr, sizeof(double) * b8 * n))) return rc;
-    if (packed) {
-        if ((rc = need(&Lane::io_psynd, b8 * rsm))) return rc;
-        if ((rc = need(&Lane::io_posdw, b8 * rsn))) return rc;
-        if (host.osd0 && (rc = need(&Lane::io_posd0, b8 * rsn))) return rc;
-        if (host.bp && (rc = need(&Lane::io_pbp, b8 * rsn))) return rc;
-    }
-    DecodeCall call = take_next_lane(h);
-    Lane& L = *call.lane;
-    if (L.copy_pending) { HIP_TRY(h, hipStreamSynchronize(L.copy_stream)); L.copy_pending = false; }
-    // The copies and the pack / unpack kernels go to the lane's HIGH-PRIORITY stream (the one its OSD kernel runs on), ordered
-    // against the lane's main stream by events: when workgroup slots free up in the tail of another call's BP kernel these small
-    // kernels are dispatched first instead of competing with the next persistent BP grid for every slot.
-    hipStream_t hs = L.osd_stream;
-    HIP_TRY(h, hipEventRecord(L.ev_copy, L.stream));   // the lane's previous call (its downloads included) has finished
-    HIP_TRY(h, hipStreamWaitEvent(hs, L.ev_copy, 0));
-    call.packed = packed && native_packed(h);  // the kernels read packed syndromes / write packed rows themselves
-    IoPtrs dev = lane_ptrs(L, call.packed, host);
-    dev.conv = (uint8_t*)L.io_conv.p;  // (written whether or not the caller takes them)
-    dev.iters = (int32_t*)L.io_iters.p;
-    const IoPtrs wire = lane_ptrs(L, packed, host);
-    HIP_TRY(h, hipMemcpyAsync((void*)wire.synd, host.synd, b8 * rsm, hipMemcpyHostToDevice, hs));
-    if (wire.synd != dev.synd && (rc = launch_unpack(h, hs, (const unsigned long long*)wire.synd, B, (int)m, (uint8_t*)dev.synd))) return rc;
-    HIP_TRY(h, hipEventRecord(L.ev_up, hs));
-    HIP_TRY(h, hipStreamWaitEvent(L.stream, L.ev_up, 0));
-    DrainOnError drain{h};
-    if ((rc = decode_device_impl(h, call, dev, B))) return rc;
-    // (decode_device_impl has made L.stream wait for the OSD kernel: an event on it covers both kernels)
-    HIP_TRY(h, hipEventRecord(L.ev_copy, L.stream));
-    HIP_TRY(h, hipStreamWaitEvent(hs, L.ev_copy, 0));
-    if (host.conv) HIP_TRY(h, hipMemcpyAsync(host.conv, dev.conv, b8, hipMemcpyDeviceToHost, hs));
-    if (host.iters) HIP_TRY(h, hipMemcpyAsync(host.iters, dev.iters, sizeof(int) * b8, hipMemcpyDeviceToHost, hs));
-    if ((rc = download_rows(h, hs, host, 0, dev, wire, B, rsn))) return rc;
-    if (host.llr) HIP_TRY(h, hipMemcpyAsync(host.llr, dev.llr, sizeof(double) * b8 * n, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(h, hipEventRecord(L.ev_osd, hs));               // bposd_synchronize_lane waits on the main stream:
-    HIP_TRY(h, hipStreamWaitEvent(L.stream, L.ev_osd, 0));  // make it cover the downloads
-    drain.armed = false;
-    return BPOSD_OK;
-}
-
-int bposd_decode_batch_async(bposd_handle* h, const uint8_t* synd, int64_t B, uint8_t* osdw, uint8_t* osd0, uint8_t* bp,
-                             uint8_t* conv, int32_t* iters, double* llr) {
-    return decode_host_async_impl(h, IoPtrs{synd, nullptr, osdw, osd0, bp, conv, iters, llr}, B, /*packed=*/false);
-}
-
-int bposd_decode_batch_packed_async(bposd_handle* h, const uint64_t* synd_words, int64_t B, uint64_t* osdw_words, uint64_t* osd0_words,
-                                    uint64_t* bp_words, uint8_t* conv, int32_t* iters) {
-    return decode_host_async_impl(h, IoPtrs{(const uint8_t*)synd_words, nullptr, (uint8_t*)osdw_words, (uint8_t*)osd0_words, (uint8_t*)bp_words, conv,
-                                            iters, nullptr}, B, /*packed=*/true);
 }
 
 // ================================================================================ logical observables
@@ -1241,12 +876,6 @@ int bposd_set_observables(bposd_handle* h, const uint64_t* table, int32_t k) {
     return BPOSD_OK;
 }
 
-static int check_observables(bposd_handle* h) {
-    if (!h) return BPOSD_ERR_INVALID;
-    if (h->obs_k <= 0) return fail(h, BPOSD_ERR_INVALID, "no observables are set on this handle (bposd_set_observables)");
-    return BPOSD_OK;
-}
-
 int bposd_observables_device_lane(bposd_handle* h, int32_t lane, const void* d_rows, int32_t packed, int64_t B, uint64_t* d_obs_words) {
     if (const int rc = check_observables(h)) return rc;
     if (lane < 0 || lane >= h->nlanes) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range", lane);
@@ -1260,71 +889,6 @@ int bposd_observables_device_lane(bposd_handle* h, int32_t lane, const void* d_r
     return launch_obs(h, h->lanes[lane].stream, rows, packed != 0, B, outs);
 }
 
-// The outputs of an observables decode: rows of ceil(k / 64) words, flags and iteration counts (host or device memory).
-struct ObsOut {
-    uint64_t *osdw = nullptr, *osd0 = nullptr, *bp = nullptr;
-    uint8_t* conv = nullptr;
-    int32_t* iters = nullptr;
-};
-
-// Lane buffers of an observables decode of up to `cap` syndromes: the rows the kernels write (packed where the kernels are,
-// bytes otherwise), the syndromes in the kernels' form where the caller's are in the other one, and for a host-pointer
-// call the syndromes as uploaded and the outputs to download.
-static int obs_reserve(bposd_handle* h, size_t cap, const ObsOut& out, bool host, bool synd_packed) {
-    const bool native = native_packed(h);
-    const size_t rs = row_bytes(h->n, native), ob = sizeof(uint64_t) * (size_t)((h->obs_k + 63) / 64);
-    bool drained = false;
-    int rc;
-    if ((rc = grow_lanes(h, native ? &Lane::io_posdw : &Lane::io_osdw, cap * rs, &drained))) return rc;
-    if (out.osd0 && (rc = grow_lanes(h, native ? &Lane::io_posd0 : &Lane::io_osd0, cap * rs, &drained))) return rc;
-    if (out.bp && (rc = grow_lanes(h, native ? &Lane::io_pbp : &Lane::io_bp, cap * rs, &drained))) return rc;
-    if ((host || native != synd_packed) && (rc = grow_lanes(h, native ? &Lane::io_psynd : &Lane::io_synd, cap * row_bytes(h->m, native), &drained))) return rc;
-    if (!host) return 0;
-    if (native != synd_packed && (rc = grow_lanes(h, synd_packed ? &Lane::io_psynd : &Lane::io_synd, cap * row_bytes(h->m, synd_packed), &drained))) return rc;
-    if ((rc = grow_lanes(h, &Lane::io_obsw, cap * ob, &drained))) return rc;
-    if (out.osd0 && (rc = grow_lanes(h, &Lane::io_obs0, cap * ob, &drained))) return rc;
-    if (out.bp && (rc = grow_lanes(h, &Lane::io_obsbp, cap * ob, &drained))) return rc;
-    if ((rc = grow_lanes(h, &Lane::io_conv, cap, &drained))) return rc;
-    return grow_lanes(h, &Lane::io_iters, sizeof(int) * cap, &drained);
-}
-
-// One decode into the lane's own row buffers with obs_kernel behind it, everything on the call's lane: `d_synd` (bytes or
-// packed words) is brought into the kernels' form first where it is in the other one; `out` is device memory.
-static int decode_obs_impl(bposd_handle* h, DecodeCall call, const void* d_synd, bool synd_packed, int64_t B, const ObsOut& out) {
-    Lane& L = *call.lane;
-    // the lane's io buffers are also read by its copy stream in the host-pointer decode path
-    if (L.copy_pending) { HIP_TRY(h, hipStreamSynchronize(L.copy_stream)); L.copy_pending = false; }
-    const bool native = native_packed(h);
-    int rc;
-    if (native && !synd_packed) {
-        if ((rc = launch_pack(h, L.stream, (const uint8_t*)d_synd, B, h->m, (unsigned long long*)L.io_psynd.p))) return rc;
-        d_synd = L.io_psynd.p;
-    } else if (!native && synd_packed) {
-        if ((rc = launch_unpack(h, L.stream, (const unsigned long long*)d_synd, B, h->m, (uint8_t*)L.io_synd.p))) return rc;
-        d_synd = L.io_synd.p;
-    }
-    call.packed = native;
-    IoPtrs dev;
-    dev.synd = (const uint8_t*)d_synd;
-    dev.osdw = (uint8_t*)(native ? L.io_posdw.p : L.io_osdw.p);
-    dev.osd0 = out.osd0 ? (uint8_t*)(native ? L.io_posd0.p : L.io_osd0.p) : nullptr;
-    dev.bp = out.bp ? (uint8_t*)(native ? L.io_pbp.p : L.io_bp.p) : nullptr;
-    dev.conv = out.conv;
-    dev.iters = out.iters;
-    if ((rc = decode_device_impl(h, call, dev, B))) return rc;
-    // (decode_device_impl has made the lane's stream wait for the OSD kernel: the rows are final)
-    const void* const rows[3] = {dev.osdw, dev.osd0, dev.bp};
-    uint64_t* const outs[3] = {out.osdw, out.osd0, out.bp};
-    CallRecord& R = *call.rec;  // (bposd_last_timing's events end in front of obs_kernel: it has a pair of its own)
-    for (auto& e : R.ev_obs)
-        if (!e) HIP_TRY(h, hipEventCreate(&e.raw));
-    HIP_TRY(h, hipEventRecord(R.ev_obs[0], L.stream));
-    if ((rc = launch_obs(h, L.stream, rows, native, B, outs))) return rc;
-    HIP_TRY(h, hipEventRecord(R.ev_obs[1], L.stream));
-    R.ran_obs = true;
-    return 0;
-}
-
 int bposd_decode_batch_observables_device(bposd_handle* h, const void* d_synd, int32_t synd_packed, int64_t B, uint64_t* d_obs_osdw,
                                           uint64_t* d_obs_osd0, uint64_t* d_obs_bp, uint8_t* d_conv, int32_t* d_iters) {
     if (const int rc = check_observables(h)) return rc;
@@ -1334,88 +898,6 @@ int bposd_decode_batch_observables_device(bposd_handle* h, const void* d_synd, i
     const ObsOut out{d_obs_osdw, d_obs_osd0, d_obs_bp, d_conv, d_iters};
     if (const int rc = obs_reserve(h, (size_t)B, out, /*host=*/false, synd_packed != 0)) return rc;
     return decode_obs_impl(h, take_next_lane(h), d_synd, synd_packed != 0, B, out);
-}
-
-// Syndromes [lo, lo + cnt) of a host-pointer call on the call's lane, in stream order: upload, decode + obs_kernel on
-// lane-resident rows, download of cnt x ceil(k / 64) words per requested output and of the flags and iteration counts.
-// (An asynchronous call with its copies and the conversion kernel on the lane's high-priority stream, the way
-// decode_host_async_impl places its own, was measured and is slower here: 23.4 against 22.8 ms per call of 131072 on
-// [[1922,50]], DESIGN.md 4.10 -- these copies are 24 B per shot, not 744.)
-static int obs_host_step(bposd_handle* h, const DecodeCall& call, const uint8_t* synd, bool synd_packed, int64_t lo, int64_t cnt,
-                         const ObsOut& host) {
-    Lane& L = *call.lane;
-    const size_t rsm = row_bytes(h->m, synd_packed), kw = (size_t)((h->obs_k + 63) / 64), c8 = (size_t)cnt;
-    void* const wire = synd_packed ? L.io_psynd.p : L.io_synd.p;
-    HIP_TRY(h, hipMemcpyAsync(wire, synd + (size_t)lo * rsm, c8 * rsm, hipMemcpyHostToDevice, L.stream));
-    ObsOut dev;
-    dev.osdw = (uint64_t*)L.io_obsw.p;
-    dev.osd0 = host.osd0 ? (uint64_t*)L.io_obs0.p : nullptr;
-    dev.bp = host.bp ? (uint64_t*)L.io_obsbp.p : nullptr;
-    dev.conv = (uint8_t*)L.io_conv.p;
-    dev.iters = (int32_t*)L.io_iters.p;
-    if (const int rc = decode_obs_impl(h, call, wire, synd_packed, cnt, dev)) return rc;
-    const struct { uint64_t* host; const uint64_t* dev; } outs[3] = {{host.osdw, dev.osdw}, {host.osd0, dev.osd0}, {host.bp, dev.bp}};
-    for (auto& o : outs)
-        if (o.host) HIP_TRY(h, hipMemcpyAsync(o.host + (size_t)lo * kw, o.dev, sizeof(uint64_t) * c8 * kw, hipMemcpyDeviceToHost, L.stream));
-    if (host.conv) HIP_TRY(h, hipMemcpyAsync(host.conv + lo, dev.conv, c8, hipMemcpyDeviceToHost, L.stream));
-    if (host.iters) HIP_TRY(h, hipMemcpyAsync(host.iters + lo, dev.iters, sizeof(int) * c8, hipMemcpyDeviceToHost, L.stream));
-    return 0;
-}
-
-// Host-pointer observables decode.  Synchronous: chunks of ~32768 syndromes alternate between the lanes like those of
-// bposd_decode_batch, one record per chunk.  Asynchronous: the whole call on the handle's next lane.  Neither needs the
-// compact-row machinery of decode_host_impl: obs_kernel runs after OSD has rewritten its rows on the device.
-static int decode_obs_host_impl(bposd_handle* h, const void* synd, bool synd_packed, int64_t B, const ObsOut& host, bool async) {
-    if (const int rc = check_observables(h)) return rc;
-    if (const int rc = check_batch(h, B, synd, host.osdw); rc || B == 0) return rc;
-    DeviceGuard dev_guard(h->device);
-    HIP_TRY(h, dev_guard.err);
-    int rc;
-    if (async) {
-        if ((rc = obs_reserve(h, (size_t)B, host, /*host=*/true, synd_packed))) return rc;
-        const DecodeCall call = take_next_lane(h);
-        DrainOnError drain{h};
-        if ((rc = obs_host_step(h, call, (const uint8_t*)synd, synd_packed, 0, B, host))) return rc;
-        drain.armed = false;
-        return BPOSD_OK;
-    }
-    // the records and lanes are about to be reused: earlier asynchronous calls must have drained
-    if (h->async_pending) { int rcs = sync_all_lanes(h); if (rcs) return rcs; }
-    int nchunks = host_chunk_count(h, B, 32768);
-    const long long CH = (B + nchunks - 1) / nchunks;
-    nchunks = (int)((B + CH - 1) / CH);
-    if ((rc = obs_reserve(h, (size_t)CH, host, /*host=*/true, synd_packed))) return rc;
-    DrainOnError drain{h};
-    for (int c = 0; c < nchunks; ++c) {
-        const long long lo = (long long)c * CH, cnt = std::min<long long>(CH, B - lo);
-        Lane& L = h->lanes[c % h->nlanes];
-        DecodeCall call{&L, &h->rec[c], L.osd_stream};
-        call.batch_hint = B;  // kernel variants are chosen for the call, not for a chunk
-        if ((rc = obs_host_step(h, call, (const uint8_t*)synd, synd_packed, lo, cnt, host))) return rc;
-    }
-    h->nrec = nchunks;
-    drain.armed = false;
-    return sync_all_lanes(h);
-}
-
-int bposd_decode_batch_observables(bposd_handle* h, const uint8_t* synd, int64_t B, uint64_t* obs_osdw, uint64_t* obs_osd0,
-                                   uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
-    return decode_obs_host_impl(h, synd, false, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/false);
-}
-
-int bposd_decode_batch_observables_packed(bposd_handle* h, const uint64_t* synd_words, int64_t B, uint64_t* obs_osdw, uint64_t* obs_osd0,
-                                          uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
-    return decode_obs_host_impl(h, synd_words, true, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/false);
-}
-
-int bposd_decode_batch_observables_async(bposd_handle* h, const uint8_t* synd, int64_t B, uint64_t* obs_osdw, uint64_t* obs_osd0,
-                                         uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
-    return decode_obs_host_impl(h, synd, false, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/true);
-}
-
-int bposd_decode_batch_observables_packed_async(bposd_handle* h, const uint64_t* synd_words, int64_t B, uint64_t* obs_osdw,
-                                                uint64_t* obs_osd0, uint64_t* obs_bp, uint8_t* conv, int32_t* iters) {
-    return decode_obs_host_impl(h, synd_words, true, B, ObsOut{obs_osdw, obs_osd0, obs_bp, conv, iters}, /*async=*/true);
 }
 
 int bposd_debug_obs_timing(bposd_handle* h, int32_t lane, double* obs_ms) {

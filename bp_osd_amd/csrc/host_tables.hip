@@ -1,7 +1,8 @@
 // host_tables.hip -- host side of libbposd_mi355x.so, what bposd_create runs once per code: GF(2) rank, priors, the
 // Tanner-graph tables of every BP kernel family with their layout searches (local_layout.h, class_layout.h), the rank
 // probe of large codes, and the host-only bposd_debug_* exports that report those layouts without a device.
-// The decode calls are in bposd_capi.hip; the declarations shared with it are in internal.h.
+// The decode calls are in bposd_capi.hip (device pointers) and decode_host.hip (host pointers); the declarations shared with
+// them are in internal.h.
 #include "internal.h"
 
 #include <climits>

@@ -1,7 +1,8 @@
 // internal.h -- host-side state shared by the translation units of libbposd_mi355x.so (not part of the C-ABI).
-// bposd_capi.hip holds the C-ABI and the decode calls, host_tables.hip table construction and the layout searches; every
-// launch_*.hip holds the instantiations and launch code of one kernel family, so that the families compile in parallel
-// (bp_osd_amd/build.py).  Every device block, page-locked block, stream and event below is held by an owning type of
+// bposd_capi.hip holds creation, the one BP + OSD launch pair every decode ends in (decode_device_impl) and the device-pointer
+// calls, decode_host.hip the host-pointer calls with their chunk plan, host_tables.hip table construction and the layout
+// searches; every launch_*.hip holds the instantiations and launch code of one kernel family, so that the families compile in
+// parallel (bp_osd_amd/build.py).  Every device block, page-locked block, stream and event below is held by an owning type of
 // owned.h: deleting a handle frees all of it, and a resource added to Lane, CallRecord or bposd_handle needs no line anywhere else.
 #pragma once
 #include "../../include/bposd_mi355x.h"
@@ -238,6 +239,50 @@ inline bool native_packed(const bposd_handle* h) {
     // (forced local-edge variants 16 .. 26 have no packed instantiation; the LDS and class kernels switch at run time)
     return !h->bp_any && h->cfg.schedule == 0 && h->bp_variant != 64 && !(h->bp_variant >= 16 && h->bp_variant <= 26);
 }
+
+// ---- the decode calls (bposd_capi.hip), as the host-pointer paths (decode_host.hip) use them
+// Device-side I/O of one kernel pair: rows of bytes, or of little-endian 64-bit words where the call is packed.  The same
+// struct names the caller's arrays of a host-pointer call (null: that output is not wanted).
+struct IoPtrs {
+    const uint8_t* synd = nullptr;
+    const uint8_t* sel = nullptr;
+    uint8_t *osdw = nullptr, *osd0 = nullptr, *bp = nullptr, *conv = nullptr;
+    int32_t* iters = nullptr;
+    double* llr = nullptr;
+    // a channel of its own for every syndrome (bposd_decode_batch_rows*): rows [B, n] of prior LLRs and of OSD-W weights
+    // as bposd_channel_tables makes them; cost_rows is null where OSD does not weigh candidates
+    const double* llr0_rows = nullptr;
+    const double* cost_rows = nullptr;
+};
+// The outputs of an observables decode: rows of ceil(k / 64) words, flags and iteration counts (host or device memory).
+struct ObsOut {
+    uint64_t *osdw = nullptr, *osd0 = nullptr, *bp = nullptr;
+    uint8_t* conv = nullptr;
+    int32_t* iters = nullptr;
+};
+bool osd_weighs_candidates(const bposd_handle* h);  // does the OSD stage rank candidates by the channel's weights?
+int check_batch(bposd_handle* h, int64_t B, const void* synd, const void* osdw);  // every decode entry point, before anything is enqueued
+int check_observables(bposd_handle* h);
+DecodeCall take_next_lane(bposd_handle* h);  // a stand-alone call on the handle's next lane, record 0 of a new "last call"
+int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io, int64_t B);  // one BP + one OSD launch, `io` in device memory
+int obs_reserve(bposd_handle* h, size_t cap, const ObsOut& out, bool host, bool synd_packed);
+int decode_obs_impl(bposd_handle* h, DecodeCall call, const void* d_synd, bool synd_packed, int64_t B, const ObsOut& out);
+int check_alt_channel(bposd_handle* h, const double* alt);
+int upload_alt_channel(bposd_handle* h, const double* alt);
+// rows of 0/1 bytes <-> rows of 64-bit words on a stream (pack_rows_kernel, unpack_rows_kernel); wg_per_cu caps the grid
+int launch_pack(bposd_handle* h, hipStream_t st, const uint8_t* d_bytes, long long B, int n, unsigned long long* d_words, int wg_per_cu = 2);
+int launch_unpack(bposd_handle* h, hipStream_t st, const unsigned long long* d_words, long long B, int n, uint8_t* d_bytes);
+
+// ---- host-pointer calls (decode_host.hip)
+size_t row_bytes(int bits, bool packed);  // one row of `bits` entries: bytes, or 64-bit words
+IoPtrs lane_ptrs(const Lane& L, bool words, const IoPtrs& host);  // the lane's row buffers of either form, for the outputs `host` names
+// The chunks of a synchronous host-pointer call of B syndromes: chunk c is [lo[c], lo[c + 1]), `capacity` the largest.
+struct HostChunkPlan {
+    int count = 0;
+    long long capacity = 0;
+    long long lo[BPOSD_MAX_CHUNKS + 1] = {};
+};
+HostChunkPlan host_chunk_plan(long long B, int n, bool per_shot_rows, int nlanes, int num_cu, bool large, bool taper);
 
 // The osdw rows of the last observables decode (bposd_decode_batch_observables_device) and their form: decode_obs_impl
 // leaves them in the buffers of the lane the call took, packed words [B][ceil(n / 64)] where the kernels are packed, bytes

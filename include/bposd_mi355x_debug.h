@@ -50,6 +50,16 @@ int bposd_debug_last_instance(bposd_handle *h, int32_t bp[6], int32_t osd[6]);
  * ds_write_b64 cycles of one bit pass, their floor. */
 int bposd_debug_local_layout(const int32_t *csr_indptr, const int32_t *csr_indices, int32_t m, int32_t n, int64_t *out);
 
+/* Diagnostics, host only (no handle, no device): how a synchronous host-pointer call of B syndromes is cut into chunks for a
+ * handle of `nlanes` lanes on a device of `num_cu` CUs.  n is the block length, read only where per_shot_rows != 0
+ * (bposd_decode_batch_rows: ~64 MB of channel rows bound a chunk); large != 0 is an HBM-resident code (at least four
+ * workgroups per CU in a chunk); taper != 0 is bposd_decode_batch and its kin (a four-chunk call on four lanes is cut
+ * 7 : 7 : 6 : 4), 0 the observables calls (equal chunks).  BPOSD_HOST_CHUNK, read on every call, replaces the target chunk
+ * size.  Returns the chunk count (at most 16) and writes count + 1 ascending bounds, bounds[0] = 0 and bounds[count] = B;
+ * BPOSD_ERR_INVALID for B outside 1 .. 2^31 - 1, a non-positive n, nlanes or num_cu, or a NULL bounds. */
+int bposd_debug_host_chunks(int64_t B, int32_t n, int32_t per_shot_rows, int32_t nlanes, int32_t num_cu, int32_t large, int32_t taper,
+                            int64_t *bounds);
+
 /* Diagnostics, host only: the wave pairing of that layout.  The two-checks-per-thread kernels run groups w and w + MP / 128
  * in wave w; groups of equal key (4 * dl(slot 0) + dl(slot 1), 15 = a slot whose lanes differ) are moved into the same wave,
  * which then runs a loop body compiled for that key.  group_key [MP / 64], pos_chk [MP] (check at a position, -1 padding),

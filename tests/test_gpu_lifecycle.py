@@ -113,8 +113,10 @@ def test_buffers_grow_idle_and_regrow_on_one_handle(gpu_ready, hgp400, monkeypat
     (B = 3000: past the stage's 1 MiB, the page-locked OSD lists appear), the stage again, a channel row per shot through the
     stage (B = 2), one chunk (B = 200) and twelve larger ones (B = 3000: the page-locked row block appears, then regrows), the
     asynchronous packed call (B = 512, then 3000), more select calls than lanes (every lane's alternative-channel block is
-    made, the first lane's reused), and B = 6000, which regrows every lane buffer after use.  Every output of every call,
-    LLR bits included where the entry point returns them, equals the oracle's on the same syndromes."""
+    made, the first lane's reused), and B = 6000, which regrows every lane buffer after use.  Then chunks of 1024: four
+    tapered chunks, one per lane (B = 4096), four equal ones (B = 4095) and the synchronous packed call (B = 4096), each with
+    the call's OSD count summed over its chunk records.  Every output of every call, LLR bits included where the entry point
+    returns them, equals the oracle's on the same syndromes."""
     import torch
 
     from bp_osd_amd import BpOsdDecoder
@@ -194,3 +196,24 @@ def test_buffers_grow_idle_and_regrow_on_one_handle(gpu_ready, hgp400, monkeypat
         _compare_exact(got, ref_sel[k % 2])
 
     plain(6000)
+
+    # chunks of 1024 on the same handle: 4096 shots are one tapered chunk per lane (bounds 0, 1216, 2432, 3456, 4096), 4095
+    # four equal ones, one shot short of the taper; a synchronous packed call patches its OSD rows from packed compact copies
+    # in every chunk.  The OSD count of the call sums the four chunk records.
+    monkeypatch.setenv("BPOSD_HOST_CHUNK", "1024")
+    failed = ref["converged"] == 0  # (the oracle's flags are uint8: ~ is no mask)
+    taper = [0, 1216, 2432, 3456, 4096]
+    assert all(failed[lo:hi].any() for lo, hi in zip(taper, taper[1:])), "a chunk without a shot for OSD"
+
+    def packed_sync(B):
+        wn = (n + 63) // 64
+        out = dict(osdw=np.zeros((B, wn), np.uint64), osd0=np.zeros((B, wn), np.uint64), bp=np.zeros((B, wn), np.uint64),
+                   conv=np.zeros(B, np.uint8), iters=np.zeros(B, np.int32))
+        g.decode_batch_packed_into(g.pack_rows(S[:B]), out["osdw"], out["osd0"], out["bp"], out["conv"], out["iters"], wait=True)
+        got = dict(osdw=g.unpack_rows(out["osdw"], n), osd0=g.unpack_rows(out["osd0"], n), bp=g.unpack_rows(out["bp"], n),
+                   converged=out["conv"].astype(bool), iters=out["iters"])
+        _compare_exact(got, _head(ref, B))
+
+    for call, B in ((plain, 4096), (plain, 4095), (packed_sync, 4096)):
+        call(B)
+        assert g.last_timing()["osd_invocations"] == int(failed[:B].sum())

@@ -241,3 +241,53 @@ def test_panel_phase_by_six_column_sub_blocks_model():
     spec.loader.exec_module(mod)
     for seed in range(300):
         mod.check(seed)
+
+
+def _equal_chunks(B, size, count):
+    return [min(B, c * size) for c in range(count + 1)]
+
+
+# (B, BPOSD_HOST_CHUNK or None, overrides of the defaults below) -> expected bounds.  The bounds are the arithmetic of the
+# host-pointer call as it stood before host_chunk_plan existed (target 32768 or BPOSD_HOST_CHUNK, or ~64 MB of channel rows;
+# count = clamp((B + target / 2) / target, 1, 16), an HBM-resident code keeps 4 * num_cu shots per chunk; equal chunks of
+# ceil(B / count), recounted; four chunks on four lanes from 4096 shots taper ceil64(B * 7 / 24) twice, ceil64(B * 6 / 24)
+# and the rest), worked out by hand for every row -- never taken from the library.
+_HOST_CHUNK_CASES = [
+    (1, None, {}, [0, 1]),
+    (1237, 100, {}, _equal_chunks(1237, 104, 12)),                                # 12 chunks of 104, the last 93
+    (1237, 1000000, {}, [0, 1237]),
+    (4096, 1024, {}, [0, 1216, 2432, 3456, 4096]),
+    (4096, 1024, dict(nlanes=2), [0, 1024, 2048, 3072, 4096]),
+    (4096, 1024, dict(taper=0), [0, 1024, 2048, 3072, 4096]),
+    (4095, 1024, {}, [0, 1024, 2048, 3072, 4095]),                                # below the taper's 4096
+    (4100, 1024, {}, [0, 1216, 2432, 3520, 4100]),
+    (4608, 1024, {}, _equal_chunks(4608, 922, 5)),                                # five chunks of 922, the last 920
+    (131072, None, {}, [0, 38272, 76544, 109312, 131072]),
+    (131072, None, dict(taper=0), _equal_chunks(131072, 32768, 4)),
+    (65536, None, {}, [0, 32768, 65536]),
+    (100000, 1, {}, _equal_chunks(100000, 6250, 16)),                             # the cap of 16 chunks
+    (5000, None, dict(large=1), [0, 5000]),                                       # fewer than 4 * 256 shots per further chunk
+    (200000, None, dict(per_shot_rows=1, n=4050), _equal_chunks(200000, 12500, 16)),
+]
+
+
+@pytest.mark.parametrize("B,chunk,over,want", _HOST_CHUNK_CASES)
+def test_host_chunk_plan(lib, monkeypatch, B, chunk, over, want):
+    """bposd_debug_host_chunks: the one chunk plan of the synchronous host-pointer calls, without a handle or a device."""
+    if chunk is None:
+        monkeypatch.delenv("BPOSD_HOST_CHUNK", raising=False)
+    else:
+        monkeypatch.setenv("BPOSD_HOST_CHUNK", str(chunk))
+    a = dict(n=1922, per_shot_rows=0, nlanes=4, num_cu=256, large=0, taper=1)
+    a.update(over)
+    bounds = np.full(17, -1, np.int64)
+    count = lib.bposd_debug_host_chunks(B, a["n"], a["per_shot_rows"], a["nlanes"], a["num_cu"], a["large"], a["taper"], bounds.ctypes.data)
+    assert count == len(want) - 1, (count, bounds)
+    assert bounds[:count + 1].tolist() == want and (bounds[count + 1:] == -1).all()  # count + 1 bounds and nothing behind them
+
+
+def test_host_chunk_plan_rejects_bad_arguments(lib):
+    bounds = np.zeros(17, np.int64)
+    assert lib.bposd_debug_host_chunks(0, 10, 0, 4, 256, 0, 1, bounds.ctypes.data) == _lib.BPOSD_ERR_INVALID
+    assert lib.bposd_debug_host_chunks(10, 10, 0, 4, 256, 0, 1, None) == _lib.BPOSD_ERR_INVALID
+    assert b"bposd_debug_host_chunks" in lib.bposd_last_error(None)
