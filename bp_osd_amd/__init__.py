@@ -9,8 +9,8 @@ when the HIP library or a device is missing (there is no CPU fallback).
 """
 from .decoder import BpOsdDecoder, bposd_decoder  # noqa: F401
 from . import codes  # noqa: F401
-from .dem import (dem_decode_sim, dem_failure_spectrum, fault_subsets, importance_table, phenomenological_dem,  # noqa: F401
-                  phenomenological_detector_times, subset_table, weight_distribution)
+from .dem import (dem_decode_sim, dem_failure_spectrum, fault_subsets, fit_sample_priors, importance_table,  # noqa: F401
+                  phenomenological_dem, phenomenological_detector_times, subset_table, weight_distribution, weight_multipliers)
 from .window import WindowedDemDecoder, window_plan, windowed_dem_decode_sim  # noqa: F401
 
 __version__ = "0.1.0"

@@ -2,7 +2,7 @@
 model's validation, the run loop over batches, the counters and rates of a run, and the native engine's plumbing (creating a
 ``bposd_dem``, fetching an item of the last batch, device bytes and kernel times), and the harvest of failing shots: its host
 restatement (``harvest_batch``), which is the definition the device kernels are held against, and what a run accumulates
-from it.  A harness keeps its constructor, its two ``_run_batch_*`` and what is its own in ``last_batch`` and
+from it; next to it the restatement of the per-fault sums over selected shots (``fault_sums_batch``).  A harness keeps its constructor, its two ``_run_batch_*`` and what is its own in ``last_batch`` and
 ``output_dict``."""
 from __future__ import annotations
 
@@ -59,6 +59,42 @@ def harvest_batch(faults, correction, select, max_rows):
         i = int(np.argmin(weight))  # the first of the least: rows ascend, so the lowest row
         out.update(min_weight=int(weight[i]), min_row=int(rows[i]), min_residual=_pack(r[i:i + 1])[0])
     return out
+
+
+def fault_sums_batch(fault_words, rows, multipliers=None, N=None):
+    """The per-fault sums over selected shots of one batch on the host -- the definition the device kernel
+    (fault_sums_kernel) is held against bit for bit.
+
+    ``fault_words`` are the packed fault rows of a batch, uint64 [B, ceil(N/64)] with padding bits zero (item "faults"),
+    ``rows`` an ascending int32 list of F selected rows and ``multipliers`` None or uint32 [F], aligned with ``rows``.
+    Returns ``(counts, sums)``, uint64 [N] each (``N`` not given: all 64 ceil(N/64) columns of the words): ``counts[i]`` = the number of
+    selected rows in which fault i fired and ``sums[i]`` = the sum of their multipliers (None without multipliers).  All of
+    it is integer: no sum can reach 2^63 with multipliers below 2^32 and fewer than 2^31 rows, and every split of the row
+    list adds up to the same arrays."""
+    words = np.ascontiguousarray(fault_words, dtype="<u8")
+    if words.ndim != 2:
+        raise ValueError("fault_words must be packed rows [B, ceil(N/64)]")
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    if rows.size and (rows[0] < 0 or rows[-1] >= words.shape[0] or (np.diff(rows) <= 0).any()):
+        raise ValueError(f"rows must ascend strictly inside [0, {words.shape[0]})")
+    mult = None
+    if multipliers is not None:
+        mult = np.asarray(multipliers)
+        if mult.shape != rows.shape or (mult.size and (not np.issubdtype(mult.dtype, np.integer) or mult.min() < 0 or mult.max() >= 2 ** 32)):
+            raise ValueError(f"multipliers must be {rows.size} integers in [0, 2^32), one per selected row")
+        mult = mult.astype(np.uint64)
+    cols = 64 * words.shape[1]
+    N = cols if N is None else int(N)
+    if not cols - 64 < N <= cols and not (cols == 0 and N == 0):
+        raise ValueError(f"rows of {words.shape[1]} words do not hold N = {N} faults")
+    counts, sums = np.zeros(cols, np.uint64), None if mult is None else np.zeros(cols, np.uint64)
+    for lo in range(0, rows.size, 4096):  # (unpacked a slab at a time)
+        sel = rows[lo:lo + 4096]
+        bits = np.unpackbits(np.ascontiguousarray(words[sel]).view(np.uint8), axis=1, bitorder="little")
+        counts += bits.sum(axis=0, dtype=np.uint64)
+        if mult is not None:
+            sums += (bits.astype(np.uint64) * mult[lo:lo + 4096, None]).sum(axis=0, dtype=np.uint64)
+    return counts[:N].copy(), None if sums is None else sums[:N].copy()
 
 
 def checked_model(H, L, priors):

@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "bposd_dem_set_subset",
     "bposd_dem_set_harvest",
     "bposd_dem_harvest_info",
+    "bposd_dem_fault_sums",
     "bposd_dem_sample",
     "bposd_dem_run",
     "bposd_dem_fetch",
@@ -104,6 +105,8 @@ DEBUG_SYMBOLS = (
     "bposd_debug_dem_timing",
     "bposd_debug_dem_harvest",
     "bposd_debug_dem_harvest_timing",
+    "bposd_debug_dem_fault_sums",
+    "bposd_debug_dem_fault_sums_timing",
     "bposd_debug_window_step",
     "bposd_debug_window_timing",
     "bposd_debug_class_layout",
@@ -201,6 +204,9 @@ DEM_ITEMS = {"faults": (0, "<u8", "N"), "detectors": (1, "<u8", "M"), "observabl
              "fail_rows": (11, "<i4", "F"), "fail_weight": (12, "<i4", "F"), "fail_residual": (13, "<u8", "FN"),
              "fail_faults": (14, "<u8", "FN"), "min_residual": (15, "<u8", "1N")}
 
+
+# bposd_dem_fault_sums(select)
+DEM_SELECT = {"all": 0, "failing": 1}
 
 # bposd_dem_set_subset(mode)
 DEM_SUBSET = {None: 0, "enumerate": 1, "random": 2}
@@ -359,6 +365,12 @@ def load():
     lib.bposd_debug_dem_harvest.restype = C.c_int
     lib.bposd_debug_dem_harvest_timing.argtypes = [vp, C.POINTER(C.c_double)]
     lib.bposd_debug_dem_harvest_timing.restype = C.c_int
+    lib.bposd_dem_fault_sums.argtypes = [vp, C.c_int32, vp, C.c_int64, vp, vp]
+    lib.bposd_dem_fault_sums.restype = C.c_int
+    lib.bposd_debug_dem_fault_sums.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp]
+    lib.bposd_debug_dem_fault_sums.restype = C.c_int
+    lib.bposd_debug_dem_fault_sums_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.bposd_debug_dem_fault_sums_timing.restype = C.c_int
     lib.bposd_window_set_harvest.argtypes = [vp, C.c_int64]
     lib.bposd_window_set_harvest.restype = C.c_int
     lib.bposd_window_harvest_info.argtypes = [vp, C.POINTER(C.c_int64)]

@@ -34,6 +34,7 @@ struct bposd_dem : EngineBase {
     DevArray<long long> d_logw;
     CounterBlock counters;  // 5 counters; with the harvest on, ints 5 .. 7 hold its triple
     Harvest hv;             // bposd_dem_set_harvest (harvest.h)
+    FaultSums fs;           // bposd_dem_fault_sums (harvest.h): nothing until the first call
 };
 
 namespace bposd_host {

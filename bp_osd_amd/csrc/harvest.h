@@ -1,6 +1,7 @@
 // harvest.h -- the host side of the failing-shot harvest (harvest_kernels.hip.h) that the detector-error-model engine and
 // the sliding-window engine share: its state in an engine, switching it, and the three launches behind a scorer.  The
-// kernels are instantiated in launch_harvest.hip and nowhere else.
+// kernels are instantiated in launch_harvest.hip and nowhere else.  Behind it: the per-fault sums over the rows a harvest
+// listed, or over all rows of a batch (fault_sums_kernel.hip.h, instantiated in launch_fault_sums.hip and nowhere else).
 //
 // Off (max_rows == 0, the default) it is nothing: no launch, no allocation, and the counters' download stays as short as it
 // was.  On, an engine's batch gains three launches on the engine's stream between its scorer and the counters' download, so
@@ -63,5 +64,46 @@ void harvest_read(Harvest& hv, const int* h_counters);
 // The five fetch items of a harvest in the order of the headers' enums (FAIL_ROWS, FAIL_WEIGHT, FAIL_RESIDUAL, FAIL_FAULTS,
 // MIN_RESIDUAL), with the row counts of the last batch.
 void harvest_items(const Harvest& hv, int fw, FetchItem out[5]);
+
+// harvest_list_kernel alone on the engine's stream: the rows whose flag byte passes the job's test go to hv.d_list in
+// ascending order and their count to the harvest's device state (harvest_count).  Nothing of the job but B and the flags is
+// read; the items of a harvest are not formed, so hv.last_on stays false.
+int harvest_list_enqueue(EngineBase* e, Harvest& hv, const HarvestJob& job);
+// where the device keeps the number of rows the last harvest_list_kernel listed
+const int* harvest_count(const Harvest& hv);
+
+}  // namespace bposd_host
+
+// Per-fault sums over selected rows of a batch.  One device block, made by the first call that needs it:
+// counts [N] and sums [N] (64-bit words), then the multipliers [capacity] (32-bit).
+struct FaultSums {
+    DevBuf block;
+    unsigned long long *d_counts = nullptr, *d_sums = nullptr;
+    uint32_t* d_mult = nullptr;
+    Event ev_t[2];       // around the last launch (bposd_debug_dem_fault_sums_timing)
+    bool timed = false;  // ... if there was one
+};
+
+// What one launch reads: `rows` selected rows of the fault rows [.][fw] -- the rows list[0 .. rows), whose number the device
+// also holds in *count (the harvest's list and count), or, list == NULL, the rows 0 .. rows - 1.  The multipliers, if any,
+// are in fs.d_mult.
+struct FaultSumsJob {
+    long long rows;
+    int N, fw;
+    const unsigned long long* faults;
+    const int* list;
+    const int* count;
+    bool weighted;
+};
+
+namespace bposd_host {
+
+inline size_t fault_sums_bytes(long long capacity, int N) { return 16 * (size_t)N + 4 * (size_t)capacity; }
+
+// The block and the events, once; counted in the engine's device_bytes.  A failure leaves the engine as it was.
+int fault_sums_ensure(EngineBase* e, FaultSums& fs, int N);
+// Clears counts (and sums) and launches the kernel behind it on the engine's stream, between fs.ev_t[0] and fs.ev_t[1];
+// with no row selected the arrays are cleared and nothing is launched.  Nothing waits.
+int fault_sums_enqueue(EngineBase* e, FaultSums& fs, const FaultSumsJob& job);
 
 }  // namespace bposd_host

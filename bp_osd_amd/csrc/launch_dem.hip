@@ -1,6 +1,7 @@
 // launch_dem.hip -- the detector-error-model Monte-Carlo engine of libbposd_mi355x.so: bposd_dem_* of include/bposd_mi355x.h.
 // One translation unit: both instances of dem_sample_kernel and dem_score_kernel (dem_kernels.hip.h) and dem_subset_kernel
-// (dem_subset_kernel.hip.h) are instantiated here and nowhere else.
+// (dem_subset_kernel.hip.h) are instantiated here and nowhere else.  The harvest's kernels and fault_sums_kernel have units
+// of their own (harvest.h).
 //
 // A batch is sample faults -> detectors and true observables -> one decode straight to observables -> compare -> five
 // integers.  The engine owns every buffer of it and a stream of its own; the decode goes through the decoder's
@@ -137,6 +138,27 @@ int enqueue_sample(bposd_dem* dem, uint64_t first_shot, long long B) {
     ENGINE_TRY(dem, hipEventRecord(dem->ev_t[1], dem->stream));
     if (dem->weighted) dem->logw_B = B;
     return 0;
+}
+
+// bposd_dem_fault_sums and its debug twin behind their checks: the multipliers go up, the kernel runs on the rows the job
+// names, the host waits and the arrays come down -- 4 n_mult bytes up, 8 N or 16 N down.
+int fault_sums_run(bposd_dem* dem, FaultSumsJob job, const uint32_t* mult, uint64_t* counts, uint64_t* sums) {
+    int rc;
+    if ((rc = bposd_host::fault_sums_ensure(dem, dem->fs, dem->N))) return rc;
+    hipStream_t st = dem->stream;
+    job.N = dem->N;
+    job.fw = dem->fw;
+    job.faults = dem->d_faults;
+    job.weighted = mult != nullptr;
+    if (mult && job.rows) ENGINE_TRY(dem, hipMemcpyAsync(dem->fs.d_mult, mult, sizeof(uint32_t) * (size_t)job.rows, hipMemcpyHostToDevice, st));
+    if ((rc = bposd_host::fault_sums_enqueue(dem, dem->fs, job))) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    ENGINE_TRY(dem, hipMemcpyAsync(counts, dem->fs.d_counts, 8 * (size_t)dem->N, hipMemcpyDeviceToHost, st));
+    if (sums) ENGINE_TRY(dem, hipMemcpyAsync(sums, dem->fs.d_sums, 8 * (size_t)dem->N, hipMemcpyDeviceToHost, st));
+    ENGINE_TRY(dem, hipStreamSynchronize(st));
+    return BPOSD_OK;
 }
 
 }  // namespace
@@ -440,6 +462,32 @@ int bposd_dem_fetch(bposd_dem* dem, int32_t what, void* host_dst, size_t bytes) 
                         host_dst, bytes);
 }
 
+int bposd_dem_fault_sums(bposd_dem* dem, int32_t select, const uint32_t* mult, int64_t n_mult, uint64_t* counts, uint64_t* sums) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    // everything is validated before anything is allocated or queued: a refusal leaves the engine as it was
+    if (select != BPOSD_DEM_SELECT_ALL && select != BPOSD_DEM_SELECT_FAILING)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "select = %d is not BPOSD_DEM_SELECT_ALL or BPOSD_DEM_SELECT_FAILING", select);
+    if (dem->sampled_B == 0) return engine_fail(dem, BPOSD_ERR_INVALID, "no batch has run yet");
+    if (select == BPOSD_DEM_SELECT_FAILING && !dem->hv.last_on)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "BPOSD_DEM_SELECT_FAILING needs a batch that ran with the harvest on (bposd_dem_set_harvest)");
+    if (!counts) return engine_fail(dem, BPOSD_ERR_INVALID, "counts is NULL");
+    if ((mult == nullptr) != (sums == nullptr))
+        return engine_fail(dem, BPOSD_ERR_INVALID, "mult and sums go together: give both, or NULL for both to count only");
+    const long long rows = select == BPOSD_DEM_SELECT_ALL ? dem->sampled_B : (long long)dem->hv.info[0];
+    if (mult && n_mult != rows)
+        return engine_fail(dem, BPOSD_ERR_INVALID, "n_mult = %lld, but the last batch has %lld %s", (long long)n_mult, rows,
+                           select == BPOSD_DEM_SELECT_ALL ? "shots" : "failing shots");
+    DeviceGuard guard(dem->device);
+    ENGINE_TRY(dem, guard.err);
+    FaultSumsJob job{};
+    job.rows = rows;
+    if (select == BPOSD_DEM_SELECT_FAILING) {  // the list harvest_list_kernel left, and its count: nothing is listed again
+        job.list = dem->hv.d_list;
+        job.count = bposd_host::harvest_count(dem->hv);
+    }
+    return fault_sums_run(dem, job, mult, counts, sums);
+}
+
 int64_t bposd_dem_device_bytes(bposd_dem* dem) { return dem ? (int64_t)dem->device_bytes : BPOSD_ERR_INVALID; }
 
 int bposd_debug_dem_timing(bposd_dem* dem, double* sample_ms, double* score_ms) {
@@ -509,6 +557,54 @@ int bposd_debug_dem_harvest_timing(bposd_dem* dem, double* harvest_ms) {
     float ms = 0.f;
     ENGINE_TRY(dem, hipEventElapsedTime(&ms, dem->hv.ev_t[0], dem->hv.ev_t[1]));
     *harvest_ms = ms;
+    return BPOSD_OK;
+}
+
+int bposd_debug_dem_fault_sums(bposd_dem* dem, const uint64_t* fault_words, const uint8_t* select_bytes, const uint32_t* mult, int64_t B,
+                               uint64_t* counts, uint64_t* sums) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (!fault_words || !counts) return engine_fail(dem, BPOSD_ERR_INVALID, "fault rows and counts are required");
+    if ((mult == nullptr) != (sums == nullptr))
+        return engine_fail(dem, BPOSD_ERR_INVALID, "mult and sums go together: give both, or NULL for both to count only");
+    if (select_bytes && !dem->hv.on()) return engine_fail(dem, BPOSD_ERR_INVALID, "select bytes need the harvest's list: the harvest is off (bposd_dem_set_harvest)");
+    if (const int rc = engine_check_batch(dem, B)) return rc;
+    DeviceGuard guard(dem->device);
+    ENGINE_TRY(dem, guard.err);
+    dem->sampled_B = dem->scored_B = dem->logw_B = 0;
+    dem->hv.last_on = false;
+    const size_t rows = (size_t)B;
+    FaultSumsJob job{};
+    job.rows = B;
+    ENGINE_TRY(dem, hipStreamSynchronize(dem->stream));
+    ENGINE_TRY(dem, hipMemcpy(dem->d_faults, fault_words, 8 * rows * dem->fw, hipMemcpyHostToDevice));
+    if (select_bytes) {
+        std::vector<uint8_t> flags(rows);
+        long long listed = 0;
+        for (size_t b = 0; b < rows; ++b) listed += (flags[b] = select_bytes[b] ? 4 : 0) != 0;  // what dem_score_kernel leaves for an osdw failure
+        ENGINE_TRY(dem, hipMemcpy(dem->d_flags, flags.data(), rows, hipMemcpyHostToDevice));
+        const HarvestJob list{B, dem->N, dem->fw, 4, 4, dem->d_flags, dem->d_faults, nullptr, true};
+        if (const int rc = bposd_host::harvest_list_enqueue(dem, dem->hv, list)) {
+            (void)hipStreamSynchronize(dem->stream);
+            return rc;
+        }
+        job.rows = listed;
+        job.list = dem->hv.d_list;
+        job.count = bposd_host::harvest_count(dem->hv);
+    }
+    if (const int rc = fault_sums_run(dem, job, mult, counts, sums)) return rc;
+    dem->sampled_B = B;  // item 0 holds this call's rows; nothing was decoded (scored_B stays 0, as after bposd_debug_dem_harvest)
+    return BPOSD_OK;
+}
+
+int bposd_debug_dem_fault_sums_timing(bposd_dem* dem, double* sums_ms) {
+    if (!dem) return BPOSD_ERR_INVALID;
+    if (!sums_ms) return engine_fail(dem, BPOSD_ERR_INVALID, "sums_ms is NULL");
+    if (!dem->fs.timed) return engine_fail(dem, BPOSD_ERR_INVALID, "no fault_sums_kernel has run since the engine's last batch selected a row");
+    DeviceGuard guard(dem->device);
+    ENGINE_TRY(dem, guard.err);
+    float ms = 0.f;
+    ENGINE_TRY(dem, hipEventElapsedTime(&ms, dem->fs.ev_t[0], dem->fs.ev_t[1]));
+    *sums_ms = ms;
     return BPOSD_OK;
 }
 

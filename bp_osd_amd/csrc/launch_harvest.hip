@@ -71,6 +71,22 @@ int bposd_host::harvest_enqueue(EngineBase* e, Harvest& hv, const HarvestJob& jo
     return 0;
 }
 
+int bposd_host::harvest_list_enqueue(EngineBase* e, Harvest& hv, const HarvestJob& job) {
+    HarvestParams P{};
+    P.B = job.B;
+    P.flag_mask = job.flag_mask;
+    P.flag_want = job.flag_want;
+    P.flags = job.flags;
+    P.state = (HarvestState*)hv.d_state;
+    P.list = hv.d_list;
+    hv.last_on = false;
+    hipLaunchKernelGGL(harvest_list_kernel, dim3(1), dim3(LIST_THREADS), 0, e->stream, P);
+    ENGINE_TRY(e, hipGetLastError());
+    return 0;
+}
+
+const int* bposd_host::harvest_count(const Harvest& hv) { return &((const HarvestState*)hv.d_state)->count; }
+
 void bposd_host::harvest_read(Harvest& hv, const int* h_counters) {
     for (int i = 0; i < 3; ++i) hv.info[i] = h_counters[HARVEST_TRIPLE_AT + i];
     hv.last_rows = std::min<long long>(hv.info[0], hv.max_rows);

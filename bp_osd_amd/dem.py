@@ -22,6 +22,10 @@ exactly ``w`` mechanisms: every set of the stratum in turn, or uniformly drawn o
 ``dem_failure_spectrum`` runs the strata of weight 0, 1, ... and returns the weight up to which the decoder corrects every
 fault set, and a logical error rate with a rigorous interval.
 
+Per-fault sums over selected shots (``fault_sums`` / ``fault_stats``) reduce the fault rows of a batch to one
+count and one weighted sum per mechanism where the rows are.  ``fit_sample_priors`` builds the cross-entropy fit of a
+sampling row on them: a ``sample_priors`` that tilts only the faults that matter, found by the engine itself.
+
 ``phenomenological_dem`` builds ``(H, L, priors)`` of the repeated-measurement model of a code, so that the engine can be
 used with no circuit simulator at hand; INTEGRATION.md says how the three come out of a detector-error-model file.
 """
@@ -33,11 +37,11 @@ import math
 import numpy as np
 import scipy.sparse as sp
 
-from ._dem_base import HARVEST_ITEMS, DemSimBase, _gf2_csr, _pack, checked_model, create_dem, harvest_batch
+from ._dem_base import HARVEST_ITEMS, DemSimBase, _gf2_csr, _pack, checked_model, create_dem, fault_sums_batch, harvest_batch
 from .sim import _default_decoder_factory, _mod2_mul, philox4x32_10, philox_uniforms
 
-__all__ = ["dem_decode_sim", "dem_failure_spectrum", "fault_subsets", "importance_table", "phenomenological_dem",
-           "phenomenological_detector_times", "subset_table", "weight_distribution"]
+__all__ = ["dem_decode_sim", "dem_failure_spectrum", "fault_subsets", "fit_sample_priors", "importance_table", "phenomenological_dem",
+           "phenomenological_detector_times", "subset_table", "weight_distribution", "weight_multipliers"]
 
 def phenomenological_dem(h, l, rounds, p_data, p_meas):
     """``(H, L, priors)`` of the phenomenological noise model of a code with checks ``h`` (m x n) and logicals ``l`` (k x n)
@@ -113,6 +117,26 @@ def importance_table(priors, sample_priors):
             raise ValueError(f"the increments up to fault {i} sum to 2^62 or more: a shot's log-weight could overflow")
         c_terms.append(lb)
     return incr, math.fsum(c_terms)
+
+
+MULTIPLIER_ONE = 2 ** 31 - 1  # the multiplier of the heaviest shot
+
+
+def weight_multipliers(logw_fail):
+    """uint32 [F]: the likelihood ratios of shots with integer log-weights ``logw_fail`` (int64, units of 2^-32, as
+    ``last_batch("logw")`` has them) relative to the heaviest of them, as the integers the per-fault sums multiply by:
+    ``rint(exp((lw - max lw) / 2**32) * (2**31 - 1))``.  The heaviest shot gets 2^31 - 1, a shot lighter than e^-22 of it 0.
+    The one place that turns log-weights into multipliers: both engines sum the same integers."""
+    lw = np.ascontiguousarray(logw_fail, dtype=np.int64).reshape(-1)
+    if lw.size == 0:
+        return np.zeros(0, np.uint32)
+    rel = (lw - lw.max()).astype(np.float64) / LOGW_ONE  # (the difference is exact in int64: |lw| < 2^62)
+    return np.rint(np.exp(rel) * MULTIPLIER_ONE).astype(np.uint32)
+
+
+def _scaled_priors(p, beta):
+    """sample_scale's row: p_i where p_i >= 0.5, else min(beta p_i, 0.5)."""
+    return np.where(p >= 0.5, p, np.minimum(float(beta) * p, 0.5))
 
 
 SUBSET_MODES = ("enumerate", "random")
@@ -253,6 +277,10 @@ class dem_decode_sim(DemSimBase):
         failing shots of the run in shot order, a dict of "shot" (uint64), "weight" (int32), "residual" and "faults" (packed
         rows) and, with importance sampling, "logw" (int64).  engine="native" compacts the failing rows on the device: no batch-sized array
         crosses to the host for it
+    fault_stats : True (needs ``harvest >= 1``) accumulates over the run ``fault_counts`` (int64 [N]: how often every fault
+        fired) and ``failure_fault_counts`` (int64 [N]: how often it fired in a shot whose osdw observables are wrong) -- which
+        mechanisms the failures are made of.  Both are unweighted counts of the shots as sampled and do not depend on the
+        batch size; :meth:`output_dict` does not list them.  See :meth:`fault_sums`
 
     Results: ``run_count``, ``bp_converge_count``, ``bp_success_count`` (converged and observables right),
     ``osd0_success_count``, ``osdw_success_count``, ``trivial_count`` (no detector fired), ``*_logical_error_rate`` with
@@ -279,7 +307,8 @@ class dem_decode_sim(DemSimBase):
     _RATES = ("bp", "osd0", "osdw")
 
     def __init__(self, H, L, priors, batch_size=4096, engine="native", seed=0, target_runs=None, decoder_factory=None, run_sim=True,
-                 sample_priors=None, sample_scale=None, harvest=0, fault_weight=None, subset=None, support=None, **decoder_kwargs):
+                 sample_priors=None, sample_scale=None, harvest=0, fault_weight=None, subset=None, support=None, fault_stats=False,
+                 **decoder_kwargs):
         self._check_engine(engine, decoder_factory, "decoder")
         self._H, self._L, self._priors = checked_model(H, L, priors)
         self.M, self.N = self._H.shape
@@ -291,6 +320,9 @@ class dem_decode_sim(DemSimBase):
         if subset is not None and (sample_priors is not None or sample_scale is not None):
             raise ValueError("fault sets of a fixed weight exclude sample_priors / sample_scale")
         self._init_harvest(harvest, with_logw=sample_priors is not None or sample_scale is not None or subset is not None)
+        self.fault_stats = bool(fault_stats)
+        if self.fault_stats and not self.harvest:
+            raise ValueError("fault_stats=True needs harvest >= 1: the failing shots are the ones the harvest lists")
         p = self._priors
         self._subset = self.fault_weight = None
         self._shot0 = 0  # global shot of the run's first
@@ -311,7 +343,7 @@ class dem_decode_sim(DemSimBase):
             self.sample_scale = float(sample_scale)
             if not 1.0 <= self.sample_scale < math.inf:
                 raise ValueError(f"sample_scale must be a finite number >= 1, not {sample_scale}")
-            sample_priors = np.where(p >= 0.5, p, np.minimum(self.sample_scale * p, 0.5))
+            sample_priors = _scaled_priors(p, self.sample_scale)
         self._tilted = sample_priors is not None
         if self._tilted:
             q = np.ascontiguousarray(sample_priors, dtype=np.float64)
@@ -319,9 +351,9 @@ class dem_decode_sim(DemSimBase):
                 raise ValueError(f"sample_priors must have length {self.N}, not {q.shape}")
             self._incr, self._c0 = importance_table(p, q)
             self._sample_priors = q
-            self._wsum = dict.fromkeys(("w", "w2", "bp", "bp2", "osd0", "osd02", "osdw", "osdw2"), 0.0)
-            self.weight_mean = self.effective_sample_fraction = 0.0
+            self._reset_weighted_sums()
         self._init_run(batch_size, seed, target_runs)
+        self._reset_fault_stats()
         if self._subset:
             self._reset_stratum_sums()
         self._dem = None
@@ -376,6 +408,8 @@ class dem_decode_sim(DemSimBase):
         if self.harvest:
             info = self._native_harvest_triple(self._dem, "bposd_dem_harvest_info", _lib.check_dem)
             self._accumulate_harvest(first, info, ask, logw)
+        if self.fault_stats:
+            self._accumulate_fault_stats()
 
     def device_bytes(self):
         """engine="native": bytes of device memory the engine holds for its batches (the decoder's workspaces are its own)."""
@@ -436,6 +470,8 @@ class dem_decode_sim(DemSimBase):
             h = harvest_batch(faults, rows["osdw"], wrong["osdw"], ask)
             self._last.update({item: h[item] for item in HARVEST_ITEMS})
             self._accumulate_harvest(first, (h["fail_count"], h["min_weight"], h["min_row"]), ask, self._last.get("logw"))
+        if self.fault_stats:
+            self._accumulate_fault_stats()
 
     # ------------------------------------------------------------------ common
     def _accumulate_weighted(self, flags, converged, logw):
@@ -457,6 +493,99 @@ class dem_decode_sim(DemSimBase):
             setattr(self, f"{key}_logical_error_rate_eb", math.sqrt(max(S[key + "2"] / n - rate * rate, 0.0) / n))
         self.weight_mean = S["w"] / n
         self.effective_sample_fraction = S["w"] * S["w"] / (n * S["w2"])
+
+    def _reset_weighted_sums(self):
+        self._wsum = dict.fromkeys(("w", "w2", "bp", "bp2", "osd0", "osd02", "osdw", "osdw2"), 0.0)
+        self.weight_mean = self.effective_sample_fraction = 0.0
+
+    def set_sampling(self, sample_priors, nominal=None, target_runs=None, first_shot=0):
+        """Another sampling row on the same model, decoder and engine -- the tilted sibling of :meth:`set_fault_weight`: the
+        faults are drawn against ``sample_priors`` = q from now on and every shot is weighed by its likelihood ratio under
+        ``nominal`` (default ``priors``; a harsher nominal row is a level of :func:`fit_sample_priors`), through
+        ``importance_table(nominal, q)``.  The decoder keeps ``priors`` as its channel.  The run starts over at global shot
+        ``first_shot`` with its counters, weighted sums, harvest and fault statistics reset (``target_runs`` None: as many
+        shots as before); :meth:`run_decode_sim` runs it.  Refused on a sim of fault sets of a fixed weight."""
+        if self._subset:
+            raise ValueError("set_sampling excludes fault sets of a fixed weight (fault_weight and subset)")
+        first_shot = int(first_shot)
+        if first_shot < 0:
+            raise ValueError("first_shot must be >= 0")
+        q = np.array(sample_priors, dtype=np.float64)
+        if q.shape != (self.N,):
+            raise ValueError(f"sample_priors must have length {self.N}, not {q.shape}")
+        nom = self._priors if nominal is None else np.ascontiguousarray(nominal, dtype=np.float64)
+        if nom.shape != (self.N,):
+            raise ValueError(f"nominal must have length {self.N}, not {nom.shape}")
+        incr, c0 = importance_table(nom, q)  # (everything is validated before anything changes)
+        if self._dem is not None:
+            from . import _lib
+
+            _lib.check_dem(self._lib, self._dem, self._lib.bposd_dem_set_sampling(self._dem, q.ctypes.data, incr.ctypes.data))
+        self._tilted, self.sample_scale = True, None
+        self._sample_priors, self._incr, self._c0 = q, incr, c0
+        self._shot0 = first_shot
+        self._reset_weighted_sums()
+        self._init_harvest(self.harvest, with_logw=True)
+        self._init_run(self._batch_size, self.seed, self.target_runs if target_runs is None else target_runs)
+        self._reset_fault_stats()
+
+    # ------------------------------------------------------------------ per-fault sums over selected shots
+    def fault_sums(self, select="failing", multipliers=None):
+        """``(counts, sums)`` of the last batch, uint64 [N] each: in how many of the selected shots every fault fired, and
+        the sum of those shots' ``multipliers`` (None without multipliers).  ``select="failing"``: the shots whose osdw
+        observables are wrong, as the harvest lists them (needs ``harvest=K > 0``); ``multipliers`` is uint32 [F], aligned
+        with ``last_batch("fail_rows")``.  ``select="all"``: every shot, ``multipliers`` [B].  engine="native" forms the
+        sums where the rows are (fault_sums_kernel): N numbers come down in place of the rows; engine="numpy" applies the
+        definition (``_dem_base.fault_sums_batch``) to ``last_batch("faults")``.  Bit-exact on both."""
+        from . import _lib
+
+        if select not in _lib.DEM_SELECT:
+            raise ValueError(f"select must be one of {sorted(_lib.DEM_SELECT)}, not {select!r}")
+        if select == "failing" and not self.harvest:
+            raise ValueError("fault_sums('failing') needs harvest=K > 0")
+        mult = None
+        if multipliers is not None:
+            mult = np.asarray(multipliers)
+            if mult.ndim != 1 or (mult.size and (not np.issubdtype(mult.dtype, np.integer) or mult.min() < 0 or mult.max() >= 2 ** 32)):
+                raise ValueError("multipliers must be a vector of integers in [0, 2^32)")
+            mult = np.ascontiguousarray(mult, dtype=np.uint32)
+        if self._engine == "numpy":
+            words = self.last_batch("faults")
+            rows = self.last_batch("fail_rows") if select == "failing" else np.arange(words.shape[0], dtype=np.int32)
+            if mult is not None and mult.size != rows.size:
+                raise ValueError(f"{mult.size} multipliers, but the last batch has {rows.size} {'failing ' if select == 'failing' else ''}shots")
+            return fault_sums_batch(words, rows, mult, self.N)
+        if not self._last_B:
+            raise RuntimeError("fault_sums needs a batch that has run")
+        counts = np.zeros(self.N, np.uint64)
+        sums = None if mult is None else np.zeros(self.N, np.uint64)
+        rc = self._lib.bposd_dem_fault_sums(self._dem, _lib.DEM_SELECT[select], None if mult is None else mult.ctypes.data,
+                                            0 if mult is None else mult.size, counts.ctypes.data, None if sums is None else sums.ctypes.data)
+        _lib.check_dem(self._lib, self._dem, rc)
+        return counts, sums
+
+    def fault_sums_ms(self):
+        """engine="native": duration of the last fault_sums_kernel launch in ms (HIP events)."""
+        import ctypes as C
+
+        from . import _lib
+
+        if self._dem is None:
+            raise RuntimeError("fault_sums_ms needs engine='native'")
+        ms = C.c_double()
+        _lib.check_dem(self._lib, self._dem, self._lib.bposd_debug_dem_fault_sums_timing(self._dem, C.byref(ms)))
+        return ms.value
+
+    def _reset_fault_stats(self):
+        """``fault_stats=True``: how often every fault fired in the run, and how often in a failing shot (None while off)."""
+        self.fault_counts = self.failure_fault_counts = None
+        if self.fault_stats:
+            self.fault_counts = np.zeros(self.N, np.int64)
+            self.failure_fault_counts = np.zeros(self.N, np.int64)
+
+    def _accumulate_fault_stats(self):
+        self.fault_counts += self.fault_sums("all")[0].astype(np.int64)
+        self.failure_fault_counts += self.fault_sums("failing")[0].astype(np.int64)
 
     # ------------------------------------------------------------------ fault sets of a fixed weight
     def _init_stratum(self, fault_weight, subset, target_runs):
@@ -505,6 +634,7 @@ class dem_decode_sim(DemSimBase):
         self._init_harvest(self.harvest, with_logw=True)
         self._init_run(self._batch_size, self.seed, target_runs)
         self._reset_stratum_sums()
+        self._reset_fault_stats()
         if self._dem is not None:
             self._native_set_subset()
 
@@ -611,3 +741,78 @@ def dem_failure_spectrum(H, L, priors, max_weight, shots_per_weight, batch_size=
             "logical_error_rate_lower_eb": math.sqrt(math.fsum(r["osdw_failure_mass_eb"] ** 2 for r in strata)),
             "tail_mass": float(_weight_dp(sim._priors, max_weight, sim._support)[1]), "corrected_weight": corrected,
             "min_failing_weight": first_fail}
+
+
+def fit_sample_priors(H, L, priors, levels=(8.0, 1.0, 1.0), shots_per_level=4096, batch_size=4096, engine="native", seed=0, smoothing=1.0,
+                      min_failures=32, **decoder_kwargs):
+    """``(q, report)``: a ``sample_priors`` row for :class:`dem_decode_sim` fitted by the cross-entropy method -- the row
+    that tilts the faults that matter and leaves the others alone, which no uniform ``sample_scale`` can do.
+
+    Among product-of-Bernoulli rows the one closest (in cross-entropy) to the ideal sampler "the model's faults, given that
+    the decoder fails" sets every fault's probability to its likelihood-weighted frequency among the failing shots,
+    ``sum_fail w f_i / sum_fail w``.  Failures have to be common for that to be measurable, so the nominal noise walks down:
+    with ``scaled(beta)_i = p_i`` where ``p_i >= 0.5``, else ``min(beta p_i, 0.5)``, the fit starts at
+    ``q = scaled(levels[0])``, and level t samples ``shots_per_level`` shots from the current q under the nominal row
+    ``scaled(levels[t])`` (``set_sampling(q, nominal=...)``, from global shot ``t << 40`` on, as the strata of
+    :func:`dem_failure_spectrum`), decodes with ``priors`` and updates
+
+        q_i <- clip((1 - smoothing) q_i + smoothing S_i / S, p_i, 0.5)   where 0 < p_i < 0.5;    q_i = p_i elsewhere
+
+    so that every row on the way is a legal ``sample_priors`` that never samples a fault more rarely than the model does.
+    ``S_i`` and ``S`` are summed per batch from integers: with lw the log-weights of the batch's failing shots,
+    ``v = weight_multipliers(lw)`` and ``(_, sums) = fault_sums("failing", v)`` -- on engine="native" the device's column
+    sums, N numbers per batch in place of the failing rows -- ``S_i += sums_i e^(max lw / 2^32)`` and
+    ``S += sum(v) e^(max lw / 2^32)`` in float64, in batch order: both engines return the same array, bit for bit, for the
+    same ``batch_size``.  The last level must be 1: the row is fitted for the true priors.
+
+    A level with fewer than ``min_failures`` failing shots is a ValueError that names it.  ``report`` is a list with one dict
+    per level: ``level``, ``scale``, ``shots``, ``failures``, ``effective_sample_fraction``, ``weight_mean`` and
+    ``sample_priors`` (the row fitted at that level).  ``decoder_kwargs`` go to :class:`dem_decode_sim` (the decoder's
+    options, and ``decoder_factory`` with engine="numpy")."""
+    levels = [float(b) for b in levels]
+    if not levels or not all(1.0 <= b < math.inf for b in levels):
+        raise ValueError("levels must be a non-empty sequence of finite scales >= 1")
+    if levels[-1] != 1.0:
+        raise ValueError(f"the last level must be 1 (the row is fitted for the true priors), not {levels[-1]:g}")
+    shots = int(shots_per_level)
+    if shots < 1:
+        raise ValueError("shots_per_level must be >= 1")
+    smoothing = float(smoothing)
+    if not 0.0 < smoothing <= 1.0:
+        raise ValueError(f"smoothing must be in (0, 1], not {smoothing}")
+    min_failures = int(min_failures)
+    if min_failures < 1:
+        raise ValueError("min_failures must be >= 1")
+    for key in ("sample_priors", "sample_scale", "fault_weight", "subset", "support", "harvest", "fault_stats", "target_runs", "run_sim"):
+        if key in decoder_kwargs:
+            raise ValueError(f"fit_sample_priors sets {key} itself")
+    p = checked_model(H, L, priors)[2]
+    free = (p > 0.0) & (p < 0.5)
+    q = _scaled_priors(p, levels[0])
+    sim = dem_decode_sim(H, L, p, batch_size=batch_size, engine=engine, seed=seed, target_runs=shots, run_sim=False, sample_priors=q, harvest=1,
+                         **decoder_kwargs)
+    run_batch = sim._run_batch_native if engine == "native" else sim._run_batch_numpy
+    report = []
+    for t, beta in enumerate(levels):
+        sim.set_sampling(q, nominal=_scaled_priors(p, beta), target_runs=shots, first_shot=t << 40)
+        S_i, S, failures = np.zeros(sim.N, np.float64), 0.0, 0
+        while sim.run_count < shots:
+            run_batch(min(sim._batch_size, shots - sim.run_count))
+            rows = sim.last_batch("fail_rows")
+            if not rows.size:
+                continue
+            lw = sim.last_batch("logw")[rows]
+            v = weight_multipliers(lw)
+            _, sums = sim.fault_sums("failing", v)
+            top = math.exp(int(lw.max()) / LOGW_ONE)
+            S_i += sums.astype(np.float64) * top
+            S += float(int(v.sum(dtype=np.uint64))) * top
+            failures += int(rows.size)
+        if failures < min_failures:
+            raise ValueError(f"level {t} (scale {beta:g}) saw {failures} failing shots in {shots}, fewer than min_failures = {min_failures}: "
+                             "start from a larger first scale, or give every level more shots")
+        q = np.where(free, np.clip((1.0 - smoothing) * q + smoothing * (S_i / S), p, 0.5), p)
+        report.append({"level": t, "scale": beta, "shots": shots, "failures": failures,
+                       "effective_sample_fraction": float(sim.effective_sample_fraction), "weight_mean": float(sim.weight_mean),
+                       "sample_priors": q.copy()})
+    return q, report

@@ -588,6 +588,35 @@ int bposd_dem_run(bposd_dem *dem, uint64_t first_shot, int64_t B, int64_t counte
 int bposd_dem_set_harvest(bposd_dem *dem, int64_t max_rows);
 int bposd_dem_harvest_info(bposd_dem *dem, int64_t out[3]);
 
+/*
+ * Per-fault sums over selected shots of the last batch -- a reduced fetch: with f_b the fault row of shot b (item
+ * BPOSD_DEM_FAULTS), b_0 < b_1 < ... the selected rows and mult[s] a 32-bit multiplier of the s-th of them,
+ *     counts[i] = sum_s f_{b_s}[i]        sums[i] = sum_s mult[s] f_{b_s}[i]        i = 0 .. N - 1
+ * as 64-bit integers (no sum can reach 2^63: mult < 2^32 and fewer than 2^31 rows).  With the likelihood ratios of the
+ * failing shots as multipliers (bp_osd_amd.dem.weight_multipliers) sums[i] / sum_s mult[s] is the cross-entropy update of
+ * fault i's sampling probability (bp_osd_amd.dem.fit_sample_priors); counts alone say which mechanisms the failures are
+ * made of.  The rows stay on the device: 4 n_mult bytes go up and 8 N (mult == NULL) or 16 N come down, where fetching the
+ * rows would move 8 ceil(N/64) bytes per shot.
+ *   BPOSD_DEM_SELECT_ALL: every shot of the last batch, after bposd_dem_run or bposd_dem_sample; mult is [B].
+ *   BPOSD_DEM_SELECT_FAILING: the failing shots the harvest listed in the last batch (BPOSD_DEM_FAIL_ROWS), read where the
+ *     harvest left the list; mult is [F], aligned with that item.  Needs a batch that ran with the harvest on.
+ * One kernel (csrc/fault_sums_kernel.hip.h) on the engine's stream; the call waits.  Integer adds only: the result does not
+ * depend on the order of arrival, and the host restatement (bp_osd_amd._dem_base.fault_sums_batch) gives the same bits.  A
+ * row with multiplier 0 still counts in counts.  mult and sums go together (both, or NULL for both: counts only); n_mult is
+ * ignored when mult is NULL.
+ *
+ * BPOSD_ERR_INVALID, with the engine left as it was: a select that is neither of the two, no batch yet, FAILING without a
+ * harvested batch, n_mult different from B (ALL) or F (FAILING), counts == NULL, one of mult and sums without the other.
+ * The first call that passes these checks allocates one block of  16 N + 4 capacity  bytes (the two arrays and the
+ * multipliers), counted in bposd_dem_device_bytes; an engine that never calls this launches, allocates and downloads what it
+ * did before.  bposd_dem_run is not involved.  (The sliding-window engine has no such call: its run knows nothing of
+ * weights.  The rows of its sampler are a sample-only bposd_dem's, on which BPOSD_DEM_SELECT_ALL works.)
+ */
+#define BPOSD_DEM_SELECT_ALL 0     /* every shot of the last batch; mult is [B]                                        */
+#define BPOSD_DEM_SELECT_FAILING 1 /* the harvest's failing rows of the last batch; mult is [F], aligned with FAIL_ROWS */
+int bposd_dem_fault_sums(bposd_dem *dem, int32_t select, const uint32_t *mult, int64_t n_mult, uint64_t *counts,
+                         uint64_t *sums);
+
 /* Copy one item (BPOSD_DEM_FAULTS ...) of the last batch to host memory; bytes must be that item's size for the last B
  * (for items 11 .. 14: for the last batch's number of failing shots -- 0 bytes is legal and copies nothing).
  * After bposd_dem_sample only items 0-2 are there.  BPOSD_DEM_OBS_FAIL came down with the counters: no device call.

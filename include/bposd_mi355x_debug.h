@@ -102,6 +102,20 @@ int bposd_debug_dem_harvest(bposd_dem *dem, const uint64_t *fault_words, const v
  * batch has been waited for).  Refused unless that batch ran with the harvest on. */
 int bposd_debug_dem_harvest_timing(bposd_dem *dem, double *harvest_ms);
 
+/* Diagnostics: fault_sums_kernel alone (bposd_dem_fault_sums of the public header), with no sampler, decoder or scorer
+ * involved.  Every pointer is a HOST pointer: fault_words [B][ceil(N/64)] (padding bits zero) go into the engine's fault
+ * rows.  select_bytes [B] (row b is selected when select_bytes[b] != 0) go through harvest_list_kernel first, so that the
+ * kernel reads the list and the count it reads in production (bposd_dem_set_harvest must be on); mult is then [F], one per
+ * selected row in ascending row order.  select_bytes == NULL selects every row the implicit way (BPOSD_DEM_SELECT_ALL);
+ * mult is then [B].  mult and sums go together, as there; counts [N] and sums [N].  1 <= B <= capacity.  Waits, and leaves
+ * item 0 of bposd_dem_fetch as a batch of B shots would (nothing else: the harvest's items are gone). */
+int bposd_debug_dem_fault_sums(bposd_dem *dem, const uint64_t *fault_words, const uint8_t *select_bytes,
+                               const uint32_t *mult, int64_t B, uint64_t *counts, uint64_t *sums);
+
+/* Diagnostics: duration of the last fault_sums_kernel launch (HIP events on the engine's stream; the call has waited).
+ * Refused when the last call selected no row, or there was none. */
+int bposd_debug_dem_fault_sums_timing(bposd_dem *dem, double *sums_ms);
+
 /* Diagnostics: one window_step_kernel launch on rows the caller supplies, with no decoder and no engine involved -- the
  * commit of one window from `decoded` and the gather of the next into `syndrome`.  Every pointer is a HOST pointer; rows
  * go up, the kernel runs on `device`, rows come back.  H, L as bposd_dem_tables takes them.  Commit entry c is position

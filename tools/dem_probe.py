@@ -25,7 +25,14 @@ last batch selected through ``bposd_debug_dem_harvest``, against a correction of
 
 ``--fault-weight W --subset MODE`` measures the fixed-weight sampler instead (profiles/dem_subset_rates.txt): two sample-only
 calls on the model, ``bposd_dem_sample`` with Bernoulli rows and with sets of weight W (``enumerate`` or ``random``),
-alternating over the rounds -- each sampler's HIP-event time -- and one whole ``bposd_dem_run`` batch of the stratum."""
+alternating over the rounds -- each sampler's HIP-event time -- and one whole ``bposd_dem_run`` batch of the stratum.
+
+``--fault-sums`` measures the per-fault sums over selected shots instead (profiles/dem_fault_sums_rates.txt): one engine with
+the harvest on, over the rounds in turn fault_sums_kernel by HIP events on the failing shots of a batch ("failing", weighted),
+on every shot ("all", weighted and counts only) and on a failure-rich batch (every shot listed through
+``bposd_debug_dem_fault_sums``), the whole ``bposd_dem_fault_sums`` call, and the path it replaces: ``bposd_dem_fetch`` of the
+fault rows plus ``np.unpackbits(...).sum(0)`` on the host.  Then a batch as a level of ``fit_sample_priors`` runs it next to a
+plain batch."""
 import argparse
 import os
 import sys
@@ -208,6 +215,93 @@ def harvest_probe(a, say):
         f"{B + 2 * 8 * fw * B:,} B read; batch time with such a batch: not measured (the decode of a batch that fails everywhere is another workload)")
 
 
+def fault_sums_probe(a, say):
+    """--fault-sums: fault_sums_kernel on the selections a batch offers, against fetching the rows."""
+    import ctypes as C
+
+    from bp_osd_amd import _lib, dem_decode_sim
+    from bp_osd_amd.dem import weight_multipliers
+
+    (H, L, priors), kw, what = model(a.model)
+    B, seed = a.batch, 5
+    N = H.shape[1]
+    fw = (N + 63) // 64
+    say(f"# tools/dem_probe.py --fault-sums on one MI355X: {what}; H {H.shape[0]} x {N}, k = {L.shape[0]}, B = {B}; {a.rounds} rounds, the forms in turn")
+    sim = dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=0, run_sim=False, harvest=1, sample_priors=priors.copy(), **kw)
+    lib = sim._lib
+    for _ in range(2):  # warm-up: workspaces, the kernels' first launch
+        sim._run_batch_native(B)
+    ones32, every = np.ones(B, np.uint32), np.ones(B, np.uint8)
+    forms = ("failing, weighted", "all, weighted", "all, counts", "rich, weighted", "fetch + unpackbits")
+    t = {f: dict(kernel=[], call=[]) for f in forms}
+    fails, bits_fail, bits_all = [], [], []
+    ms = C.c_double()
+    for _ in range(a.rounds):
+        sim._run_batch_native(B)
+        rows = sim.last_batch("fail_rows")
+        v = weight_multipliers(sim.last_batch("logw")[rows])
+        for form in forms[:3]:
+            sel, mult = ("failing", v) if form.startswith("failing") else ("all", ones32 if form.endswith("weighted") else None)
+            t0 = time.perf_counter()
+            counts, _ = sim.fault_sums(sel, mult)
+            t[form]["call"].append((time.perf_counter() - t0) * 1e3)
+            t[form]["kernel"].append(sim.fault_sums_ms())
+            (bits_fail if sel == "failing" else bits_all).append(int(counts.sum()))
+        fails.append(rows.size)
+        t0 = time.perf_counter()
+        words = sim.last_batch("faults")
+        t1 = time.perf_counter()
+        host = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little").sum(0)[:N]
+        t2 = time.perf_counter()
+        assert (host == counts.astype(np.int64)).all()
+        t["fetch + unpackbits"]["call"].append((t2 - t0) * 1e3)
+        t["fetch + unpackbits"]["kernel"].append((t1 - t0) * 1e3)  # (the fetch alone)
+        # a failure-rich batch: every shot of this one listed
+        c, s_ = np.zeros(N, np.uint64), np.zeros(N, np.uint64)
+        t0 = time.perf_counter()
+        _lib.check_dem(lib, sim._dem, lib.bposd_debug_dem_fault_sums(sim._dem, words.ctypes.data, every.ctypes.data, ones32.ctypes.data, B,
+                                                                      c.ctypes.data, s_.ctypes.data))
+        t["rich, weighted"]["call"].append((time.perf_counter() - t0) * 1e3)
+        _lib.check_dem(lib, sim._dem, lib.bposd_debug_dem_fault_sums_timing(sim._dem, C.byref(ms)))
+        t["rich, weighted"]["kernel"].append(ms.value)
+        assert (c == counts).all() and (s_ == counts).all()
+    fmt = lambda v: " / ".join(f"{x:.4f}" for x in v)
+    say(f"failing shots per batch: mean {np.mean(fails):.1f} (min {min(fails)}, max {max(fails)}); set bits walked: {np.mean(bits_fail):,.0f} in the failing rows, "
+        f"{np.mean(bits_all):,.0f} in all rows; bytes read: {8 * fw} B per selected row = {8 * fw * np.mean(fails):,.0f} B (failing), {8 * fw * B:,} B (all)")
+    for form in forms[:4]:
+        note = " (the call uploads the rows first: the kernel's time is the figure)" if form.startswith("rich") else ""
+        say(f"{form}: fault_sums_kernel, HIP events, ms per round: {fmt(t[form]['kernel'])}; the whole call, ms: {fmt(t[form]['call'])}{note}")
+    r = t["fetch + unpackbits"]
+    say(f"the path it replaces: bposd_dem_fetch(BPOSD_DEM_FAULTS) of {8 * fw * B:,} B, ms per round: {fmt(r['kernel'])}; with np.unpackbits(...).sum(0): {fmt(r['call'])}")
+    say(f"device {sim.device_bytes() / B:.1f} B per shot ({16 * N + 4 * B:,} B of it for the sums and the multipliers)")
+    # ---- a batch of a fit_sample_priors level next to a plain batch: what a level adds per batch is the fetch of the failing
+    # rows' numbers and of the log-weights, the multipliers and the sums
+    plain = dem_decode_sim(H, L, priors, batch_size=B, engine="native", seed=seed, target_runs=0, run_sim=False, **kw)
+    for _ in range(2):
+        plain._run_batch_native(B)
+    t_plain, t_level, t_extra = [], [], []
+    for _ in range(a.rounds):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            plain._run_batch_native(B)
+        t1 = time.perf_counter()
+        extra = 0.0
+        for _ in range(a.steps):
+            sim._run_batch_native(B)
+            t2 = time.perf_counter()
+            rows = sim.last_batch("fail_rows")
+            v = weight_multipliers(sim.last_batch("logw")[rows])
+            sim.fault_sums("failing", v)
+            extra += time.perf_counter() - t2
+        t3 = time.perf_counter()
+        t_plain.append((t1 - t0) / a.steps * 1e3)
+        t_level.append((t3 - t1) / a.steps * 1e3)
+        t_extra.append(extra / a.steps * 1e3)
+    fmt2 = lambda v: " / ".join(f"{x:.2f}" for x in v)
+    say(f"a plain batch as dem_decode_sim runs it, ms per batch and round: {fmt2(t_plain)}; a batch of a fit_sample_priors level (weighted sampling, harvest of 1 "
+        f"row, then fail_rows, logw, multipliers and the sums): {fmt2(t_level)}, of which the steps behind the batch: {fmt2(t_extra)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("h1922", "hgp400r3"), default="h1922")
@@ -219,16 +313,18 @@ def main():
     ap.add_argument("--sample-scale", type=float, default=None, help="measure the weighted sampler against the plain one at this sample_scale")
     ap.add_argument("--harvest", type=int, default=None, help="measure the harvest of failing shots (this many rows kept) against a plain engine")
     ap.add_argument("--fault-weight", type=int, default=None, help="measure the fixed-weight sampler (sets of this weight) against the Bernoulli one")
+    ap.add_argument("--fault-sums", action="store_true", help="measure the per-fault sums over selected shots against fetching the rows")
     ap.add_argument("--subset", choices=("enumerate", "random"), default="random", help="with --fault-weight: every set in turn, or drawn uniformly")
     a = ap.parse_args()
-    if a.sample_scale is not None or a.harvest is not None or a.fault_weight is not None:
+    if a.sample_scale is not None or a.harvest is not None or a.fault_weight is not None or a.fault_sums:
         lines = []
 
         def say(s):
             print(s, flush=True)
             lines.append(s)
 
-        (weighted_probe if a.sample_scale is not None else harvest_probe if a.harvest is not None else subset_probe)(a, say)
+        (fault_sums_probe if a.fault_sums else weighted_probe if a.sample_scale is not None else harvest_probe if a.harvest is not None
+         else subset_probe)(a, say)
         if a.out:
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n\n")
