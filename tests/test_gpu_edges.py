@@ -19,6 +19,7 @@ import pytest
 import scipy.sparse as sp
 
 from tests.edge_codes import EDGES, edge_pcm, kprime, order_of, pcm_for
+from tests.gpu_contract import check_outside_column_space
 from tests.test_gpu_parity import _compare_exact, _gpu_decode
 
 pytestmark = pytest.mark.gpu
@@ -90,18 +91,9 @@ def test_instance_edge_vs_oracle(gpu_ready, case):
     assert (~got["converged"]).mean() > 0.5, "the elimination hardly ran"
     ref = o.decode_batch(syn)
     _compare_exact(_rows(got, slice(0, c)), _rows(ref, slice(0, c)))
-    # outside the column space: BP exact, OSD by the contract (module docstring)
-    bad = ((np.asarray(sp.csr_matrix(H, dtype=np.int32) @ got["osd0"][c:].T.astype(np.int32)) % 2).T != syn[c:]).any(axis=1)
+    # outside the column space: BP exact, OSD by the contract (module docstring; tests/gpu_contract.py)
+    bad = check_outside_column_space(H, o, syn, got, ref, c)
     assert bad.sum() >= len(syn) - c - (len(syn) - c) // 2, "too few syndromes outside the column space"
-    for k in ("converged", "iters", "bp"):
-        assert (np.asarray(got[k][c:]) == np.asarray(ref[k][c:]).astype(got[k].dtype)).all(), k
-    assert (got["llr"][c:].view(np.uint64) == ref["llr"][c:].view(np.uint64)).all(), "LLR bits differ"
-    assert not got["converged"][c:][bad].any()
-    for b in range(c, len(syn)):
-        x0 = got["osd0"][b]
-        r = o.osd((np.asarray(H @ x0.astype(np.int64)) % 2).astype(np.uint8), got["llr"][b])
-        assert (r["osd0"] == x0).all(), ("osd0 is no OSD-0 solution of the checks it satisfies", b)
-        assert (r["osdw"] == got["osdw"][b]).all(), ("osdw is not the oracle's search from osd0", b)
     again = _gpu_decode(g, syn)
     for k in ("osdw", "osd0", "bp", "converged", "iters"):
         assert (again[k] == got[k]).all(), f"{k} differs between two decodes of the same batch"
