@@ -5,7 +5,8 @@ and leaves on its own when it is zero; the same test runs once more after the la
 one iteration early or late, a wave that disagrees with the others, a bitmap that carries a bit over from the syndrome the
 workgroup decoded before.  So this file decodes syndromes whose iteration counts the oracle has fixed beforehand.
 
-The plan of a matrix (``plan``; CPU only, asserted by ``test_oracle_alone_produces_every_case`` without a GPU):
+The plan of a matrix (``plan``: tests/bp_exit_cases.py ``plan_for``, shared with the other BP families' test
+tests/test_gpu_bp_exits.py; CPU only, asserted by ``test_oracle_alone_produces_every_case`` without a GPU):
 - a pool of syndromes: the all-zero one (iters = 0), H e for one error of weight 1 (min-sum flips that bit in the first
   iteration: iters = 1), and H e for 30 random errors of the row's rate q;
 - the *target*: the pool row the oracle converges in the fewest iterations k >= 3 at max_iter 30;
@@ -33,13 +34,9 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from tests.bp_exit_cases import CASES, N_POOL, _occurred, batch_index, plan_for
 from tests.local_codes import LOCAL_CODES, decoder_settings, matrix_of, row_by_id, syndrome_seed
 from tests.test_gpu_local_bodies import FORMS, OUTPUTS, _decode, _expected_local
-
-N_POOL = 32
-CASES = ("zero syndrome: iters 0", "one iteration, max_iter > 1", "one iteration, max_iter 1: converged in the last",
-         "converged inside the loop", "converged in the last iteration", "missed by one", "missed at max_iter 1",
-         "ordinary converged next to a missed one")
 
 
 def _row_1024():
@@ -53,62 +50,14 @@ B_TWO_CHECKS = 40000 + 3  # just above the small-call threshold (launch_bp_local
 GPU_CASES = [(rid, "small") for rid in ROW_IDS] + [(rid, "large") for rid in ROW_IDS if row_by_id(rid)["MP"] == 1024]
 
 
-def _occurred(res, target, k, max_iter):
-    """The CASES a result (oracle's or kernel's, pool order) with this max_iter shows."""
-    conv, it = np.asarray(res["converged"]).astype(bool), np.asarray(res["iters"])
-    seen = set()
-    if conv[0] and it[0] == 0:
-        seen.add(CASES[0])
-    if conv[1] and it[1] == 1:
-        seen.add(CASES[1] if max_iter > 1 else CASES[2])
-    t = (bool(conv[target]), int(it[target]))
-    if max_iter == k + 1 and t == (True, k):
-        seen.add(CASES[3])
-        others = np.arange(len(it)) != target
-        if (conv[2:] & (it[2:] >= 2) & others[2:]).any() and (~conv[2:] & (it[2:] == max_iter)).any():
-            seen.add(CASES[7])
-    if max_iter == k and t == (True, k):
-        seen.add(CASES[4])
-    if max_iter == k - 1 and t == (False, k - 1):
-        seen.add(CASES[5])
-    if max_iter == 1 and t == (False, 1):
-        seen.add(CASES[6])
-    return seen
-
-
 @functools.lru_cache(maxsize=None)
 def plan(row_id):
-    """dict(H, q, pool, target, k, max_iters, refs {max_iter: the oracle's result for the pool}); see the module docstring."""
-    from oracle import OracleDecoder
-
+    """The plan of a LOCAL_CODES row (tests/bp_exit_cases.py plan_for): dict(H, q, pool, target, k, max_iters, refs
+    {max_iter: the oracle's result for the pool}); see the module docstring."""
     row = row_by_id(row_id)
-    H = matrix_of(row)
-    m, n = H.shape
-    rng = np.random.default_rng(syndrome_seed(row))
-    err = (rng.random((N_POOL, n)) < row["q"]).astype(np.int32)
-    err[0] = 0
-    err[1] = 0
-    err[1, int(rng.integers(n))] = 1
-    pool = np.ascontiguousarray((np.asarray(H.astype(np.int32) @ err.T) % 2).T.astype(np.uint8))
-    ref30 = OracleDecoder(H, **decoder_settings(row["q"], 30)).decode_batch(pool)
-    ok = [i for i in range(2, N_POOL) if ref30["converged"][i] and ref30["iters"][i] >= 3]
-    assert ok, (row_id, "no pool syndrome converges in 3 .. 30 iterations", ref30["iters"])
-    target = min(ok, key=lambda i: ref30["iters"][i])
-    k = int(ref30["iters"][target])
-    max_iters = (k + 1, k, k - 1, 1)
-    refs = {mi: OracleDecoder(H, **decoder_settings(row["q"], mi)).decode_batch(pool) for mi in max_iters}
-    seen = set().union(*[_occurred(refs[mi], target, k, mi) for mi in max_iters])
-    assert seen == set(CASES), (row_id, "the oracle does not produce", sorted(set(CASES) - seen))
-    return dict(H=H, q=row["q"], pool=pool, target=target, k=k, max_iters=max_iters, refs=refs)
-
-
-def batch_index(B, target):
-    """Pool row of every batch row: the pool in order, over and over, with the target, the zero syndrome and the
-    one-iteration syndrome at both ends."""
-    idx = np.arange(B) % N_POOL
-    idx[:3] = (target, 0, 1)
-    idx[-3:] = (1, 0, target)
-    return idx
+    kw = decoder_settings(row["q"], 0)
+    del kw["max_iter"]
+    return plan_for(matrix_of(row), kw, row["q"], syndrome_seed(row), what=(row_id,))
 
 
 @pytest.mark.parametrize("row_id", ROW_IDS)
