@@ -11,6 +11,7 @@ from .decoder import BpOsdDecoder, bposd_decoder  # noqa: F401
 from . import codes  # noqa: F401
 from .dem import (dem_decode_sim, dem_failure_spectrum, fault_subsets, fit_sample_priors, importance_table,  # noqa: F401
                   phenomenological_dem, phenomenological_detector_times, subset_table, weight_distribution, weight_multipliers)
+from .circuit import Circuit, check_annotations, circuit_dem, css_memory_circuit, dem_text, fault_columns  # noqa: F401
 from .window import WindowedDemDecoder, window_plan, windowed_dem_decode_sim  # noqa: F401
 
 __version__ = "0.1.0"

@@ -88,6 +88,12 @@ EXPORTED_SYMBOLS = (
     "bposd_window_device_bytes",
     "bposd_window_last_error",
     "bposd_window_destroy",
+    "bposd_frame_create",
+    "bposd_frame_columns",
+    "bposd_frame_fetch",
+    "bposd_frame_device_bytes",
+    "bposd_frame_last_error",
+    "bposd_frame_destroy",
     "bposd_last_error",
     "bposd_destroy",
 )
@@ -109,6 +115,7 @@ DEBUG_SYMBOLS = (
     "bposd_debug_dem_fault_sums_timing",
     "bposd_debug_window_step",
     "bposd_debug_window_timing",
+    "bposd_debug_frame_timing",
     "bposd_debug_class_layout",
     "bposd_debug_last_instance",
     "bposd_debug_portable_math",
@@ -153,6 +160,15 @@ class BposdWindowConfig(C.Structure):
     _fields_ = [
         ("device", C.c_int32),
         ("capacity", C.c_int64),
+    ]
+
+
+class BposdFrameConfig(C.Structure):
+    _fields_ = [
+        ("device", C.c_int32),
+        ("layered", C.c_int32),
+        ("max_words", C.c_int64),
+        ("workspace_bytes", C.c_int64),
     ]
 
 
@@ -204,6 +220,9 @@ DEM_ITEMS = {"faults": (0, "<u8", "N"), "detectors": (1, "<u8", "M"), "observabl
              "fail_rows": (11, "<i4", "F"), "fail_weight": (12, "<i4", "F"), "fail_residual": (13, "<u8", "FN"),
              "fail_faults": (14, "<u8", "FN"), "min_residual": (15, "<u8", "1N")}
 
+
+# bposd_frame_config.layered
+FRAME_LAYERED = {None: 0, False: 1, True: 2}
 
 # bposd_dem_fault_sums(select)
 DEM_SELECT = {"all": 0, "failing": 1}
@@ -412,6 +431,21 @@ def load():
     lib.bposd_debug_window_step.restype = C.c_int
     lib.bposd_debug_window_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.bposd_debug_window_timing.restype = C.c_int
+    lib.bposd_frame_create.argtypes = [C.POINTER(BposdFrameConfig), vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int32,
+                                       C.POINTER(vp)]
+    lib.bposd_frame_create.restype = C.c_int
+    lib.bposd_frame_columns.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp]
+    lib.bposd_frame_columns.restype = C.c_int
+    lib.bposd_frame_fetch.argtypes = [vp, vp, vp, vp, vp]
+    lib.bposd_frame_fetch.restype = C.c_int
+    lib.bposd_frame_device_bytes.argtypes = [vp]
+    lib.bposd_frame_device_bytes.restype = C.c_int64
+    lib.bposd_frame_last_error.argtypes = [vp]
+    lib.bposd_frame_last_error.restype = C.c_char_p
+    lib.bposd_frame_destroy.argtypes = [vp]
+    lib.bposd_frame_destroy.restype = None
+    lib.bposd_debug_frame_timing.argtypes = [vp, vp, vp]
+    lib.bposd_debug_frame_timing.restype = C.c_int
     _lib = lib
     return lib
 
@@ -435,6 +469,11 @@ def check_dem(lib, dem, rc):
 def check_window(lib, win, rc):
     """check() for the sliding-window engine's calls (win None: a failed bposd_window_create / bposd_debug_window_step)."""
     _raise(lib.bposd_window_last_error, win, rc)
+
+
+def check_frame(lib, fr, rc):
+    """check() for the frame-propagation handle's calls (fr None: a failed bposd_frame_create)."""
+    _raise(lib.bposd_frame_last_error, fr, rc)
 
 
 def check_mc(lib, mc, rc):

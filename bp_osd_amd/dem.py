@@ -27,7 +27,8 @@ count and one weighted sum per mechanism where the rows are.  ``fit_sample_prior
 sampling row on them: a ``sample_priors`` that tilts only the faults that matter, found by the engine itself.
 
 ``phenomenological_dem`` builds ``(H, L, priors)`` of the repeated-measurement model of a code, so that the engine can be
-used with no circuit simulator at hand; INTEGRATION.md says how the three come out of a detector-error-model file.
+used with no circuit simulator at hand; ``bp_osd_amd.circuit`` derives the circuit-level model of a Clifford circuit with
+Pauli noise (``circuit_dem``), and INTEGRATION.md says how the three come out of a detector-error-model file.
 """
 from __future__ import annotations
 

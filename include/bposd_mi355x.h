@@ -750,6 +750,94 @@ const char *bposd_window_last_error(bposd_window *win);
 
 void bposd_window_destroy(bposd_window *win);
 
+/* =====================================================================================================================
+ * Circuit-level noise: the columns of a detector error model from a Clifford circuit (csrc/launch_frame.hip, DESIGN.md
+ * 4.17; bp_osd_amd/circuit.py holds the circuit description, the host restatement and the reduction to a model).  (No
+ * counterpart in the reference.)
+ *
+ * A circuit is T ops on Q qubits, int32 ops[T][3] = (opcode, a, b); b is read by the two-qubit ops only.  Measurements are
+ * numbered in order of appearance.  A fault is a Pauli on one or two qubits in front of op `pos` (pos = T: behind the last
+ * op); a Pauli is two bits, bit 0 its X part and bit 1 its Z part (X = 1, Z = 2, Y = 3).  Each fault is propagated on its
+ * own as a Pauli frame, one (x, z) bit pair per qubit, all zero at the start:
+ *     H    swap x, z                          S    z ^= x
+ *     CX   x[b] ^= x[a];  z[a] ^= z[b]        CZ   z[a] ^= x[b];  z[b] ^= x[a]
+ *     R, RX   clear both bits                 M / MX   record the flip x[a] / z[a], frame unchanged
+ *     MR, MRX record the flip as M / MX, then clear
+ * A detector (an observable) is a set of measurements, and its value for a frame the XOR of their flips.  Column i of H
+ * (M x F) stacked on L (k x F) is that pair of rows for the frame holding fault i alone.
+ *
+ * frame_propagate_kernel (csrc/frame_kernels.hip.h) packs 64 faults to a uint64 word, one thread per word; the frames and
+ * rows of a chunk of faults live in HBM, word index innermost.  frame_count_kernel and frame_fill_kernel turn the rows into
+ * columns (count, prefix sum, fill: deterministic).  Everything is integer and exact.
+ */
+typedef struct bposd_frame bposd_frame;
+
+enum {
+    BPOSD_FRAME_OP_R = 0,   /* reset to |0>            */
+    BPOSD_FRAME_OP_RX = 1,  /* reset to |+>            */
+    BPOSD_FRAME_OP_M = 2,   /* measure Z               */
+    BPOSD_FRAME_OP_MX = 3,  /* measure X               */
+    BPOSD_FRAME_OP_MR = 4,  /* measure Z, reset to |0> */
+    BPOSD_FRAME_OP_MRX = 5, /* measure X, reset to |+> */
+    BPOSD_FRAME_OP_H = 6,
+    BPOSD_FRAME_OP_S = 7,
+    BPOSD_FRAME_OP_CX = 8, /* a control, b target */
+    BPOSD_FRAME_OP_CZ = 9
+};
+
+enum { BPOSD_FRAME_DEFAULT = 0, BPOSD_FRAME_OP_BY_OP = 1, BPOSD_FRAME_GROUPS = 2 };
+
+typedef struct {
+    int32_t device;          /* HIP device ordinal                                                                  */
+    int32_t layered;         /* BPOSD_FRAME_GROUPS (the default): up to 4 ops on disjoint qubits per memory round   */
+                             /* trip (frame_propagate_layered_kernel); BPOSD_FRAME_OP_BY_OP: one op at a time       */
+    int64_t max_words;       /* most words (of 64 faults) in a chunk; 0: whatever workspace_bytes admits            */
+    int64_t workspace_bytes; /* byte budget of a chunk's frames, rows, counts and offsets; 0: 1 GiB                 */
+} bposd_frame_config;
+
+/*
+ * The annotations arrive inverted: CSR over the n_meas measurements, row i of md_* the detectors (ascending, < M) and of
+ * mo_* the observables (ascending, < k) that hold measurement i.  M = 0 or k = 0 is legal.  BPOSD_ERR_INVALID, with the op
+ * named (bposd_frame_last_error(NULL)), for an unknown opcode, a qubit outside [0, Q), a == b on a two-qubit op, an n_meas
+ * that is not the number of measurements of the op table (an annotation names a measurement out of range), or a table that
+ * is not such a CSR.  Everything is copied.
+ *
+ * Device memory (bposd_frame_device_bytes; every block at least 256 bytes): the tables 4 (3 T + T + 1 + 2 (n_meas + 1) +
+ * entries of both CSRs), and from the first bposd_frame_columns on, with wc = min(ceil(F/64), words of a chunk):
+ *     13 F                      the faults (pos, qa, qb, Pauli byte);  4 T  the groups of BPOSD_FRAME_GROUPS
+ *     8 wc (2 Q + M + k)        frames x, z and rows D, O of a chunk
+ *     2 * 2 * 4 * 64 wc         counts and offsets per fault of a chunk, for H and for L
+ *     4 * entries               the indices of the chunk with the most column entries
+ * The per-call blocks grow and never shrink.
+ */
+int bposd_frame_create(const bposd_frame_config *cfg, const int32_t *ops, int32_t T, int32_t Q, int32_t n_meas,
+                       const int32_t *md_indptr, const int32_t *md_indices, const int32_t *mo_indptr,
+                       const int32_t *mo_indices, int32_t M, int32_t k, bposd_frame **out);
+
+/*
+ * Propagate F faults (host pointers): pos[F] in 0 .. T and ascending, qa[F], qb[F] (-1: a one-qubit fault; qb == NULL:
+ * all of them are), pauli[F] = pa | pb << 2.  The fault index is the position in these arrays.  BPOSD_ERR_INVALID, with the
+ * fault named, for pos outside 0 .. T, faults not sorted by pos, a qubit out of range, qa == qb, Pauli code 0 on qa, and
+ * Pauli code 0 on a qb that is not -1 (or a code on qb = -1); nothing is launched then.  The faults are cut into chunks of
+ * whole words; the last word is ragged, and its padding bits belong to no fault and give no entry.  Synchronous.
+ * counts_out (may be NULL) receives the entries of H and of L over the F columns, which is what bposd_frame_fetch needs room
+ * for.  Every call starts from zero frames.
+ */
+int bposd_frame_columns(bposd_frame *fr, const int32_t *pos, const int32_t *qa, const int32_t *qb, const uint8_t *pauli,
+                        int64_t F, int64_t counts_out[2]);
+
+/* The columns of the last bposd_frame_columns as CSC over the faults: h_indptr / l_indptr [F + 1], h_indices / l_indices
+ * the detectors / observables of every column in ascending order. */
+int bposd_frame_fetch(bposd_frame *fr, int64_t *h_indptr, int32_t *h_indices, int64_t *l_indptr, int32_t *l_indices);
+
+/* Device memory the handle holds: the sum documented at bposd_frame_create. */
+int64_t bposd_frame_device_bytes(bposd_frame *fr);
+
+/* Message for the last error on this handle (fr == NULL: the last bposd_frame_create failure). */
+const char *bposd_frame_last_error(bposd_frame *fr);
+
+void bposd_frame_destroy(bposd_frame *fr);
+
 /* Message for the last error on this handle (h == NULL: last create() failure). */
 const char *bposd_last_error(bposd_handle *h);
 

@@ -151,6 +151,12 @@ int bposd_debug_window_step(bposd_window_step_args *args);
  * pointer may be NULL. */
 int bposd_debug_window_timing(bposd_window *win, double *step_ms, double *score_ms);
 
+/* Diagnostics: the durations of the last bposd_frame_columns call's frame_propagate_kernel, frame_count_kernel and
+ * frame_fill_kernel launches, each summed over the chunks (HIP events on the handle's stream; the call has waited), in
+ * ms[3]; info[2] = the chunks of that call, and the kernel launches of the handle so far (a refused call adds none).
+ * Either pointer may be NULL; ms is refused before the first successful call. */
+int bposd_debug_frame_timing(bposd_frame *fr, double ms[3], int64_t info[2]);
+
 /* Diagnostics, host only: the tables bp_class_kernel would run with for a pcm whose check and bit degrees fall inside one
  * compiled instance -- (check degrees; bit degrees) = (7; 3..4), (6; 3), (4; 2), (8; 4), (3..4; 1..2) -- and
  * BPOSD_ERR_UNSUPPORTED otherwise.  info[11]: highest check degree, lowest / highest bit degree, bit slots per thread, LDS
