@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "bposd_info",
     "bposd_posterior_llr",
     "bposd_set_bp_variant",
+    "bposd_set_relay",
+    "bposd_relay_stats",
     "bposd_set_osd_variant",
     "bposd_last_osd_kernel",
     "bposd_mc_create",
@@ -351,6 +353,10 @@ def load():
     lib.bposd_last_osd_kernel.restype = C.c_int
     lib.bposd_set_bp_variant.argtypes = [vp, C.c_int32]
     lib.bposd_set_bp_variant.restype = C.c_int
+    lib.bposd_set_relay.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32]
+    lib.bposd_set_relay.restype = C.c_int
+    lib.bposd_relay_stats.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64]
+    lib.bposd_relay_stats.restype = C.c_int
     lib.bposd_last_error.argtypes = [vp]
     lib.bposd_last_error.restype = C.c_char_p
     lib.bposd_destroy.argtypes = [vp]

@@ -270,7 +270,11 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
         if (two_back.done_recorded) HIP_TRY(h, hipStreamWaitEvent(L.stream, two_back.ev_done, 0));
     }
     if (!lean) HIP_TRY(h, hipEventRecord(R.ev[0], L.stream));
-    if (h->cfg.schedule == 1) {
+    L.relay_B = -1;  // (launch_bp_relay sets it)
+    if (h->relay_legs > 0) {
+        h->last_bp_kernel = BPOSD_BP_KERNEL_RELAY;
+        if ((rc = launch_bp_relay(h, call, P))) return rc;
+    } else if (h->cfg.schedule == 1) {
         h->last_bp_kernel = BPOSD_BP_KERNEL_SERIAL;
         if ((rc = launch_bp_serial(h, call, P))) return rc;
     } else if (h->bp_any || h->bp_variant == 64) {
@@ -696,6 +700,60 @@ int bposd_set_bp_variant(bposd_handle* h, int32_t variant) {
     if (variant >= 16 && variant <= 26 && !(h->local_ok && h->cfg.bp_method == BPOSD_BP_MIN_SUM))
         return fail(h, BPOSD_ERR_UNSUPPORTED, "the local-edge BP kernel needs a (3,6)-regular code with n = 2m and min-sum");
     h->bp_variant = variant;
+    return BPOSD_OK;
+}
+
+int bposd_set_relay(bposd_handle* h, int32_t legs, const double* gammas, const int32_t* leg_iters, int32_t stop_after, int32_t leg_init) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (legs == 0) {  // off: the tables stay where they are
+        h->relay_legs = 0;
+        return BPOSD_OK;
+    }
+    if (legs < 0) return fail(h, BPOSD_ERR_INVALID, "relay: legs = %d is negative", legs);
+    if (h->cfg.bp_method != BPOSD_BP_MIN_SUM) return fail(h, BPOSD_ERR_UNSUPPORTED, "relay mode needs min-sum (bp_method is product-sum)");
+    if (h->cfg.schedule != 0) return fail(h, BPOSD_ERR_UNSUPPORTED, "relay mode needs the flooding schedule (schedule is serial)");
+    if (!gammas || !leg_iters) return fail(h, BPOSD_ERR_INVALID, "relay: %s is NULL with legs = %d", !gammas ? "gammas" : "leg_iters", legs);
+    if (stop_after < 1) return fail(h, BPOSD_ERR_INVALID, "relay: stop_after = %d must be at least 1", stop_after);
+    if (leg_init != 0 && leg_init != 1) return fail(h, BPOSD_ERR_INVALID, "relay: leg_init = %d must be 0 (reset the messages) or 1 (keep them)", leg_init);
+    for (int r = 0; r < legs; ++r)
+        if (leg_iters[r] < 1) return fail(h, BPOSD_ERR_INVALID, "relay: leg_iters[%d] = %d must be at least 1", r, leg_iters[r]);
+    const size_t count = (size_t)legs * h->n;
+    for (size_t k = 0; k < count; ++k)
+        if (!std::isfinite(gammas[k]))
+            return fail(h, BPOSD_ERR_INVALID, "relay: gammas[%d][%d] = %g is not finite", (int)(k / h->n), (int)(k % h->n), gammas[k]);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls may still read the old tables
+    if (!h->d_cp) {  // the CSC edge map the kernel walks (a handle of the tuned kernels has none yet)
+        const int rct = build_tables_serial(h);
+        if (rct) return rct;
+    }
+    h->relay_legs = 0;  // (a failed upload leaves the mode off: the tables may be half written)
+    HIP_TRY(h, h->d_relay_gammas.ensure(sizeof(double) * count));
+    HIP_TRY(h, h->d_relay_iters.ensure(sizeof(int) * (size_t)legs));
+    HIP_TRY(h, hipMemcpy(h->d_relay_gammas, gammas, sizeof(double) * count, hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_relay_iters, leg_iters, sizeof(int) * (size_t)legs, hipMemcpyHostToDevice));
+    h->relay_legs = legs;
+    h->relay_stop = stop_after;
+    h->relay_init = leg_init;
+    return BPOSD_OK;
+}
+
+int bposd_relay_stats(bposd_handle* h, int32_t lane, int32_t* solutions, int32_t* best_leg, int64_t* weight, int64_t B) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (lane == -1) lane = h->relay_lane;
+    if (lane < 0 || lane >= h->nlanes) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range", lane);
+    Lane& L = h->lanes[lane];
+    if (L.relay_B < 0) return fail(h, BPOSD_ERR_INVALID, "the last call on lane %d did not run in relay mode", lane);
+    // no arrays: the batch size of that call (check_batch admits no batch above 2^31 - 1, so the value fits the return code)
+    if (!solutions && !best_leg && !weight) return (int)std::min<long long>(L.relay_B, INT_MAX);
+    if (B != L.relay_B) return fail(h, BPOSD_ERR_INVALID, "the last call on lane %d decoded %lld syndromes, not %lld", lane, L.relay_B, (long long)B);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    HIP_TRY(h, hipStreamSynchronize(L.stream));
+    if (solutions) HIP_TRY(h, hipMemcpy(solutions, L.relay_sol.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    if (best_leg) HIP_TRY(h, hipMemcpy(best_leg, L.relay_leg.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    if (weight) HIP_TRY(h, hipMemcpy(weight, L.relay_wt.p, sizeof(long long) * (size_t)B, hipMemcpyDeviceToHost));
     return BPOSD_OK;
 }
 

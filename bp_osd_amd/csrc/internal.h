@@ -67,6 +67,10 @@ struct Lane {
     PinnedBuf h_tail;                // one int, page-locked, device-visible: the BP kernel of this lane's current call has entered its tail
     // host-pointer observables calls (bposd_decode_batch_observables): the chunk's observable words, [chunk][ceil(k/64)] each
     DevBuf io_obsw, io_obs0, io_obsbp;
+    // relay mode (bposd_set_relay): per-shot solutions (int), best leg (int) and weight (int64) of the lane's last call,
+    // and that call's batch size; -1: the lane's last call did not run in relay mode (bposd_relay_stats)
+    DevBuf relay_sol, relay_leg, relay_wt;
+    long long relay_B = -1;
 };
 
 // What bposd_last_timing reports: one record per kernel pair launched by the last call (one per chunk for a
@@ -150,6 +154,11 @@ struct bposd_handle {
     // logical observables (bposd_set_observables): L transposed and packed, [ceil(n/64)][obs_k] words; obs_k = 0: none set
     DevArray<unsigned long long> d_obs_table;
     int obs_k = 0;
+    // relay mode (bposd_set_relay): relay_legs = 0 is off; gammas [legs][n], iterations per leg [legs]
+    int relay_legs = 0, relay_stop = 1, relay_init = 0;
+    int relay_lane = 0;  // lane of the last relay launch (bposd_relay_stats with lane = -1)
+    DevArray<double> d_relay_gammas;
+    DevArray<int> d_relay_iters;
 };
 
 // One BP + OSD launch pair: what it needs beyond the handle's per-code state.  The entry point that makes the call fills
@@ -224,6 +233,7 @@ bool class_preferred(const bposd_handle* h);
 int launch_bp_large(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);  // launch_bp_misc.hip   (bp_large_kernel)
 int launch_bp_serial(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P); //                      (bp_serial_kernel)
 int launch_bp_any(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);    //                      (bp_anydeg_kernel)
+int launch_bp_relay(bposd_handle* h, const DecodeCall& call, const bposd::BpParams& P);  // launch_bp_relay.hip  (bp_relay_kernel)
 int bp_serial_max_dv();
 size_t bp_large_lds_need(int m, int n);
 int launch_osd(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& P, long long B);  // launch_osd.hip (osd_kernel, osd_wave_kernel)

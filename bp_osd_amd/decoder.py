@@ -70,7 +70,7 @@ class BpOsdDecoder:
     def __init__(self, pcm, error_rate=None, error_channel=None, max_iter=0, bp_method="minimum_sum",
                  ms_scaling_factor=1.0, schedule="parallel", omp_thread_count=1, osd_method="osd_0",
                  osd_order=0, input_vector_type="syndrome", channel_probs=None, device=0,
-                 sort_tie_policy=0, weight_fn=0, ps_clip=0.0, osd_e_bit_order=0, ps_math_form=0, **kwargs):
+                 sort_tie_policy=0, weight_fn=0, ps_clip=0.0, osd_e_bit_order=0, ps_math_form=0, relay=None, **kwargs):
         if kwargs:
             raise TypeError(f"unexpected keyword arguments: {sorted(kwargs)}")
         sched = str(schedule).lower()
@@ -179,6 +179,48 @@ class BpOsdDecoder:
         self.batch_obs_osdw = None
         self.batch_obs_osd0 = None
         self.batch_obs_bp = None
+        self._relay = None
+        if relay is not None:
+            self.set_relay(relay)
+
+    # ------------------------------------------------------------------ relay mode
+    @property
+    def relay(self):
+        """The :class:`bp_osd_amd.RelayConfig` this decoder runs with, None when the mode is off."""
+        return self._relay
+
+    def set_relay(self, cfg):
+        """Switch relay mode on with a :class:`bp_osd_amd.RelayConfig` (min-sum, parallel schedule only), or off with None:
+        the BP stage of every later decode call of this decoder -- and of the engines built on it -- runs ``bp_relay_kernel``
+        (``bposd_set_relay``).  Off, the decoder launches what it launched before."""
+        from .relay import RelayConfig
+        if cfg is None:
+            _lib.check(self._lib, self._h, self._lib.bposd_set_relay(self._h, 0, None, None, 1, 0))
+            self._relay = None
+            return
+        if not isinstance(cfg, RelayConfig):
+            raise TypeError("relay must be a RelayConfig or None")
+        if cfg.n != self.n:
+            raise ValueError(f"the relay configuration is for {cfg.n} bits, this decoder has {self.n}")
+        g = np.ascontiguousarray(cfg.gammas, dtype=np.float64)
+        it = np.ascontiguousarray(cfg.leg_iters, dtype=np.int32)
+        _lib.check(self._lib, self._h, self._lib.bposd_set_relay(self._h, cfg.legs, g.ctypes.data, it.ctypes.data, cfg.stop_after, cfg.leg_init))
+        self._relay = cfg
+
+    def relay_stats(self, lane=None):
+        """dict(solutions int32 [B], best_leg int32 [B], weight int64 [B]) of the last call that ran on ``lane`` (default: the
+        lane of the last relay launch) in relay mode: solutions found per shot, the leg the kept one came from (-1: none) and its
+        integer weight (sum of the set bits' prior LLRs in units of 2^-32).  Waits for that lane.  A host-pointer call that
+        was cut into several chunks leaves each lane the words of its last chunk only: use the device-pointer calls, or
+        batches of one chunk, where every shot's words are wanted."""
+        lane = -1 if lane is None else int(lane)  # (-1: the lane of the last relay launch)
+        B = self._lib.bposd_relay_stats(self._h, lane, None, None, None, 0)  # (no arrays: that call's batch size)
+        if B < 0:
+            _lib.check(self._lib, self._h, B)
+        sol, leg, wt = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.int64)
+        if B:
+            _lib.check(self._lib, self._h, self._lib.bposd_relay_stats(self._h, lane, sol.ctypes.data, leg.ctypes.data, wt.ctypes.data, B))
+        return {"solutions": sol, "best_leg": leg, "weight": wt}
 
     # ------------------------------------------------------------------ lifetime
     def __del__(self):
@@ -774,7 +816,8 @@ class BpOsdDecoder:
         _lib.check(self._lib, self._h, self._lib.bposd_layout_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"natural": a.value, "chosen": b.value, "ideal": c.value}
 
-    BP_KERNEL_NAMES = {0: "bp_kernel", 1: "bp_local_kernel", 2: "bp_class_kernel", 3: "bp_large_kernel", 4: "bp_serial_kernel", 5: "bp_anydeg_kernel"}
+    BP_KERNEL_NAMES = {0: "bp_kernel", 1: "bp_local_kernel", 2: "bp_class_kernel", 3: "bp_large_kernel", 4: "bp_serial_kernel", 5: "bp_anydeg_kernel",
+                       6: "bp_relay_kernel"}
 
     def bp_kernel_info(self):
         """Which BP kernel the last decode call launched, with the bank-conflict model of its bit pass (modelled LDS
@@ -796,7 +839,7 @@ class BpOsdDecoder:
         return self.OSD_KERNEL_NAMES.get(self._lib.bposd_last_osd_kernel(self._h), "none")
 
     # template integers bposd_debug_last_instance reports per family (include/bposd_mi355x_debug.h)
-    _BP_INSTANCE_ARITY = {0: 4, 1: 4, 2: 4, 3: 3, 4: 0, 5: 0}
+    _BP_INSTANCE_ARITY = {0: 4, 1: 4, 2: 4, 3: 3, 4: 0, 5: 0, 6: 2}
     _OSD_INSTANCE_ARITY = {1: 1, 2: 2, 3: 1, 4: 4}
 
     def last_instance(self):

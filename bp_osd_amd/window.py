@@ -35,7 +35,7 @@ __all__ = ["window_plan", "WindowedDemDecoder", "windowed_dem_decode_sim"]
 _ITEMS = ("faults", "detectors", "observables", "obs_osdw", "correction", "residual", "flags", "converged", "iters", "obs_fail") + HARVEST_ITEMS
 
 
-def window_plan(H, detector_time, window, priors=None, check_rank=True):
+def window_plan(H, detector_time, window, priors=None, check_rank=True, fault_key=None):
     """The index lists of a windowed decode of ``H`` (M x N) with one time per detector and ``window = (W, C)``.
 
     Returns a namespace with ``M``, ``N``, ``T``, ``W``, ``C``, ``tau`` (int64 [N], -1 for a fault with an empty column) and
@@ -44,7 +44,9 @@ def window_plan(H, detector_time, window, priors=None, check_rank=True):
     ``unique`` lists the first window of every distinct (H_w, priors_w) -- without ``priors``, of every distinct H_w -- so a
     time-invariant model needs two or three decoders whatever its T.  ``step_words[s] = (w_lo, w_hi)`` for step s = 0 ..
     len(windows): the 64-bit words of the detector row that the columns committed from window s - 1 touch or the gather of
-    window s reads, which is all that window_step_kernel stages.
+    window s reads, which is all that window_step_kernel stages.  ``fault_key`` (an array with one row per fault, e.g. the
+    transposed memory strengths of a relay configuration over all N faults) joins H_w and priors_w in what makes two windows
+    distinct: windows share a decoder only where their rows of it agree too.
 
     ValueError (naming the window) for an empty D_w or F_w and, with ``check_rank``, for rank(H_w) < |D_w|."""
     from .codes import gf2_rank
@@ -76,6 +78,9 @@ def window_plan(H, detector_time, window, priors=None, check_rank=True):
     p = None if priors is None else np.ascontiguousarray(priors, dtype=np.float64)
     if p is not None and p.shape != (N,):
         raise ValueError(f"priors must have length {N}, not {p.shape}")
+    fk = None if fault_key is None else np.ascontiguousarray(fault_key)
+    if fk is not None and (fk.ndim < 1 or fk.shape[0] != N):
+        raise ValueError(f"fault_key must have one row per fault ({N}), not shape {fk.shape}")
 
     windows, unique, seen = [], [], {}
     w = 0
@@ -89,7 +94,8 @@ def window_plan(H, detector_time, window, priors=None, check_rank=True):
         commit = np.ones(fault.size, np.uint8) if last else (tau[fault] < lo + C).astype(np.uint8)
         Hw = H[det][:, fault].tocsr()
         Hw.sort_indices()
-        key = (Hw.shape, Hw.indptr.tobytes(), Hw.indices.tobytes(), b"" if p is None else p[fault].tobytes())
+        key = (Hw.shape, Hw.indptr.tobytes(), Hw.indices.tobytes(), b"" if p is None else p[fault].tobytes(),
+               b"" if fk is None else fk[fault].tobytes())
         if key not in seen:
             if check_rank:
                 rank = gf2_rank(Hw.toarray())
@@ -128,11 +134,15 @@ def _split_decode(r, decoder):
 class _Model:
     """The validated model and its plan: what both classes below start from."""
 
-    def __init__(self, H, L, priors, detector_time, window):
+    def __init__(self, H, L, priors, detector_time, window, relay=None):
         self.H, self.L, self.priors = checked_model(H, L, priors)
         self.M, self.N = self.H.shape
         self.K = self.L.shape[0]
-        self.plan = window_plan(self.H, detector_time, window, priors=self.priors)
+        # relay= over the model: memory strengths for all N faults, every window takes the columns of its own faults, and
+        # windows share a decoder only where those agree (a configuration of another width goes to every window as it is)
+        self.relay = relay if relay is not None and getattr(relay, "n", None) == self.N else None
+        self.plan = window_plan(self.H, detector_time, window, priors=self.priors,
+                                fault_key=None if self.relay is None else self.relay.gammas.T)
         self.HT = self.H.T.tocsr()  # row i = column i of H
         self.LT = self.L.T.tocsr()
 
@@ -141,8 +151,9 @@ class _Model:
         decs = []
         for w in self.plan.unique:
             win = self.plan.windows[w]
+            kw = decoder_kwargs if self.relay is None else dict(decoder_kwargs, relay=self.relay.restrict(win.fault))
             try:
-                decs.append(factory(win.H, channel_probs=self.priors[win.fault], **decoder_kwargs))
+                decs.append(factory(win.H, channel_probs=self.priors[win.fault], **kw))
             except ValueError as e:
                 raise ValueError(f"window {w} (times [{win.lo}, {win.hi}), {win.H.shape[0]} x {win.H.shape[1]}): {e}") from None
         return decs
@@ -203,7 +214,8 @@ class WindowedDemDecoder:
         they come out of a detector-error-model file)
     window : (W, C), 1 <= C <= W
     batch_size : rows the engine's device buffers hold; a longer ``decode_batch`` runs in chunks of it (default 4096)
-    decoder_kwargs : for every window's ``BpOsdDecoder(H_w, channel_probs=priors[F_w], ...)``
+    decoder_kwargs : for every window's ``BpOsdDecoder(H_w, channel_probs=priors[F_w], ...)``.  ``relay=`` takes a
+        ``RelayConfig`` over all N faults of the model: window w runs with the columns F_w of its memory strengths
 
     ``decode_batch(detectors)`` returns the observable rows and leaves ``batch_correction``, ``batch_residual``,
     ``batch_converge`` (BP converged in every window) and ``batch_iter`` (iterations summed over the windows)."""
@@ -212,7 +224,7 @@ class WindowedDemDecoder:
         from .decoder import BpOsdDecoder
 
         self._win = None
-        self._model = m = _Model(H, L, priors, detector_time, window)
+        self._model = m = _Model(H, L, priors, detector_time, window, relay=decoder_kwargs.get("relay"))
         self.M, self.N, self.K = m.M, m.N, m.K
         self.plan = m.plan
         self._capacity = int(batch_size)
@@ -322,7 +334,7 @@ class windowed_dem_decode_sim(DemSimBase):
                  decoder_factory=None, run_sim=True, harvest=0, **decoder_kwargs):
         self._check_engine(engine, decoder_factory, "decoders")
         self._win = self._sampler = None
-        self._model = m = _Model(H, L, priors, detector_time, window)
+        self._model = m = _Model(H, L, priors, detector_time, window, relay=decoder_kwargs.get("relay"))
         self.M, self.N, self.K = m.M, m.N, m.K
         self._init_harvest(harvest)
         self.plan = m.plan

@@ -345,6 +345,41 @@ int bposd_last_osd_kernel(bposd_handle *h);
 int bposd_set_bp_variant(bposd_handle *h, int32_t variant);
 
 /*
+ * Relay-BP (Mueller et al., 2025): a mode of the handle.  With it on, the BP stage of every decode call (host, device and
+ * packed pointers, per-shot channels, observables, the DEM engine) runs min-sum as a chain of `legs` legs with a memory term
+ * per bit.  The mode and its tables belong to one handle and its n bits: the window engine (bposd_window_*) runs every window
+ * on the handle it was given for it, in relay mode where that handle is, so a windowed relay decode sets each window's handle
+ * with the columns of its own faults (bp_osd_amd/window.py does).  The outputs, the OSD hand-off and the lane buffers are
+ * those of every other BP kernel.  Per shot, with l0 the shot's prior LLRs:
+ *   M = l0, dec = 0, every bit->check message = l0 of its bit, t = 0, found = 0.  An all-zero syndrome returns zeros,
+ *   converged 1, 0 iterations (solutions 0, best_leg -1, weight 0).
+ *   Leg r = 0 .. legs-1, g = gammas[r]: for r > 0 and leg_init == 0 the bit->check messages go back to l0 (leg_init == 1
+ *   keeps them; M is always kept).  Up to leg_iters[r] times: t += 1; the min-sum check pass with the scaling factor of
+ *   iteration t; the bit pass with  lam = (1 - g[j]) * l0[j] + g[j] * M[j]  (two products, one add, each rounded) in the
+ *   place of the prior -- M[j] becomes the posterior, dec[j] = (M[j] <= 0).  If H dec == syndrome: found += 1,
+ *   w = sum_j dec[j] * W[j] with W[j] = (int64) rint(clamp(l0[j], -32768, 32768) * 2^32); the solution replaces the best one
+ *   if it is the first or w is strictly lower; the leg ends; after `stop_after` solutions the shot ends.
+ *   Result: iterations = t.  found > 0: the bp, osd0 and osdw rows are the best solution, converged 1.  Otherwise the bp row
+ *   is the last dec, converged 0, and with OSD enabled the shot goes to the OSD stage with M as its LLRs.  The LLR output
+ *   is the final M.
+ * legs = 1, gammas = 0, leg_iters = {max_iter}, stop_after = 1 is plain min-sum bit for bit (priors inside (0, 1)).
+ *
+ * bposd_set_relay copies gammas (float64 [legs][n]) and leg_iters (int32 [legs]) to the device after the calls in flight
+ * have ended.  legs = 0 switches the mode off: the handle launches what it launched before.  BPOSD_ERR_INVALID (handle
+ * unchanged) for legs < 0, a non-finite gamma, a leg of fewer than 1 iteration, stop_after < 1, leg_init other than 0 / 1
+ * or NULL tables with legs > 0; BPOSD_ERR_UNSUPPORTED for product-sum or the serial schedule.
+ *
+ * bposd_relay_stats copies the per-shot words of the last call that ran on `lane` (-1: the lane of the last relay launch) to host arrays of B
+ * entries, any of which may be NULL: solutions found, leg of the best one (-1: none), its weight.  It waits for that lane.
+ * BPOSD_ERR_INVALID if that call did not run in relay mode or B is not its batch size.  With all three arrays NULL nothing
+ * is copied and the return value is that call's batch size (>= 1).  A host-pointer call of several chunks leaves each
+ * lane the words of its last chunk only.
+ */
+int bposd_set_relay(bposd_handle *h, int32_t legs, const double *gammas, const int32_t *leg_iters, int32_t stop_after,
+                    int32_t leg_init);
+int bposd_relay_stats(bposd_handle *h, int32_t lane, int32_t *solutions, int32_t *best_leg, int64_t *weight, int64_t B);
+
+/*
  * Monte-Carlo engine: the device-resident form of the reference's harness loop
  * (/root/reference/src/bposd/css_decode_sim.py:174-365, 465-498).  One bposd_mc_run is one batch of shots:
  * sample the errors -> both syndromes -> the two decodes -> logical checks of the bp / osd0 / osdw outputs -> seven

@@ -28,6 +28,7 @@ int bposd_layout_info(bposd_handle *h, int64_t *natural_cycles, int64_t *chosen_
 #define BPOSD_BP_KERNEL_LARGE 3  /* bp_large_kernel: messages in HBM */
 #define BPOSD_BP_KERNEL_SERIAL 4 /* bp_serial_kernel: schedule = serial */
 #define BPOSD_BP_KERNEL_ANYDEG 5 /* bp_anydeg_kernel: check degree > 16 or bit degree > 8 (run-time degree loops) */
+#define BPOSD_BP_KERNEL_RELAY 6  /* bp_relay_kernel: relay mode (bposd_set_relay), any degree */
 int bposd_bp_kernel_info(bposd_handle *h, int32_t *kernel, int64_t *lds_model);
 
 /* Diagnostics: the exact kernel instances the last launches of this handle ran (a later change of the dispatch rules shows
@@ -40,6 +41,7 @@ int bposd_bp_kernel_info(bposd_handle *h, int32_t *kernel, int64_t *lds_model);
  *   bp_class_kernel <DCLO, DC, DVHI, MP>    (DVLO follows from the degree class)
  *   bp_large_kernel <DC, DV, METHOD>
  *   bp_serial_kernel, bp_anydeg_kernel      (no template integers)
+ *   bp_relay_kernel <INSTANCE>, threads     (INSTANCE 1: messages, prefixes and M in LDS; 2: in the lane's workspace)
  *   osd_kernel <W>,  osd_wave_kernel <RPL, W>,  osd_mw_kernel <NWV, RPL, W, MINW>,  osd_large_kernel <RPT>
  * The OSD record is also written by the rank probe of an HBM-resident handle at creation. */
 int bposd_debug_last_instance(bposd_handle *h, int32_t bp[6], int32_t osd[6]);
