@@ -109,6 +109,8 @@ DEBUG_SYMBOLS = (
     "bposd_debug_local_keys",
     "bposd_debug_local_waves",
     "bposd_debug_last_pair_key",
+    "bposd_debug_set_park",
+    "bposd_debug_last_parked",
     "bposd_debug_obs_timing",
     "bposd_debug_dem_timing",
     "bposd_debug_dem_harvest",
@@ -339,6 +341,10 @@ def load():
     lib.bposd_debug_local_waves.restype = C.c_int
     lib.bposd_debug_last_pair_key.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.bposd_debug_last_pair_key.restype = C.c_int
+    lib.bposd_debug_set_park.argtypes = [vp, C.c_int32]
+    lib.bposd_debug_set_park.restype = C.c_int
+    lib.bposd_debug_last_parked.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.bposd_debug_last_parked.restype = C.c_int
     lib.bposd_debug_obs_timing.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     lib.bposd_debug_obs_timing.restype = C.c_int
     lib.bposd_debug_class_layout.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]

@@ -33,6 +33,7 @@
 
 #include "bp_kernel.hip.h"
 #include "local_keys.h"
+#include "local_park.h"
 
 namespace bposd {
 
@@ -67,7 +68,12 @@ struct BpLocalParams {
     unsigned long long* __restrict__ iter_total;
     int* __restrict__ tail_flag;  // nullable, host-visible: set to 1 by the workgroup that finds the queue empty (the tail begins)
     int packed_io;  // 1: packed syndromes in, packed result rows out (bp_kernel.hip.h: BpParams::packed_io)
-    const double* __restrict__ llr0_rows;  // [B, n] nullable: this shot's own priors (wins over sel); last, so that no other argument moves
+    const double* __restrict__ llr0_rows;  // [B, n] nullable: this shot's own priors (wins over sel); behind the others, so that none of them moves
+    // park at drain (local_park.h): the first launch of a call parks unfinished shots once its queue is dry, the second
+    // launch (resume = 1, park_on_dry = 0) takes the records from a queue of their own and finishes them
+    unsigned char* __restrict__ park;  // [gridDim.x] records of bposd_local_park::layout(mp).bytes; null unless a launch parks or resumes
+    int park_on_dry;                   // bposd_local_park::Mode
+    int resume;
 };
 
 __host__ __device__ inline size_t bp_local_lds_bytes(int mp) {
@@ -160,7 +166,7 @@ __host__ __device__ constexpr bool bpl_specialised(int cpt, int mpt, int minw, b
 // instruction what it was before the packed form existed (as a run-time switch it cost the headline launch 1.2 %, same-box A/B)
 // PAIRKEY: -1, or the uniform key k of the one (k, mixed) wave this instance has a loop body for (local_keys.h: pair keys).
 // The host picks the instance from the layout's wave table; any other wave of unequal groups runs the generic body.
-template <int CPT, int MPT, int MINW, bool EARLY, bool UPRIOR, bool PACKED = false, int PAIRKEY = -1>
+template <int CPT, int MPT, int MINW, bool EARLY, bool UPRIOR, bool PACKED = false, int PAIRKEY = -1, bool RESUME = false>
 __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocalParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // (m and n are read where they are used, like the other per-syndrome arguments: held next to B as one four-dword load,
@@ -180,7 +186,7 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
     double* msg_plain = reinterpret_cast<double*>(smem);
     msg_ptr msg = (msg_ptr)msg_plain;
     unsigned int* diffw = reinterpret_cast<unsigned int*>(msg_plain + (size_t)4 * MP + 2);
-    int* sh = reinterpret_cast<int*>(diffw + (MP / 32 + 2));  // control words: [2] the queue ticket, [3] the OSD slot ([0], [1] unused)
+    int* sh = reinterpret_cast<int*>(diffw + (MP / 32 + 2));  // control words: [0], [1] the park words (by chunk parity), [2] the queue ticket, [3] the OSD / park slot
     const unsigned int diffw_base = (unsigned int)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)diffw;
 
     // ---- per-thread graph tables
@@ -262,14 +268,45 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
         asm volatile("" : "+v"(w));  // (waited for here, behind whatever was issued after the read)
         return __ballot(w != 0ull) == 0ull;
     };
+    // ---- park at drain (local_park.h)
+    // The keyed, pair and generic loops run in chunks of CH iterations: iterate() returns at a chunk boundary and the
+    // per-syndrome code below enters it again, or parks the shot.
+    constexpr int CH = bposd_local_park::kChunk;
+    constexpr bposd_local_park::Layout PARK = bposd_local_park::layout(MP);
+    static_assert((4 * MP) % NT == 0 && NT <= MP && NT >= MP / 32 && NT >= 2, "the park record is copied in whole rounds of the workgroup");
     for (;;) {
-        if (tid == 0) sh[2] = atomicAdd(&bpl_args()->counters[0], 1);
+        // both park words are cleared where the ticket is published (the barrier below is between this and their first read)
+        if (tid == 0) {
+            int t;
+            if (RESUME) {
+                // The continuation takes the records first (ticket >= 0; the first launch has ended: its record count is
+                // final), then whatever the first launch left in the call's queue (ticket = -1 - shot): nothing where it
+                // parked because the queue was dry, the rest of the batch where every workgroup was made to park before.
+                t = atomicAdd(&bpl_args()->counters[bposd_local_park::kResumeHead], 1);
+                if (t >= bpl_args()->counters[bposd_local_park::kParkCount]) t = -1 - atomicAdd(&bpl_args()->counters[0], 1);
+            } else t = atomicAdd(&bpl_args()->counters[0], 1);
+            sh[2] = t;
+            int zero = 0;
+            asm volatile("" : "+v"(zero));  // (made here: as a loop invariant the pair of zeros went to scratch)
+            sh[0] = zero;
+            sh[1] = zero;
+        }
         __syncthreads();
-        const long long s = __builtin_amdgcn_readfirstlane(sh[2]);
-        if (s >= P.B) {
-            // the chunk loop of the host-pointer API launches the next chunk's kernels when this one's tail begins
-            if (s == P.B && tid == 0 && bpl_args()->tail_flag) *(volatile int*)bpl_args()->tail_flag = 1;
-            break;
+        const int ticket = __builtin_amdgcn_readfirstlane(sh[2]);
+        const unsigned char* rec = nullptr;  // the record this workgroup restores
+        const bool resume = RESUME && ticket >= 0;
+        long long s;
+        if (resume) {
+            rec = bpl_args()->park + (size_t)ticket * PARK.bytes;
+            const long long sv = *(const long long*)(rec + PARK.shot);
+            s = ((long long)__builtin_amdgcn_readfirstlane((int)(sv >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)sv);
+        } else {
+            s = RESUME ? -1 - ticket : ticket;
+            if (s >= P.B) {
+                // the chunk loop of the host-pointer API launches the next chunk's kernels when this one's tail begins
+                if (s == P.B && tid == 0 && bpl_args()->tail_flag) *(volatile int*)bpl_args()->tail_flag = 1;
+                break;
+            }
         }
 
         // ---- syndrome bits of my checks; the mismatch bitmap (indexed by position) starts as the syndrome
@@ -279,7 +316,7 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
             const int c = bpl_table_load(bpl_args()->pos_chk, (unsigned int)tid * 4u, (unsigned int)(j * NT * 4));
             sbit[j] = (c >= 0) ? (PACKED ? bp_synd_bit(bpl_args()->synd, 1, s, m, c) : ((bpl_args()->synd[(size_t)s * m + c] & 1) != 0)) : false;
             const unsigned long long bal = __ballot(sbit[j]);
-            if (lane == 0) {
+            if (lane == 0 && !resume) {  // (a restored shot brings its bitmap)
                 const int w0 = ((wave << 6) + j * NT) >> 5;
                 diffw[w0] = (unsigned int)bal;
                 diffw[w0 + 1] = (unsigned int)(bal >> 32);
@@ -303,16 +340,33 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
                 }
         }
         // ---- a3: every edge's bit->check message starts at the prior (two in LDS, one in a register)
-        double loc[NB];
 #define BPL_LLRT (bpl_args()->llr_tmp + (size_t)blockIdx.x * n)
+        double loc[NB];
         unsigned int decmask = 0u;  // bit r: hard decision of my r-th bit
+        int it_cur = 1;             // the iteration the shot goes on from
+        if (!resume) {
 #pragma unroll
-        for (int r = 0; r < NB; ++r) {
-            double lp = BPL_L0(r);
-            if (UPRIOR) asm volatile("" : "+s"(lp));  // copied from the scalar pair here, not kept in a vector pair
-            loc[r] = lp;
-            *BPL_AT(alo[r]) = lp;
-            *BPL_AT(ahi[r]) = lp;
+            for (int r = 0; r < NB; ++r) {
+                double lp = BPL_L0(r);
+                if (UPRIOR) asm volatile("" : "+s"(lp));  // copied from the scalar pair here, not kept in a vector pair
+                loc[r] = lp;
+                *BPL_AT(alo[r]) = lp;
+                *BPL_AT(ahi[r]) = lp;
+            }
+        } else {
+            // ---- the shot as its record holds it: messages, bitmap, local messages, decisions, the iteration to go on from
+            // (a uniform base plus a 32-bit byte offset per lane, formed here: see bpl_table_load; volatile, as the LDS side is:
+            // one element in flight, not 4 * CPT register pairs)
+            unsigned int t8 = (unsigned int)tid * 8u;
+            asm volatile("" : "+v"(t8));
+#pragma unroll
+            for (int q = 0; q < 4 * MP / NT; ++q) msg[tid + q * NT] = *(const volatile double*)(rec + (t8 + (unsigned int)(PARK.msg + (size_t)q * NT * 8)));
+            if (tid < 2) msg[4 * MP + tid] = *(const volatile double*)(rec + (t8 + (unsigned int)(PARK.msg + (size_t)4 * MP * 8)));
+            if (tid < MP / 32) *(volatile __attribute__((address_space(3))) unsigned int*)(uintptr_t)(diffw_base + (t8 >> 1)) = *(const unsigned int*)(rec + ((t8 >> 1) + (unsigned int)PARK.bitmap));
+#pragma unroll
+            for (int r = 0; r < NB; ++r) loc[r] = *(const double*)(rec + (t8 + (unsigned int)(PARK.loc + (size_t)r * NT * 8)));
+            decmask = *(const unsigned int*)(rec + ((t8 >> 1) + (unsigned int)PARK.dec));
+            it_cur = __builtin_amdgcn_readfirstlane(*(const int*)(rec + PARK.iter));
         }
         if (want_llr()) {  // a syndrome that needs no iteration reports the priors
 #pragma unroll
@@ -326,12 +380,15 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
         __syncthreads();
 
         int it_done = 0;
-        int conv = bitmap_is_zero(bitmap_word()) ? 1 : 0;  // the zero syndrome (an int in one scalar register, not a lane mask)
+        // the zero syndrome (an int in one scalar register, not a lane mask); a restored shot is tested at the top of the
+        // iteration it goes on from, as it would have been without the park
+        int conv = (!resume && bitmap_is_zero(bitmap_word())) ? 1 : 0;
         // The iteration loop, as a body per (KEY, LLR).  KEY >= 0: every group of the wave has this key (local_keys.h) and the
         // bit pass is straight-line code (a pair key: group 0 has the uniform key, group 1 the mixed one); KEY < 0: the generic
         // body, one switch per group on its key.  LLR: the body that
         // stores the posterior LLRs (every iteration if out_llr is set, else the last one only); the body without them runs
-        // iterations it0 .. max_iter - 1 and holds no test of it.  Returns 1 once conv / it_done are final.
+        // one chunk, iterations it0 .. min(max_iter, it0 + CH) - 1, and holds no test of max_iter.  Returns 1 once conv /
+        // it_done are final.
         // Convergence: the bitmap is final at the barrier that ends a bit pass, and the top of iteration `it` tests all of it
         // (bitmap_word): zero means the decisions of iteration it - 1 satisfy the syndrome.  The test is a ballot, so the exit
         // is a scalar branch, and it is the same in every wave.  Nobody writes the bitmap between that barrier and the next
@@ -341,8 +398,10 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
             constexpr int KEY = decltype(key_c)::value;
             constexpr bool LLR = decltype(llr_c)::value;
             const int max_iter = bpl_args()->max_iter;  // (read here: hoisted out of the syndrome loop it and the tests on it occupy scalar registers)
+            // the body without LLR stores runs one chunk: it returns 0 at the boundary it0 + CH, or at max_iter as before
+            const int lim = (max_iter - it0 > CH) ? it0 + CH : max_iter;
 #pragma clang loop unroll(disable)
-            for (int it = it0; LLR || it < max_iter; ++it) {
+            for (int it = it0; LLR || it < lim; ++it) {
                 asm volatile("; bpl_body key=%0 llr=%1" ::"n"(KEY), "n"((int)LLR));  // names the loop in the ISA listing (tools/isa_loop_count.py)
                 // the bitmap read, then the first check's message loads (all checks' if EARLY), then the test: its LDS round
                 // trip overlaps the loads, which a converged syndrome discards (LDS accesses are volatile: issued in this order)
@@ -466,37 +525,85 @@ __global__ __launch_bounds__(MPT / CPT, MINW) void bp_local_kernel(const BpLocal
             }
             return 0;
         };
+        int done = 0;  // (an int in one scalar register, not a lane mask) 1: conv / it_done are final, 2: the shot parks
         if (!conv) {
             // the body is chosen here, once per syndrome, from a scalar register; every wave of the workgroup passes the same
             // barriers and leaves at the same iteration whichever body it runs
-            int done = 0;  // (an int in one scalar register, not a lane mask)
             int it_llr = 1;  // (out_llr set: every iteration stores LLRs, the LLR body runs from the start)
             if (!want_llr()) {
                 int wk = wkey;
                 asm volatile("" : "+s"(wk));
+              for (;;) {  // one chunk per trip: the same switch, entered again at the boundary
                 if constexpr (SPEC) {
                     switch (wk) {
-                        case 0: done = iterate(bpl_int<0>{}, bpl_int<0>{}, 1); break;
-                        case 1: done = iterate(bpl_int<1>{}, bpl_int<0>{}, 1); break;
-                        case 2: done = iterate(bpl_int<2>{}, bpl_int<0>{}, 1); break;
-                        case 5: done = iterate(bpl_int<5>{}, bpl_int<0>{}, 1); break;
-                        case 6: done = iterate(bpl_int<6>{}, bpl_int<0>{}, 1); break;
-                        case 10: done = iterate(bpl_int<10>{}, bpl_int<0>{}, 1); break;
-                        case bposd_local_keys::kMixedKey: done = iterate(bpl_int<bposd_local_keys::kMixedKey>{}, bpl_int<0>{}, 1); break;
+                        case 0: done = iterate(bpl_int<0>{}, bpl_int<0>{}, it_cur); break;
+                        case 1: done = iterate(bpl_int<1>{}, bpl_int<0>{}, it_cur); break;
+                        case 2: done = iterate(bpl_int<2>{}, bpl_int<0>{}, it_cur); break;
+                        case 5: done = iterate(bpl_int<5>{}, bpl_int<0>{}, it_cur); break;
+                        case 6: done = iterate(bpl_int<6>{}, bpl_int<0>{}, it_cur); break;
+                        case 10: done = iterate(bpl_int<10>{}, bpl_int<0>{}, it_cur); break;
+                        case bposd_local_keys::kMixedKey: done = iterate(bpl_int<bposd_local_keys::kMixedKey>{}, bpl_int<0>{}, it_cur); break;
                         default:  // the instance's pair key, if it has one; else the generic body
-                            if (PKEY >= 0 && wk == PKEY) done = iterate(bpl_int<(PKEY >= 0 ? PKEY : -1)>{}, bpl_int<0>{}, 1);
-                            else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1);
+                            if (PKEY >= 0 && wk == PKEY) done = iterate(bpl_int<(PKEY >= 0 ? PKEY : -1)>{}, bpl_int<0>{}, it_cur);
+                            else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, it_cur);
                             break;
                     }
-                } else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, 1);
+                } else done = iterate(bpl_int<-1>{}, bpl_int<0>{}, it_cur);
                 asm volatile("" : "+s"(done));
                 it_llr = bpl_args()->max_iter;
+                if (done || it_llr - it_cur < CH) break;  // finished, or what is left is the last iteration's (the LLR body's)
+                // ---- a chunk boundary: the body has run iterations it_cur .. it_cur + CH - 1 and the shot is not finished
+                it_cur += CH;
+                const int pmode = bpl_args()->park_on_dry;
+                if (pmode) {
+                    // Why every wave takes the same exit.  The word read at the end of chunk c, sh[c & 1], was written at the end
+                    // of chunk c - 1 (or cleared with the ticket), and every wave has passed the 2 * CH barriers of chunk c since;
+                    // its next write comes at the end of chunk c + 1, behind the barriers of that chunk, which no wave passes
+                    // before all have read here.  At least one barrier lies between a word's write and its read and between that
+                    // read and its next write, so all waves read the same value -- with no barrier of the park's own and nobody
+                    // waiting for anybody.  A shot parks at most two chunks after the queue ran dry.
+                    // The queue head is loaded here, by thread 0, and not a chunk earlier: held across the chunk it is a 65th
+                    // vector register (44 B/lane of scratch in the headline instance).  Wave 0 waits for the load once per CH
+                    // iterations -- and only shots past iteration CH get here at all.
+                    const int chunk = (it_cur - 1) / CH - 1;  // the chunk that has ended (a shot of a parking launch starts at iteration 1)
+                    const int parkw = __builtin_amdgcn_readfirstlane(*(volatile int*)&sh[chunk & 1]);
+                    if (tid == 0) sh[(chunk + 1) & 1] = (__hip_atomic_load(&bpl_args()->counters[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= P.B) ? 1 : 0;
+                    if (parkw != 0 || pmode == bposd_local_park::kForce) {
+                        done = 2;  // the record is written in front of the result section
+                        break;
+                    }
+                }
+              }
                 it_llr = it_llr > 1 ? it_llr : 1;
             }
             if (!done) iterate(bpl_int<-1>{}, bpl_int<1>{}, it_llr);
         }
 
         // ---- results
+        if (done == 2) {
+            // ---- park: the shot's state goes into a record and the workgroup leaves (it draws no ticket again,
+            // so a launch writes at most gridDim.x records).  Every wave is behind the barrier that ended the
+            // chunk's last bit pass: messages and bitmap are final.
+            if (tid == 0) sh[3] = atomicAdd(&bpl_args()->counters[bposd_local_park::kParkCount], 1);
+            __syncthreads();
+            unsigned char* prec = bpl_args()->park + (size_t)__builtin_amdgcn_readfirstlane(sh[3]) * PARK.bytes;
+            // (a uniform base plus a 32-bit byte offset per lane, formed here: see bpl_table_load; volatile, as the
+            // LDS side is: one element in flight, not 4 * CPT register pairs)
+            unsigned int t8 = (unsigned int)tid * 8u;
+            asm volatile("" : "+v"(t8));
+#pragma unroll
+            for (int q = 0; q < 4 * MP / NT; ++q) *(volatile double*)(prec + (t8 + (unsigned int)(PARK.msg + (size_t)q * NT * 8))) = msg[tid + q * NT];
+            if (tid < 2) *(volatile double*)(prec + (t8 + (unsigned int)(PARK.msg + (size_t)4 * MP * 8))) = msg[4 * MP + tid];
+            if (tid < MP / 32) *(unsigned int*)(prec + ((t8 >> 1) + (unsigned int)PARK.bitmap)) = *(const volatile __attribute__((address_space(3))) unsigned int*)(uintptr_t)(diffw_base + (t8 >> 1));
+#pragma unroll
+            for (int r = 0; r < NB; ++r) *(double*)(prec + (t8 + (unsigned int)(PARK.loc + (size_t)r * NT * 8))) = loc[r];
+            *(unsigned int*)(prec + ((t8 >> 1) + (unsigned int)PARK.dec)) = decmask;
+            if (tid == 0) {
+                *(long long*)(prec + PARK.shot) = s;
+                *(int*)(prec + PARK.iter) = it_cur;
+            }
+            return;
+        }
         const bool to_osd = (!conv) && bpl_args()->osd_enabled;
         if (tid == 0) {
             if (to_osd) {

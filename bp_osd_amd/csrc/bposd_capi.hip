@@ -202,7 +202,9 @@ DecodeCall take_next_lane(bposd_handle* h) {
     h->nrec = 0;
     h->async_pending = true;
     Lane& L = h->lanes[lane];
-    return DecodeCall{&L, &h->lane_rec[lane], L.osd_stream};  // stream order on the lane: its previous call has filled the record by now
+    DecodeCall call{&L, &h->lane_rec[lane], L.osd_stream};  // stream order on the lane: its previous call has filled the record by now
+    call.device_ptr = true;
+    return call;
 }
 
 static int report_osd_debug(bposd_handle* h, const DecodeCall& call);
@@ -222,7 +224,7 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
         if ((rc = ensure_lanes(h, &Lane::llr_ws, sizeof(double) * (size_t)B * h->n))) return rc;
         if ((rc = ensure_lanes(h, &Lane::osd_list, sizeof(int) * (size_t)B))) return rc;
     }
-    HIP_TRY(h, hipMemsetAsync(L.d_counters, 0, 32, L.stream));
+    HIP_TRY(h, hipMemsetAsync(L.d_counters, 0, bposd_local_park::kCounterBytes, L.stream));
 
     BpParams P{};
     P.m = h->m;
@@ -259,8 +261,12 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
     // second from the first workgroup on -- both then take twice as long and finish together.  (ii) The OSD kernel needs a
     // whole CU (131 KB of LDS for H1922); while ANY persistent BP grid is waiting, every slot a draining CU frees goes to a BP
     // workgroup, which fits, and the eliminations of call k starve until the pipeline runs dry (traced with three and four
-    // asynchronous host calls in flight: completions came in bursts of three).  With this rule OSD(k) gets its CUs at the
-    // start of BP(k + 1)'s tail and BP(k + 2) follows ~1 ms later, whatever the number of calls queued.
+    // asynchronous host calls in flight: completions came in bursts of three).  With this rule OSD(k) gets its CUs in the tail
+    // of BP(k + 1), whatever the number of calls queued -- and only as fast as that tail frees whole CUs: a workgroup of the
+    // persistent grid finishes the shot it holds after the queue has run dry, a max_iter straggler pins its CU for
+    // milliseconds, and BP(k + 2) waits behind that ramp and the eliminations.  The local-edge kernel therefore ends its
+    // first launch at the drain (park at drain, local_park.h / launch_bp_local.h: unfinished shots go into records, a second
+    // launch of the kernel's small footprint finishes them next to OSD(k) and BP(k + 2)); the other BP kernels drain as before.
     // (Not where BP is HBM-resident: there both kernels need a whole CU, the OSD stream has the higher priority, and three calls in
     // flight are what fills the CUs -- see the lane count in bposd_create.  BPOSD_TWO_BACK=0/1 overrides, for probes.)
     static const char* two_back_env = getenv("BPOSD_TWO_BACK");
@@ -338,6 +344,7 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
     }
     if (osd_on && !lean) {  // whatever follows on the lane's stream comes after the OSD kernel
         HIP_TRY(h, hipEventRecord(L.ev_osd, L.osd_stream));
+        L.osd_recorded = true;
         HIP_TRY(h, hipStreamWaitEvent(L.stream, L.ev_osd, 0));
     }
     if (!lean) {
@@ -569,9 +576,9 @@ int bposd_create(const bposd_config* cfg, const int32_t* indptr, const int32_t* 
     for (auto& l : h->lanes) {
         CREATE_HIP(hipStreamCreateWithFlags(&l.stream.raw, hipStreamNonBlocking));
         CREATE_HIP(hipStreamCreateWithPriority(&l.osd_stream.raw, hipStreamNonBlocking, prio_greatest));
-        for (Event* e : {&l.ev_bp, &l.ev_osd, &l.ev_done, &l.ev_up, &l.ev_copy}) CREATE_HIP(hipEventCreateWithFlags(&e->raw, hipEventDisableTiming));
+        for (Event* e : {&l.ev_bp, &l.ev_osd, &l.ev_park, &l.ev_done, &l.ev_up, &l.ev_copy}) CREATE_HIP(hipEventCreateWithFlags(&e->raw, hipEventDisableTiming));
         CREATE_HIP(hipStreamCreateWithFlags(&l.copy_stream.raw, hipStreamNonBlocking));
-        CREATE_HIP(l.d_counters.alloc(32));  // 4 counters + the 64-bit iteration total: one memset, one copy
+        CREATE_HIP(l.d_counters.alloc(bposd_local_park::kCounterBytes));  // 4 counters + the 64-bit iteration total (one copy) + the park words: one memset
         CREATE_HIP(l.h_tail.alloc(64, hipHostMallocMapped));
         *l.h_tail.as<int>() = 0;
     }
@@ -821,6 +828,26 @@ int bposd_debug_last_instance(bposd_handle* h, int32_t bp[6], int32_t osd[6]) {
     if (!h) return BPOSD_ERR_INVALID;
     if (bp) std::copy(h->last_bp_inst, h->last_bp_inst + 6, bp);
     if (osd) std::copy(h->last_osd_inst, h->last_osd_inst + 6, osd);
+    return BPOSD_OK;
+}
+
+int bposd_debug_set_park(bposd_handle* h, int32_t mode) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (mode < bposd_local_park::kAuto || mode > bposd_local_park::kAlways) return fail(h, BPOSD_ERR_INVALID, "bposd_debug_set_park: mode must be 0 (auto), 1 (never) or 2 (force)");
+    h->park_mode = mode;
+    return BPOSD_OK;
+}
+
+int bposd_debug_last_parked(bposd_handle* h, int32_t lane, int32_t* parked) {
+    if (!h || !parked) return BPOSD_ERR_INVALID;
+    if (lane < 0 || lane >= h->nlanes) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range (%d lanes)", lane, h->nlanes);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    // the lane's counter block keeps the word until the lane's next call clears it
+    HIP_TRY(h, hipStreamSynchronize(h->lanes[lane].stream));
+    int v = 0;
+    HIP_TRY(h, hipMemcpy(&v, h->lanes[lane].d_counters + bposd_local_park::kParkCount, sizeof(int), hipMemcpyDeviceToHost));
+    *parked = v;
     return BPOSD_OK;
 }
 

@@ -417,6 +417,7 @@ int decode_host_async_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool 
         if (host.bp && (rc = need(&Lane::io_pbp, b8 * rsn))) return rc;
     }
     DecodeCall call = take_next_lane(h);
+    call.device_ptr = false;
     Lane& L = *call.lane;
     if (L.copy_pending) { HIP_TRY(h, hipStreamSynchronize(L.copy_stream)); L.copy_pending = false; }
     // The copies and the pack / unpack kernels go to the lane's HIGH-PRIORITY stream (the one its OSD kernel runs on), ordered
@@ -488,7 +489,8 @@ int decode_obs_host_impl(bposd_handle* h, const void* synd, bool synd_packed, in
     int rc;
     if (async) {
         if ((rc = obs_reserve(h, (size_t)B, host, /*host=*/true, synd_packed))) return rc;
-        const DecodeCall call = take_next_lane(h);
+        DecodeCall call = take_next_lane(h);
+        call.device_ptr = false;
         DrainOnError drain{h};
         if ((rc = obs_host_step(h, call, (const uint8_t*)synd, synd_packed, 0, B, host))) return rc;
         drain.armed = false;

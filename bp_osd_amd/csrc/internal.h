@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "local_park.h"      // park at drain of the local-edge BP kernel: counter block, record layout, the rule
 #include "bp_kernel.hip.h"   // BpParams, bp_lds_bytes (templates only: nothing is instantiated by including it)
 #include "osd_kernel.hip.h"  // OsdParams
 #include "owned.h"           // DeviceGuard, DevBuf, DevArray, PinnedBuf, Stream, Event
@@ -33,12 +34,15 @@ struct Lane {
     // grid of the NEXT call's BP kernel for every CU that frees up and take many times their own run time.
     Stream osd_stream;
     Event ev_bp, ev_osd;
+    Event ev_park;  // park at drain: orders the continuation launch (on osd_stream) between the lane's two streams
     Event ev_done;  // both kernels of the lane's last (non-lean) call have ended
     bool done_recorded = false;
     PinnedBuf h_stage;  // page-locked, device-visible staging for small host-pointer calls (zero-copy path)
     Event ev_up;        // host-pointer calls: this lane's chunk has been uploaded (uploads go one at a time, in
                         // chunk order: the first chunk's kernels then start after one chunk's copy time)
     DevBuf bpl_msg, bpl_llr;  // large BP workspaces (bpl_llr also serves the local-edge kernel: LLRs of the current syndrome)
+    DevBuf bpl_park;          // local-edge kernel, park at drain (local_park.h): one record per workgroup of the BP grid
+    bool osd_recorded = false;  // ev_osd has been recorded at least once
     DevBuf osdl_ws;           // large OSD workspaces (matrix, sort keys, pivots, weights) carved from one allocation
     DevBuf osd_rows_ws;       // OSD kernel's per-workgroup spill area for finished row words
     DevBuf llr_ws, osd_list, io_synd, io_osdw, io_osd0, io_bp, io_conv, io_iters, io_llr, io_sel;
@@ -56,7 +60,8 @@ struct Lane {
     PinnedBuf h_list;                // page-locked copy of the chunk's OSD list (syndrome index per slot, ints)
     bool copy_pending = false;
     DevArray<long long> d_osd_dbg;   // diagnostics (BPOSD_OSD_DEBUG=1): phase timestamps
-    DevArray<int> d_counters;        // 4 ints, and behind them the 64-bit iteration total
+    DevArray<int> d_counters;        // 4 ints, the 64-bit iteration total (these 32 bytes go into the call record), and the park
+                                     // words of the local-edge kernel behind them (local_park.h: kCounterBytes)
     // per-shot channel of a device-pointer call (bposd_decode_batch_select_device): priors and weights of the alternative
     // channel, 2n doubles, copied from a page-locked staging block on the lane's own stream -- consecutive select calls
     // overlap like plain ones (the first version drained every lane and made two blocking copies per call)
@@ -131,6 +136,7 @@ struct bposd_handle {
     int32_t last_osd_inst[6] = {-1, 0, 0, 0, 0, 0};
     int local_pair_key = -1;    // PAIRKEY of the bp_local_kernel instance this layout's (uniform, mixed) wave wants (local_layout::wave_plan), -1 none
     int last_bp_pair_key = -1;  // bposd_debug_last_pair_key: PAIRKEY of the last bp_local_kernel launch (-1: the plain instance)
+    int park_mode = 0;          // bposd_debug_set_park: bposd_local_park::UserMode (BPOSD_PARK in the environment wins)
     // host copies
     std::vector<int> rp, ci;
     std::vector<double> probs;
@@ -175,6 +181,7 @@ struct DecodeCall {
     bool packed = false;               // the kernels read packed syndromes and write packed result rows
     bool tail_gate = false;            // a chunk of a synchronous host-pointer call: its BP kernel reports its tail
     bool lean = false;                 // the small host-pointer call: one stream, no events (decode_device_impl)
+    bool device_ptr = false;           // a device-pointer call (take_next_lane; the asynchronous host-pointer forms clear it)
 };
 
 namespace bposd_host {

@@ -25,10 +25,49 @@ static int launch_bp_local_tp(bposd_handle* h, const DecodeCall& call, const bpo
     if (rc) return rc;
     BpLocalParams Lq = L;
     Lq.llr_tmp = (double*)call.lane->bpl_llr.p;
+    // park at drain (local_park.h) exists for the instances auto-selection takes: launch_bp_local has applied the rest of the rule
+    constexpr bool can_park = bpl_specialised(CPT, MP, MINW, EARLY);
+    if (!can_park) Lq.park_on_dry = bposd_local_park::kOff;
+    if (Lq.park_on_dry) {
+        if ((rc = ensure_lanes(h, &Lane::bpl_park, bposd_local_park::layout(MP).bytes * (size_t)grid))) return rc;
+        Lq.park = (unsigned char*)call.lane->bpl_park.p;
+    }
     note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_LOCAL, CPT, MP, MINW, EARLY, PACKED);
     h->last_bp_pair_key = PAIRKEY;
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(nt), lds, call.lane->stream, Lq);
     HIP_TRY(h, hipGetLastError());
+    if constexpr (can_park) {
+        if (Lq.park_on_dry) {
+            // The continuation: the same kernel's RESUME instance directly behind the first launch, same shape and grid,
+            // persistent over the park records.  Events are all that lies between the two.  It goes to the call's
+            // HIGH-PRIORITY stream (the one the OSD kernel follows on): the slots the first launch frees at the drain
+            // otherwise go to workgroups of the other lane's BP grid that are still undispatched, the continuation then
+            // starts only when THAT grid drains, and the pipeline settles a phase later (seen once in eight runs of the
+            // headline: 22.5 instead of 21.2 ms per step, kernel_ms.bp 36 ms).  The lane's main stream waits for it, so
+            // everything recorded there afterwards -- the timing event, ev_bp -- covers both launches.
+            auto kr = bp_local_kernel<CPT, MP, MINW, EARLY, UPRIOR, PACKED, PAIRKEY, true>;
+            { int rc_lds = set_max_lds(h, (const void*)kr, lds); if (rc_lds) return rc_lds; }
+            Lq.park_on_dry = bposd_local_park::kOff;
+            Lq.resume = 1;
+            // BPOSD_PARK_ORDER=1 (A/B): the continuation lets the previous lane's OSD kernel go first
+            static const char* order_env = getenv("BPOSD_PARK_ORDER");
+            if (order_env && order_env[0] == '1') {
+                Lane& prev = h->lanes[((int)(call.lane - h->lanes) + h->nlanes - 1) % h->nlanes];
+                if (&prev != call.lane && prev.osd_recorded) HIP_TRY(h, hipStreamWaitEvent(call.lane->stream, prev.ev_osd, 0));
+            }
+            hipStream_t cs = call.osd_stream ? call.osd_stream : call.lane->stream;
+            if (cs != call.lane->stream) {
+                HIP_TRY(h, hipEventRecord(call.lane->ev_park, call.lane->stream));
+                HIP_TRY(h, hipStreamWaitEvent(cs, call.lane->ev_park, 0));
+            }
+            hipLaunchKernelGGL(kr, dim3((unsigned)grid), dim3(nt), lds, cs, Lq);
+            HIP_TRY(h, hipGetLastError());
+            if (cs != call.lane->stream) {
+                HIP_TRY(h, hipEventRecord(call.lane->ev_park, cs));
+                HIP_TRY(h, hipStreamWaitEvent(call.lane->stream, call.lane->ev_park, 0));
+            }
+        }
+    }
     return 0;
 }
 

@@ -40,6 +40,28 @@ int launch_bp_local(bposd_handle* h, const DecodeCall& call, const BpParams& P) 
     L.grp_dl = h->d_lgrp_dl; L.pos_dl = h->d_lpos_dl;
     L.out_bp = P.out_bp; L.out_osd0 = P.out_osd0; L.out_osdw = P.out_osdw; L.out_conv = P.out_conv; L.out_iters = P.out_iters;
     L.out_llr = P.out_llr; L.llr_ws = P.llr_ws; L.osd_list = P.osd_list; L.counters = P.counters; L.iter_total = P.iter_total; L.tail_flag = P.tail_flag; L.packed_io = P.packed_io;
+    // a chunked host call counts as a whole; at most 40000 syndromes are a small call (below)
+    const long long work = call.batch_hint > 0 ? call.batch_hint : L.B;
+    const bool small_call = h->bp_variant == 0 && work <= 40000;
+    // ---- park at drain (local_park.h: park_rule).  "Another lane has work in flight" is asked of the streams themselves.
+    {
+        int user_mode = h->park_mode;
+        static const char* park_env = getenv("BPOSD_PARK");
+        if (park_env && park_env[0] == 'f') user_mode = bposd_local_park::kAlways;
+        else if (park_env && park_env[0] == '1') user_mode = bposd_local_park::kAuto;
+        else if (park_env && park_env[0] == '0') user_mode = bposd_local_park::kNever;
+        bool other_busy = false;
+        if (user_mode == bposd_local_park::kAuto && !small_call && call.device_ptr && !call.lean && !call.tail_gate && P.osd_enabled && !P.out_llr) {
+            for (int l = 0; l < h->nlanes && !other_busy; ++l) {
+                const Lane& o = h->lanes[l];
+                if (&o == call.lane) continue;
+                other_busy = hipStreamQuery(o.stream) == hipErrorNotReady || hipStreamQuery(o.osd_stream) == hipErrorNotReady;
+            }
+            if (hipPeekAtLastError() == hipErrorNotReady) (void)hipGetLastError();  // (a stream that is not ready is no error of this call; anything else stays)
+        }
+        L.park_on_dry = bposd_local_park::park_rule(user_mode, call.device_ptr, call.lean, call.tail_gate, P.out_llr != nullptr, P.osd_enabled != 0,
+                                                    /*specialised=*/true /* (launch_bp_local_tp knows) */, other_busy, small_call);
+    }
     // auto-selection launches the instance that has a body for the layout's (uniform key, mixed) wave, if it has one; a
     // variant asked for by number is the plain instance (generic body for that wave)
     const bool pair = h->bp_variant == 0 && h->local_pair_key >= 0;
@@ -55,8 +77,6 @@ int launch_bp_local(bposd_handle* h, const DecodeCall& call, const BpParams& P) 
     // per thread (16 waves per syndrome) iterates 25-30 % faster per syndrome, two checks per thread (4 workgroups per
     // CU) have the higher throughput.  Measured crossover on the [[1922,50]] code: 32768 syndromes per call (2048: 2.5
     // against 3.3 ms, 8192: 4.1 / 5.1, 32768: 9.6 / 10.0, 131072: 31.0 / 28.2).  A chunked host call counts as a whole.
-    const long long work = call.batch_hint > 0 ? call.batch_hint : L.B;
-    const bool small_call = h->bp_variant == 0 && work <= 40000;
     if (small_call) return uprior ? launch_bp_local_t<1, 1024, 8, false, true>(h, call, L) : launch_bp_local_t<1, 1024, 8, false>(h, call, L);
     if (pair) return launch_bp_local_pair_any(h, call, L, uprior ? kBplPair1024x8U : kBplPair1024x6);
     if ((h->bp_variant == 22 || h->bp_variant == 0) && uprior) return launch_bp_local_t<2, 1024, 8, false, true>(h, call, L);  // <= 64 VGPRs: 4 workgroups per CU

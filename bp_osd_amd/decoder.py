@@ -866,6 +866,18 @@ class BpOsdDecoder:
         _lib.check(self._lib, self._h, self._lib.bposd_debug_last_pair_key(self._h, C.byref(k)))
         return int(k.value)
 
+    PARK_MODES = {"auto": 0, "never": 1, "force": 2}
+
+    def set_park(self, mode: str):
+        """Test knob for the local-edge BP kernel's park at drain (``bposd_debug_set_park``): "auto", "never" or "force"."""
+        _lib.check(self._lib, self._h, self._lib.bposd_debug_set_park(self._h, self.PARK_MODES[mode]))
+
+    def last_parked(self, lane: int) -> int:
+        """Park records the last call queued on ``lane`` wrote (``bposd_debug_last_parked``); waits for that lane."""
+        k = C.c_int32(-1)
+        _lib.check(self._lib, self._h, self._lib.bposd_debug_last_parked(self._h, int(lane), C.byref(k)))
+        return int(k.value)
+
     def set_bp_variant(self, variant: int):
         """Tuning / test knob: 0 auto; 1, 2, 4 LDS kernel shapes; 16 .. 26 local-edge kernel; 32 class kernel; 63 HBM-resident min-sum with whole check records in the workspace; 64 any-degree kernel (slow; cross-checks) -- see the C header."""
         _lib.check(self._lib, self._h, self._lib.bposd_set_bp_variant(self._h, int(variant)))

@@ -83,6 +83,16 @@ int bposd_debug_local_waves(const int32_t *csr_indptr, const int32_t *csr_indice
  * after a launch of another kernel family. */
 int bposd_debug_last_pair_key(bposd_handle *h, int32_t *pair_key);
 
+/* Diagnostics: park at drain of the local-edge BP kernel (csrc/local_park.h).  mode 0 = auto (a device-pointer call with an
+ * OSD stage parks its unfinished shots once its queue is dry, if another lane of the handle has work in flight), 1 = never,
+ * 2 = force: every call the kernel can park in does, and every shot that reaches its first chunk boundary parks there
+ * whatever the queue says -- a test then depends on no timing.  BPOSD_PARK=0|1|force in the environment wins (0 = never). */
+int bposd_debug_set_park(bposd_handle *h, int32_t mode);
+
+/* Diagnostics: the number of park records the last call queued on `lane` wrote (0 where it did not park).  Waits for that
+ * lane; valid until the lane's next call. */
+int bposd_debug_last_parked(bposd_handle *h, int32_t lane, int32_t *parked);
+
 /* Diagnostics: duration of obs_kernel in the last observables call queued on `lane` (HIP events on the lane's stream; waits
  * for that lane), or, lane = -1, summed over the chunks of the last synchronous host-pointer observables call.  obs_kernel
  * runs behind the events of bposd_last_timing / bposd_lane_timing: their bp_ms and osd_ms do not include it. */
