@@ -14,6 +14,7 @@ from .dem import (dem_decode_sim, dem_failure_spectrum, fault_subsets, fit_sampl
 from .circuit import Circuit, check_annotations, circuit_dem, css_memory_circuit, dem_text, fault_columns  # noqa: F401
 from .window import WindowedDemDecoder, window_plan, windowed_dem_decode_sim  # noqa: F401
 from .relay import RelayConfig, RelayReferenceDecoder, relay_decode_reference, relay_gammas  # noqa: F401
+from .lsd import LsdConfig, LsdReferenceDecoder, lsd_decode_reference  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = (
     "bposd_set_bp_variant",
     "bposd_set_relay",
     "bposd_relay_stats",
+    "bposd_set_lsd",
+    "bposd_lsd_stats",
     "bposd_set_osd_variant",
     "bposd_last_osd_kernel",
     "bposd_mc_create",
@@ -363,6 +365,10 @@ def load():
     lib.bposd_set_relay.restype = C.c_int
     lib.bposd_relay_stats.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int64]
     lib.bposd_relay_stats.restype = C.c_int
+    lib.bposd_set_lsd.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    lib.bposd_set_lsd.restype = C.c_int
+    lib.bposd_lsd_stats.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int64]
+    lib.bposd_lsd_stats.restype = C.c_int
     lib.bposd_last_error.argtypes = [vp]
     lib.bposd_last_error.restype = C.c_char_p
     lib.bposd_destroy.argtypes = [vp]

@@ -218,7 +218,9 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
     Lane& L = *call.lane;
     CallRecord& R = *call.rec;
     const bool lean = call.lean;
-    const bool osd_on = h->cfg.osd_method != BPOSD_OSD_OFF && !call.bp_only;
+    const bool osd_kernel_on = h->cfg.osd_method != BPOSD_OSD_OFF && !call.bp_only;
+    const bool lsd_on = h->lsd_on && !call.bp_only;  // LSD mode: lsd_kernel consumes BP's list, with or without an OSD kernel behind it
+    const bool osd_on = osd_kernel_on || lsd_on;     // BP leaves a list, and something runs over it on the OSD stream
     int rc;
     if (osd_on) {
         if ((rc = ensure_lanes(h, &Lane::llr_ws, sizeof(double) * (size_t)B * h->n))) return rc;
@@ -277,6 +279,7 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
     }
     if (!lean) HIP_TRY(h, hipEventRecord(R.ev[0], L.stream));
     L.relay_B = -1;  // (launch_bp_relay sets it)
+    L.lsd_B = -1;    // (launch_lsd sets it)
     if (h->relay_legs > 0) {
         h->last_bp_kernel = BPOSD_BP_KERNEL_RELAY;
         if ((rc = launch_bp_relay(h, call, P))) return rc;
@@ -335,12 +338,17 @@ int decode_device_impl(bposd_handle* h, const DecodeCall& call, const IoPtrs& io
             HIP_TRY(h, hipMemsetAsync(L.d_osd_dbg, 0, 8192 * sizeof(long long), call.osd_stream));
             Q.dbg = L.d_osd_dbg;
         }
-        if (h->large) {
-            h->last_osd_kernel = 3;
-            if ((rc = launch_osd_large(h, call, Q, B, nullptr))) return rc;
-        } else if ((rc = launch_osd(h, call, Q, B))) return rc;
+        // LSD mode: lsd_kernel first; the OSD kernel then walks the list of the shots it handed on (launch_lsd redirects Q)
+        if (lsd_on && (rc = launch_lsd(h, call, Q, B, osd_kernel_on))) return rc;
+        if (osd_kernel_on) {
+            if (h->large) {
+                h->last_osd_kernel = 3;
+                if ((rc = launch_osd_large(h, call, Q, B, nullptr))) return rc;
+            } else if ((rc = launch_osd(h, call, Q, B))) return rc;
+            if (lsd_on && (rc = launch_lsd_compact(h, call, Q, (const int*)L.osd_list.p, L.d_counters, io.osd0 ? call.cmp_osd0 : nullptr, call.cmp_osdw, B))) return rc;
+        }
         R.ran_osd = true;
-        if (Q.dbg && (rc = report_osd_debug(h, call))) return rc;
+        if (Q.dbg && osd_kernel_on && (rc = report_osd_debug(h, call))) return rc;
     }
     if (osd_on && !lean) {  // whatever follows on the lane's stream comes after the OSD kernel
         HIP_TRY(h, hipEventRecord(L.ev_osd, L.osd_stream));
@@ -717,6 +725,7 @@ int bposd_set_relay(bposd_handle* h, int32_t legs, const double* gammas, const i
         return BPOSD_OK;
     }
     if (legs < 0) return fail(h, BPOSD_ERR_INVALID, "relay: legs = %d is negative", legs);
+    if (h->lsd_on) return fail(h, BPOSD_ERR_UNSUPPORTED, "relay mode cannot be combined with LSD mode (switch LSD mode off first)");
     if (h->cfg.bp_method != BPOSD_BP_MIN_SUM) return fail(h, BPOSD_ERR_UNSUPPORTED, "relay mode needs min-sum (bp_method is product-sum)");
     if (h->cfg.schedule != 0) return fail(h, BPOSD_ERR_UNSUPPORTED, "relay mode needs the flooding schedule (schedule is serial)");
     if (!gammas || !leg_iters) return fail(h, BPOSD_ERR_INVALID, "relay: %s is NULL with legs = %d", !gammas ? "gammas" : "leg_iters", legs);
@@ -761,6 +770,55 @@ int bposd_relay_stats(bposd_handle* h, int32_t lane, int32_t* solutions, int32_t
     if (solutions) HIP_TRY(h, hipMemcpy(solutions, L.relay_sol.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
     if (best_leg) HIP_TRY(h, hipMemcpy(best_leg, L.relay_leg.p, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
     if (weight) HIP_TRY(h, hipMemcpy(weight, L.relay_wt.p, sizeof(long long) * (size_t)B, hipMemcpyDeviceToHost));
+    return BPOSD_OK;
+}
+
+int bposd_set_lsd(bposd_handle* h, int32_t on, int32_t max_cluster_bits, int32_t max_cluster_checks) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (!on) {  // off: the tables stay where they are
+        h->lsd_on = false;
+        return BPOSD_OK;
+    }
+    if (h->relay_legs > 0) return fail(h, BPOSD_ERR_UNSUPPORTED, "LSD mode cannot be combined with relay mode (switch relay mode off first)");
+    if (max_cluster_bits < 1 || max_cluster_bits > lsd_max_bits())
+        return fail(h, BPOSD_ERR_INVALID, "lsd: max_cluster_bits = %d must be in [1, %d] (the ceiling of lsd_kernel)", max_cluster_bits, lsd_max_bits());
+    if (max_cluster_checks < 1 || max_cluster_checks > lsd_max_checks())
+        return fail(h, BPOSD_ERR_INVALID, "lsd: max_cluster_checks = %d must be in [1, %d] (the ceiling of lsd_kernel)", max_cluster_checks, lsd_max_checks());
+    // 16 bits per check, and the sparse set tells a lane's tag (0x8000 | lane) from a list index only while every index -- a
+    // check or a slot of a list of checks -- is below 0x8000 (a handle is created for m <= 16384)
+    if (h->m > 0x8000)
+        return fail(h, BPOSD_ERR_UNSUPPORTED, "LSD mode: m = %d checks do not fit lsd_kernel's 15-bit check indices", h->m);
+    if (lsd_lds_need(h->m, h->n) > h->lds_per_cu)
+        return fail(h, BPOSD_ERR_UNSUPPORTED, "LSD mode: the cluster state of m = %d checks and n = %d bits needs %zu bytes of LDS, the CU has %zu",
+                    h->m, h->n, lsd_lds_need(h->m, h->n), h->lds_per_cu);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls run without the mode
+    if (!h->d_lsd_cp) {
+        const int rct = build_tables_lsd(h);
+        if (rct) return rct;
+    }
+    h->lsd_max_bits = max_cluster_bits;
+    h->lsd_max_checks = max_cluster_checks;
+    h->lsd_on = true;
+    return BPOSD_OK;
+}
+
+int bposd_lsd_stats(bposd_handle* h, int32_t lane, int32_t* status, int32_t* rounds, int32_t* clusters, int32_t* max_bits, int64_t B) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (lane == -1) lane = h->lsd_lane;
+    if (lane < 0 || lane >= h->nlanes) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range", lane);
+    Lane& L = h->lanes[lane];
+    if (L.lsd_B < 0) return fail(h, BPOSD_ERR_INVALID, "the last call on lane %d did not run in LSD mode", lane);
+    // no arrays: the batch size of that call (as bposd_relay_stats)
+    if (!status && !rounds && !clusters && !max_bits) return (int)std::min<long long>(L.lsd_B, INT_MAX);
+    if (B != L.lsd_B) return fail(h, BPOSD_ERR_INVALID, "the last call on lane %d decoded %lld syndromes, not %lld", lane, L.lsd_B, (long long)B);
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    HIP_TRY(h, hipStreamSynchronize(L.stream));
+    int32_t* const dst[4] = {status, rounds, clusters, max_bits};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k]) HIP_TRY(h, hipMemcpy(dst[k], (const int*)L.lsd_stat.p + (size_t)k * B, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
     return BPOSD_OK;
 }
 

@@ -457,6 +457,19 @@ int build_tables_serial(bposd_handle* h) {
     h->nlevels = nlev;
     return 0;
 }
+
+// LSD mode (lsd_kernel): H by column -- the checks of every bit, ascending -- next to the CSR copy every handle has
+int build_tables_lsd(bposd_handle* h) {
+    const int m = h->m, n = h->n, E = h->E;
+    std::vector<int> cp(n + 1, 0), cr(E), fill(n, 0);
+    for (int e = 0; e < E; ++e) cp[h->ci[e] + 1]++;
+    for (int i = 0; i < n; ++i) cp[i + 1] += cp[i];
+    for (int c = 0; c < m; ++c)
+        for (int e = h->rp[c]; e < h->rp[c + 1]; ++e) cr[cp[h->ci[e]] + fill[h->ci[e]]++] = c;
+    int rc;
+    if ((rc = upload_ints(h, h->d_lsd_cp, cp))) return rc;
+    return upload_ints(h, h->d_lsd_cr, cr);
+}
 // rank of a large code: one elimination of the zero syndrome on the device (the host routine is O(m^2 n / 64))
 int probe_rank_large(bposd_handle* h, const DecodeCall& call, int* rank) {
     DevBuf tmp;

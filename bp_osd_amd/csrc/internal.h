@@ -76,6 +76,12 @@ struct Lane {
     // and that call's batch size; -1: the lane's last call did not run in relay mode (bposd_relay_stats)
     DevBuf relay_sol, relay_leg, relay_wt;
     long long relay_B = -1;
+    // LSD mode (bposd_set_lsd): status | rounds | clusters | max_bits, [B] ints each, of the lane's last call and that call's
+    // batch size (-1: the lane's last call had no LSD stage); the list of the shots lsd_kernel handed on with their LLR rows
+    // [second-list slot][n]; the kernel's per-workgroup scratch; the second list's counters (lsd_kernel.hip.h)
+    DevBuf lsd_stat, lsd_list2, lsd_llr2, lsd_ws;
+    long long lsd_B = -1;
+    DevArray<int> d_lsd_counters;
 };
 
 // What bposd_last_timing reports: one record per kernel pair launched by the last call (one per chunk for a
@@ -165,6 +171,11 @@ struct bposd_handle {
     int relay_lane = 0;  // lane of the last relay launch (bposd_relay_stats with lane = -1)
     DevArray<double> d_relay_gammas;
     DevArray<int> d_relay_iters;
+    // LSD mode (bposd_set_lsd): lsd_kernel between the BP and the OSD stage; H by column (build_tables_lsd)
+    bool lsd_on = false;
+    int lsd_max_bits = 0, lsd_max_checks = 0;
+    int lsd_lane = 0;  // lane of the last LSD launch (bposd_lsd_stats with lane = -1)
+    DevArray<int> d_lsd_cp, d_lsd_cr;
 };
 
 // One BP + OSD launch pair: what it needs beyond the handle's per-code state.  The entry point that makes the call fills
@@ -217,6 +228,7 @@ int build_tables_local(bposd_handle* h);  // sets local_ok
 int build_tables_class(bposd_handle* h);  // sets class_ok
 int build_tables_large(bposd_handle* h, int DV, int MP);
 int build_tables_serial(bposd_handle* h);
+int build_tables_lsd(bposd_handle* h);  // d_lsd_cp, d_lsd_cr
 struct DegPair { int dc, dv; };
 bool pick_pair(int dc, int dv, DegPair* out);  // the compiled bp_kernel degree pair that covers (dc, dv)
 int gf2_rank_host(int m, int n, const std::vector<int>& rp, const std::vector<int>& ci);
@@ -247,6 +259,13 @@ int launch_osd(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& 
 int osd_words(int n);
 int launch_osd_large(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& P, long long B, int* d_rank_out);  // launch_osd_large.hip
 int osd_large_maxspan(bool cs);
+// ---- LSD mode (launch_lsd.hip: lsd_kernel, lsd_compact_kernel)
+int lsd_max_bits();
+int lsd_max_checks();
+size_t lsd_lds_need(int m, int n);
+int launch_lsd(bposd_handle* h, const DecodeCall& call, bposd::OsdParams& Q, long long B, bool osd_follows);
+int launch_lsd_compact(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& Q, const int* bp_list, const int* bp_counters,
+                       uint8_t* cmp_osd0, uint8_t* cmp_osdw, long long B);
 // ---- logical observables (launch_obs.hip: obs_kernel)
 int obs_max_k();
 int observable_table(const int32_t* indptr, const int32_t* indices, int k, int n, uint64_t* table, std::string* why);

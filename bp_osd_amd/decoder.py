@@ -70,7 +70,7 @@ class BpOsdDecoder:
     def __init__(self, pcm, error_rate=None, error_channel=None, max_iter=0, bp_method="minimum_sum",
                  ms_scaling_factor=1.0, schedule="parallel", omp_thread_count=1, osd_method="osd_0",
                  osd_order=0, input_vector_type="syndrome", channel_probs=None, device=0,
-                 sort_tie_policy=0, weight_fn=0, ps_clip=0.0, osd_e_bit_order=0, ps_math_form=0, relay=None, **kwargs):
+                 sort_tie_policy=0, weight_fn=0, ps_clip=0.0, osd_e_bit_order=0, ps_math_form=0, relay=None, lsd=None, **kwargs):
         if kwargs:
             raise TypeError(f"unexpected keyword arguments: {sorted(kwargs)}")
         sched = str(schedule).lower()
@@ -182,6 +182,9 @@ class BpOsdDecoder:
         self._relay = None
         if relay is not None:
             self.set_relay(relay)
+        self._lsd = None
+        if lsd is not None:
+            self.set_lsd(lsd)
 
     # ------------------------------------------------------------------ relay mode
     @property
@@ -221,6 +224,41 @@ class BpOsdDecoder:
         if B:
             _lib.check(self._lib, self._h, self._lib.bposd_relay_stats(self._h, lane, sol.ctypes.data, leg.ctypes.data, wt.ctypes.data, B))
         return {"solutions": sol, "best_leg": leg, "weight": wt}
+
+    # ------------------------------------------------------------------ LSD mode
+    @property
+    def lsd(self):
+        """The :class:`bp_osd_amd.LsdConfig` this decoder runs with, None when the mode is off."""
+        return self._lsd
+
+    def set_lsd(self, cfg):
+        """Switch LSD mode on with a :class:`bp_osd_amd.LsdConfig`, or off with None: every later decode call of this
+        decoder -- and of the engines built on it -- runs ``lsd_kernel`` over the shots BP leaves open and the OSD stage only
+        over the shots LSD does not solve (``bposd_set_lsd``).  Not together with relay mode.  Off, the decoder launches
+        what it launched before."""
+        from .lsd import LsdConfig
+        if cfg is None:
+            _lib.check(self._lib, self._h, self._lib.bposd_set_lsd(self._h, 0, 0, 0))
+            self._lsd = None
+            return
+        if not isinstance(cfg, LsdConfig):
+            raise TypeError("lsd must be an LsdConfig or None")
+        _lib.check(self._lib, self._h, self._lib.bposd_set_lsd(self._h, 1, cfg.max_cluster_bits, cfg.max_cluster_checks))
+        self._lsd = cfg
+
+    def lsd_stats(self, lane=None):
+        """dict(status, rounds, clusters, max_bits: int32 [B]) of the last call that ran on ``lane`` (default: the lane of the
+        last LSD launch) in LSD mode: per shot 0 solved, 1 a cluster outgrew a cap, 2 no bit left to select, -1 BP converged;
+        the rounds in which bits joined; the clusters and the most bits in one when the shot ended.  Waits for that lane.  A
+        host-pointer call that was cut into several chunks leaves each lane the words of its last chunk only."""
+        lane = -1 if lane is None else int(lane)  # (-1: the lane of the last LSD launch)
+        B = self._lib.bposd_lsd_stats(self._h, lane, None, None, None, None, 0)  # (no arrays: that call's batch size)
+        if B < 0:
+            _lib.check(self._lib, self._h, B)
+        out = {k: np.empty(B, np.int32) for k in ("status", "rounds", "clusters", "max_bits")}
+        if B:
+            _lib.check(self._lib, self._h, self._lib.bposd_lsd_stats(self._h, lane, *(v.ctypes.data for v in out.values()), B))
+        return out
 
     # ------------------------------------------------------------------ lifetime
     def __del__(self):

@@ -131,6 +131,13 @@ def _split_decode(r, decoder):
     return np.asarray(r), np.asarray(decoder.batch_converge), np.asarray(decoder.batch_iter)
 
 
+def _refuse_lsd(decoder_kwargs):
+    """LSD mode (``BpOsdDecoder(lsd=...)``) is not offered for windows; without this check the keyword would reach every
+    window's decoder unnoticed."""
+    if decoder_kwargs.get("lsd") is not None:
+        raise ValueError("windowed decoding takes no lsd= argument: LSD mode belongs to the unwindowed decoder (dem_decode_sim)")
+
+
 class _Model:
     """The validated model and its plan: what both classes below start from."""
 
@@ -224,6 +231,7 @@ class WindowedDemDecoder:
         from .decoder import BpOsdDecoder
 
         self._win = None
+        _refuse_lsd(decoder_kwargs)
         self._model = m = _Model(H, L, priors, detector_time, window, relay=decoder_kwargs.get("relay"))
         self.M, self.N, self.K = m.M, m.N, m.K
         self.plan = m.plan
@@ -334,6 +342,7 @@ class windowed_dem_decode_sim(DemSimBase):
                  decoder_factory=None, run_sim=True, harvest=0, **decoder_kwargs):
         self._check_engine(engine, decoder_factory, "decoders")
         self._win = self._sampler = None
+        _refuse_lsd(decoder_kwargs)
         self._model = m = _Model(H, L, priors, detector_time, window, relay=decoder_kwargs.get("relay"))
         self.M, self.N, self.K = m.M, m.N, m.K
         self._init_harvest(harvest)

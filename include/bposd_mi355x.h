@@ -380,6 +380,44 @@ int bposd_set_relay(bposd_handle *h, int32_t legs, const double *gammas, const i
 int bposd_relay_stats(bposd_handle *h, int32_t lane, int32_t *solutions, int32_t *best_leg, int64_t *weight, int64_t B);
 
 /*
+ * BP+LSD (localized statistics decoding of order 0, Hillmann et al., 2024): a mode of the handle.  With it on, every decode
+ * call (host, device and packed pointers, per-shot channels, observables, the DEM engine) runs lsd_kernel over the list of
+ * shots BP left open, in front of the OSD kernel, which then decodes only the shots LSD did not solve.  Per listed shot,
+ * with l its posterior LLRs as the OSD stage would get them:
+ *   Bit a comes before bit b iff l[a] < l[b], ties by ascending bit index (sort_tie_policy 0) or descending (1): the order
+ *   the OSD stage sorts columns in.  Every unsatisfied check starts as a cluster of its own without bits.  A cluster (checks
+ *   C, bits V, every check of a bit of V is in C) is valid iff s[C] lies in the column span of H[C, V].
+ *   A round: every cluster that is invalid at its start selects the first bit, in that order, among the bits that have a
+ *   check in C and are in no cluster.  All selected bits join at once (two clusters may select the same bit), each with all
+ *   its checks; clusters connected through a joined bit merge (valid ones may be swallowed), and the validity of every
+ *   cluster that grew or merged is evaluated afresh.  Rounds repeat until every cluster is valid.
+ *   Result: per cluster the solution of H[C, V] x = s[C] supported on the greedy column basis with V in the order above
+ *   (OSD-0 restricted to the cluster); every other bit 0.  The result does not depend on the order clusters are visited in.
+ *   status 0: solved -- the osdw and osd0 rows are that solution.  1: after some round a cluster held more than
+ *   max_cluster_bits bits or max_cluster_checks checks.  2: at the start of a round an invalid cluster had no bit to select
+ *   (the syndrome is outside the column space).  Shots of status 1 and 2 go to the OSD stage as BP left them; with
+ *   osd_method off they keep BP's decisions.  rounds = rounds in which bits joined, clusters and max_bits = the number of
+ *   clusters and the most bits in one of them when the shot ended.  Shots BP converged on: status -1, zeros.
+ * The OSD stage's rows of the shots it decodes are those of a handle without the mode.  It is this project's synchronous
+ * definition, not upstream ldpc's BpLsdDecoder, whose sequential growth order differs; higher LSD orders are not offered.
+ *
+ * bposd_set_lsd(on = 0) switches the mode off: the handle launches what it did before and allocates nothing more for the
+ * mode; what the mode has allocated (H by column, each lane's second list with its LLR rows, the four words per shot) stays
+ * with the handle until it is destroyed, ready for the next switch-on.  A handle that never had the mode on holds none of
+ * it.  BPOSD_ERR_INVALID
+ * (handle unchanged) for a cap outside [1, 256], the kernel's ceilings (4 rows per lane of a 64-lane wave, 4 words per
+ * row); BPOSD_ERR_UNSUPPORTED while relay mode is on (and bposd_set_relay while this mode is on), or if the cluster state of
+ * the handle's shape does not fit one CU's LDS (no shape a handle is created for: 4 bytes + 1 bit per check, 2 bits per
+ * bit and 12 864 bytes for one elimination -- 88 640 bytes at 16384 x 32767).
+ *
+ * bposd_lsd_stats: as bposd_relay_stats, for the four words per shot of the last call that ran on `lane` (-1: the lane of
+ * the last LSD launch); any array may be NULL, all NULL returns that call's batch size.
+ */
+int bposd_set_lsd(bposd_handle *h, int32_t on, int32_t max_cluster_bits, int32_t max_cluster_checks);
+int bposd_lsd_stats(bposd_handle *h, int32_t lane, int32_t *status, int32_t *rounds, int32_t *clusters, int32_t *max_bits,
+                    int64_t B);
+
+/*
  * Monte-Carlo engine: the device-resident form of the reference's harness loop
  * (/root/reference/src/bposd/css_decode_sim.py:174-365, 465-498).  One bposd_mc_run is one batch of shots:
  * sample the errors -> both syndromes -> the two decodes -> logical checks of the bp / osd0 / osdw outputs -> seven
