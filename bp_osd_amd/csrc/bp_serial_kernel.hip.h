@@ -13,119 +13,93 @@
 // Per bit (the CPU restatement under tests' checker directory walks the same steps): LLR := prior; for its checks top to
 // bottom: message := f(current bit->check messages of the check's OTHER edges); bit->check := LLR (prefix); LLR +=
 // message.  Decision = (LLR <= 0).  Then bottom to top: bit->check += suffix sum.  fp64, no contraction.
+// That per-edge "all other edges" check update and the level loop are this kernel's own; the queue take, the start of a shot,
+// the candidate-syndrome test and the results protocol are those of bp_csr.hip.h, shared with bp_anydeg_kernel and
+// bp_relay_kernel.  The launch passes no tail flag: the kernel could report its tail, the host path does not ask it to yet.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bp_kernel.hip.h"
+#include "bp_csr.hip.h"
 #include "portable_math.h"
 
 namespace bposd {
 
 constexpr int BPS_NT = 256;
 constexpr int BPS_MAXDV = 8;
+constexpr int BPS_PACKED = 0;  // launched with byte rows only (native_packed() in internal.h)
 
 struct BpSerialParams {
-    int m, n, E;
-    long long B;
-    int max_iter;
+    BpShotIo io;  // (io.tail_flag is null: this kernel's launch does not report its tail)
+    BpCsrGraph g;
     int bp_method;  // 0 product-sum, 1 min-sum
-    double ms_scaling;
-    double ps_clip;
-    int ps_form;  // product-sum evaluation order (portable_math.h: pm_ps_tanh_half)
-    int osd_enabled;
+    int ps_form;    // product-sum evaluation order (portable_math.h: pm_ps_tanh_half)
     int nlevels;
-    const uint8_t* __restrict__ synd;     // [B, m]
-    const double* __restrict__ llr0;      // [n]
-    const uint8_t* __restrict__ sel;      // [B, n] nullable
-    const double* __restrict__ llr0_alt;  // [n]
-    const double* __restrict__ llr0_rows; // [B, n] nullable: this shot's own priors (wins over sel)
-    const int* __restrict__ rp;           // CSR indptr [m + 1]
-    const int* __restrict__ ci;           // CSR indices [E]
-    const int* __restrict__ cp;           // CSC indptr [n + 1]
-    const int* __restrict__ ce;           // [E] CSR edge ids of a column, ascending row
-    const int* __restrict__ erow;         // [E] row of a CSR edge
-    const int* __restrict__ lvl_ptr;      // [nlevels + 1]
-    const int* __restrict__ lvl_bits;     // [n] bits by level, ascending inside a level
-    double* __restrict__ msg_ws;          // [gridDim.x][E] bit->check messages
-    double* __restrict__ llr_tmp;         // [gridDim.x][n]
-    uint8_t* __restrict__ out_bp;
-    uint8_t* __restrict__ out_osd0;
-    uint8_t* __restrict__ out_osdw;
-    uint8_t* __restrict__ out_conv;
-    int* __restrict__ out_iters;
-    double* __restrict__ out_llr;
-    double* __restrict__ llr_ws;
-    int* __restrict__ osd_list;
-    int* __restrict__ counters;
-    unsigned long long* __restrict__ iter_total;
+    const int* __restrict__ erow;      // [E] row of a CSR edge
+    const int* __restrict__ lvl_ptr;   // [nlevels + 1]
+    const int* __restrict__ lvl_bits;  // [n] bits by level, ascending inside a level
+    double* __restrict__ msg_ws;       // [gridDim.x][E] bit->check messages
+    double* __restrict__ llr_tmp;      // [gridDim.x][n]
 };
 
-__host__ __device__ inline size_t bp_serial_lds_bytes(int n) { return (size_t)((n + 15) & ~15) + 8 * 4; }
+__host__ __device__ inline size_t bp_serial_lds_bytes(int n) { return bp_csr_row_bytes(n) + 8 * 4; }
 
 __global__ __launch_bounds__(BPS_NT) void bp_serial_kernel(const BpSerialParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int m = P.m, n = P.n;
+    const BpShotIo& io = P.io;
+    const BpCsrGraph& g = P.g;
+    const int m = io.m, n = io.n;
     const int tid = threadIdx.x;
     unsigned char* dec = smem;
-    int* sh = reinterpret_cast<int*>(smem + ((n + 15) & ~15));
-    double* b2c = P.msg_ws + (size_t)blockIdx.x * P.E;
+    int* ctl = reinterpret_cast<int*>(smem + bp_csr_row_bytes(n));
+    double* b2c = P.msg_ws + (size_t)blockIdx.x * g.E;
     double* llrt = P.llr_tmp + (size_t)blockIdx.x * n;
 
     for (;;) {
-        if (tid == 0) sh[2] = atomicAdd(&P.counters[0], 1);
-        __syncthreads();
-        const long long s = sh[2];
-        if (s >= P.B) break;
-        const uint8_t* syn = P.synd + (size_t)s * m;
-        bool nz = false;
-        for (int c = tid; c < m; c += BPS_NT) nz |= (syn[c] & 1) != 0;
-        for (int i = tid; i < n; i += BPS_NT) {
-            const double l0 = bp_shot_prior(P, s, n, i);
-            for (int k = P.cp[i]; k < P.cp[i + 1]; ++k) b2c[P.ce[k]] = l0;
-            dec[i] = 0;
-            llrt[i] = l0;
-        }
-        const bool zero = !__syncthreads_or(nz);  // all-zero syndrome: zeros, converge = true, BP not run (A.2)
+        const long long s = bp_csr_take(io, nullptr, ctl, tid)  /* no tail report yet: launch_bp_serial */;
+        if (s < 0) break;
+        const auto synd_of = [&](int c) { return bp_synd_bit(io.synd, BPS_PACKED, s, m, c) ? 1u : 0u; };
+        const bool zero = !__syncthreads_or(bp_csr_start(io, g, s, BPS_PACKED, b2c, dec, llrt, nullptr, tid, BPS_NT));  // (A.2)
 
         int it_done = 0;
         bool conv = zero;
         if (!zero) {
 #pragma clang loop unroll(disable)
-            for (int it = 1; it <= P.max_iter; ++it) {
-                const double alpha = alpha_for_iteration(P.ms_scaling, it);
+            for (int it = 1; it <= io.max_iter; ++it) {
+                const double alpha = alpha_for_iteration(io.ms_scaling, it);
                 for (int lv = 0; lv < P.nlevels; ++lv) {
                     const int lo = P.lvl_ptr[lv], hi = P.lvl_ptr[lv + 1];
                     for (int q = lo + tid; q < hi; q += BPS_NT) {
                         const int i = P.lvl_bits[q];
-                        const double l0 = bp_shot_prior(P, s, n, i);
+                        const double l0 = bp_shot_prior(io, s, n, i);
                         double llr = l0;
                         double c2b[BPS_MAXDV];
-                        const int k0 = P.cp[i], deg = P.cp[i + 1] - k0;
+                        const int k0 = g.cp[i], deg = g.cp[i + 1] - k0;
                         for (int d = 0; d < deg; ++d) {
-                            const int e = P.ce[k0 + d], c = P.erow[e];
-                            const int g0 = P.rp[c], g1 = P.rp[c + 1];
+                            const int e = g.ce[k0 + d], c = P.erow[e];
+                            const int g0 = g.rp[c], g1 = g.rp[c + 1];
                             double msg;
                             if (P.bp_method == 0) {
                                 double prod = 1.0;
-                                for (int g = g0; g < g1; ++g)
-                                    if (g != e) prod *= pm_ps_tanh_half(b2c[g], P.ps_form);
-                                msg = ((syn[c] & 1) ? -1.0 : 1.0) * pm_ps_log_ratio(prod, P.ps_form);
-                                if (P.ps_clip > 0.0) {
-                                    if (msg > P.ps_clip) msg = P.ps_clip;
-                                    if (msg < -P.ps_clip) msg = -P.ps_clip;
+                                for (int j = g0; j < g1; ++j)
+                                    if (j != e) prod *= pm_ps_tanh_half(b2c[j], P.ps_form);
+                                msg = (synd_of(c) ? -1.0 : 1.0) * pm_ps_log_ratio(prod, P.ps_form);
+                                if (io.ps_clip > 0.0) {
+                                    if (msg > io.ps_clip) msg = io.ps_clip;
+                                    if (msg < -io.ps_clip) msg = -io.ps_clip;
                                 }
                             } else {
-                                int sgn = syn[c] & 1;
+                                const unsigned int sb = synd_of(c);  // (loaded here, needed behind the loop)
+                                int sgn = 0;
                                 double temp = __DBL_MAX__;
-                                for (int g = g0; g < g1; ++g) {
-                                    if (g == e) continue;
-                                    const double v = b2c[g];
+                                for (int j = g0; j < g1; ++j) {
+                                    if (j == e) continue;
+                                    const double v = b2c[j];
                                     const double a = fabs(v);
                                     if (a < temp) temp = a;
                                     if (v <= 0.0) sgn += 1;
                                 }
-                                const double message_sign = (sgn & 1) ? -1.0 : 1.0;
+                                const double message_sign = ((sgn + sb) & 1) ? -1.0 : 1.0;
                                 msg = alpha * message_sign * temp;
                             }
                             c2b[d] = msg;
@@ -136,7 +110,7 @@ __global__ __launch_bounds__(BPS_NT) void bp_serial_kernel(const BpSerialParams 
                         dec[i] = (llr <= 0.0) ? 1 : 0;
                         double temp = 0.0;  // suffix from the bottom of the column
                         for (int d = deg - 1; d >= 0; --d) {
-                            const int e = P.ce[k0 + d];
+                            const int e = g.ce[k0 + d];
                             b2c[e] += temp;
                             temp += c2b[d];
                         }
@@ -144,47 +118,14 @@ __global__ __launch_bounds__(BPS_NT) void bp_serial_kernel(const BpSerialParams 
                     __syncthreads();
                 }
                 // candidate syndrome of this sweep's decisions against the input syndrome
-                bool mis = false;
-                for (int c = tid; c < m; c += BPS_NT) {
-                    unsigned int par = 0u;
-                    for (int g = P.rp[c]; g < P.rp[c + 1]; ++g) par ^= dec[P.ci[g]];
-                    mis |= par != (unsigned int)(syn[c] & 1);
-                }
                 it_done = it;
-                if (!__syncthreads_or(mis)) {
+                if (!__syncthreads_or(bp_csr_mismatch(g, dec, m, tid, BPS_NT, synd_of))) {
                     conv = true;
                     break;
                 }
             }
         }
-
-        // ---- results (as the flooding kernels)
-        const bool to_osd = (!conv) && P.osd_enabled;
-        if (tid == 0) {
-            if (to_osd) {
-                const int slot = atomicAdd(&P.counters[1], 1);
-                P.osd_list[slot] = (int)s;
-                sh[3] = slot;
-            }
-            if (P.out_conv) P.out_conv[s] = conv ? 1 : 0;
-            if (P.out_iters) P.out_iters[s] = it_done;
-            if (it_done) atomicAdd(P.iter_total, (unsigned long long)it_done);
-        }
-        __syncthreads();
-        const int slot = to_osd ? sh[3] : 0;
-        for (int i = tid; i < n; i += BPS_NT) {
-            const size_t o = (size_t)s * n + i;
-            const uint8_t b = dec[i];
-            if (P.out_bp) P.out_bp[o] = b;
-            if (!to_osd) {
-                P.out_osdw[o] = b;
-                if (P.out_osd0) P.out_osd0[o] = b;
-            } else {
-                P.llr_ws[(size_t)slot * n + i] = llrt[i];
-            }
-            if (P.out_llr) P.out_llr[o] = llrt[i];
-        }
-        __syncthreads();
+        bp_csr_finish(io, s, BPS_PACKED, conv, it_done, dec, llrt, ctl, tid, BPS_NT);
     }
 }
 

@@ -703,11 +703,8 @@ int bposd_set_bp_variant(bposd_handle* h, int32_t variant) {
     if (!h) return BPOSD_ERR_INVALID;
     if (variant != 0 && variant != 1 && variant != 2 && variant != 4 && !(variant >= 16 && variant <= 26) && variant != 32 && variant != 63 && variant != 64)
         return fail(h, BPOSD_ERR_INVALID, "bp variant must be 0 (auto), 1, 2, 4 (LDS kernel shapes), 16 .. 26 (local-edge kernel), 32 (class kernel), 63 (HBM-resident min-sum with whole check records in the workspace) or 64 (any-degree kernel)");
-    if (variant == 64 && !h->d_cp) {  // the any-degree kernel as a second implementation for cross-checks: its CSC edge map
-        DeviceGuard dev_guard(h->device);
-        HIP_TRY(h, dev_guard.err);
-        int rc_any = sync_all_lanes(h);
-        if (!rc_any) rc_any = build_tables_serial(h);
+    if (variant == 64) {  // the any-degree kernel as a second implementation for cross-checks: its CSC edge map
+        const int rc_any = ensure_csc_tables(h);
         if (rc_any) return rc_any;
     }
     if (variant == 32 && !h->class_ok)
@@ -740,10 +737,8 @@ int bposd_set_relay(bposd_handle* h, int32_t legs, const double* gammas, const i
     DeviceGuard dev_guard(h->device);
     HIP_TRY(h, dev_guard.err);
     { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls may still read the old tables
-    if (!h->d_cp) {  // the CSC edge map the kernel walks (a handle of the tuned kernels has none yet)
-        const int rct = build_tables_serial(h);
-        if (rct) return rct;
-    }
+    // (ensure_csc_tables guards and drains again where it builds: bposd_set_bp_variant calls it bare; the sync above is for the uploads below)
+    { int rct = ensure_csc_tables(h); if (rct) return rct; }
     h->relay_legs = 0;  // (a failed upload leaves the mode off: the tables may be half written)
     HIP_TRY(h, h->d_relay_gammas.ensure(sizeof(double) * count));
     HIP_TRY(h, h->d_relay_iters.ensure(sizeof(int) * (size_t)legs));

@@ -457,6 +457,15 @@ int build_tables_serial(bposd_handle* h) {
     h->nlevels = nlev;
     return 0;
 }
+// The CSC edge map the CSR-edge kernels walk (any-degree as a forced variant, relay): a handle of the tuned kernels has none
+// until one of them is asked for.  Earlier calls may still be running on the handle's lanes.
+int ensure_csc_tables(bposd_handle* h) {
+    if (h->d_cp) return 0;
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    const int rc = sync_all_lanes(h);
+    return rc ? rc : build_tables_serial(h);
+}
 
 // LSD mode (lsd_kernel): H by column -- the checks of every bit, ascending -- next to the CSR copy every handle has
 int build_tables_lsd(bposd_handle* h) {

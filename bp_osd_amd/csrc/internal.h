@@ -2,8 +2,10 @@
 // bposd_capi.hip holds creation, the one BP + OSD launch pair every decode ends in (decode_device_impl) and the device-pointer
 // calls, decode_host.hip the host-pointer calls with their chunk plan, host_tables.hip table construction and the layout
 // searches; every launch_*.hip holds the instantiations and launch code of one kernel family, so that the families compile in
-// parallel (bp_osd_amd/build.py).  Every device block, page-locked block, stream and event below is held by an owning type of
-// owned.h: deleting a handle frees all of it, and a resource added to Lane, CallRecord or bposd_handle needs no line anywhere else.
+// parallel (bp_osd_amd/build.py).  The any-degree, serial and relay kernels (launch_bp_misc.hip, launch_bp_relay.hip) are three
+// schedules on one core, bp_csr.hip.h: its parameter blocks, and the queue, sweep and results helpers.
+// Every device block, page-locked block, stream and event below is held by an owning type of owned.h: deleting a handle frees
+// all of it, and a resource added to Lane, CallRecord or bposd_handle needs no line anywhere else.
 #pragma once
 #include "../../include/bposd_mi355x.h"
 #include "../../include/bposd_mi355x_debug.h"
@@ -18,6 +20,7 @@
 
 #include "local_park.h"      // park at drain of the local-edge BP kernel: counter block, record layout, the rule
 #include "bp_kernel.hip.h"   // BpParams, bp_lds_bytes (templates only: nothing is instantiated by including it)
+#include "bp_csr.hip.h"      // BpShotIo, BpCsrGraph of the CSR-edge kernels (inlined helpers only)
 #include "osd_kernel.hip.h"  // OsdParams
 #include "owned.h"           // DeviceGuard, DevBuf, DevArray, PinnedBuf, Stream, Event
 
@@ -213,6 +216,20 @@ inline void note_instance(int32_t (&dst)[6], int family, int a, int b, int c, in
     std::copy(v, v + 6, dst);
 }
 
+// The shot-level fields of a BP launch, from the BpParams decode_device_impl fills into the parameter block of the kernel
+// that runs: BpShotIo (bp_csr.hip.h) for the three CSR-edge kernels, BpClassParams, BpLargeParams.  By name: the tuned
+// kernels' structs keep the field order they were measured with.  The one list of these fields on the host side.
+template <class Dst>
+inline void copy_shot_fields(Dst& d, const bposd::BpParams& P) {
+    d.m = P.m; d.n = P.n; d.B = P.B; d.max_iter = P.max_iter; d.ms_scaling = P.ms_scaling; d.ps_clip = P.ps_clip;
+    d.osd_enabled = P.osd_enabled; d.packed_io = P.packed_io;
+    d.synd = P.synd; d.llr0 = P.llr0; d.sel = P.sel; d.llr0_alt = P.llr0_alt; d.llr0_rows = P.llr0_rows;
+    d.out_bp = P.out_bp; d.out_osd0 = P.out_osd0; d.out_osdw = P.out_osdw; d.out_conv = P.out_conv; d.out_iters = P.out_iters;
+    d.out_llr = P.out_llr; d.llr_ws = P.llr_ws; d.osd_list = P.osd_list; d.counters = P.counters; d.iter_total = P.iter_total;
+    d.tail_flag = P.tail_flag;
+}
+inline bposd::BpCsrGraph csr_graph(const bposd_handle* h) { return bposd::BpCsrGraph{h->E, h->d_rp, h->d_ci, h->d_cp, h->d_ce}; }
+
 int sync_all_lanes(bposd_handle* h);
 int set_max_lds(bposd_handle* h, const void* kernel, size_t lds);
 int cached_occupancy(bposd_handle* h, const void* kernel, int nt, size_t lds, int* out);
@@ -228,6 +245,7 @@ int build_tables_local(bposd_handle* h);  // sets local_ok
 int build_tables_class(bposd_handle* h);  // sets class_ok
 int build_tables_large(bposd_handle* h, int DV, int MP);
 int build_tables_serial(bposd_handle* h);
+int ensure_csc_tables(bposd_handle* h);  // d_cp / d_ce of the CSR-edge kernels, built (behind the calls in flight) if the handle has none
 int build_tables_lsd(bposd_handle* h);  // d_lsd_cp, d_lsd_cr
 struct DegPair { int dc, dv; };
 bool pick_pair(int dc, int dv, DegPair* out);  // the compiled bp_kernel degree pair that covers (dc, dv)

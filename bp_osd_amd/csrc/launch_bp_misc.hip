@@ -48,65 +48,50 @@ static int launch_bp_large_t(bposd_handle* h, const DecodeCall& call, BpLargePar
 
 int launch_bp_large(bposd_handle* h, const DecodeCall& call, const BpParams& G) {
     BpLargeParams P{};
-    P.m = G.m; P.n = G.n; P.B = G.B; P.max_iter = G.max_iter; P.ms_scaling = G.ms_scaling; P.ps_clip = G.ps_clip; P.ps_form = h->cfg.ps_math_form;
-    P.osd_enabled = G.osd_enabled; P.mp = h->tab_mp;
-    P.synd = G.synd; P.llr0 = G.llr0; P.sel = G.sel; P.llr0_alt = G.llr0_alt; P.llr0_rows = G.llr0_rows;
+    copy_shot_fields(P, G);
+    P.ps_form = h->cfg.ps_math_form; P.mp = h->tab_mp;
     P.chk_deg = h->d_chk_deg; P.var_deg = h->d_var_deg; P.var_pos = h->d_var_pos; P.var_ck = h->d_var_ck;
-    P.out_bp = G.out_bp; P.out_osd0 = G.out_osd0; P.out_osdw = G.out_osdw; P.out_conv = G.out_conv;
-    P.out_iters = G.out_iters; P.out_llr = G.out_llr; P.llr_ws = G.llr_ws; P.osd_list = G.osd_list;
-    P.counters = G.counters; P.iter_total = G.iter_total; P.tail_flag = G.tail_flag; P.packed_io = G.packed_io;
     if (h->dc_max <= 12 && h->dv_max <= 6) return launch_bp_large_t<12, 6>(h, call, P);
     if (h->dc_max <= 16 && h->dv_max <= 8) return launch_bp_large_t<16, 8>(h, call, P);
     return fail(h, BPOSD_ERR_UNSUPPORTED, "check degree %d / bit degree %d exceed the built kernels (16 / 8)", h->dc_max, h->dv_max);
 }
 
-int launch_bp_serial(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
-    BpSerialParams S{};
-    S.m = P.m; S.n = P.n; S.E = h->E; S.B = P.B; S.max_iter = P.max_iter; S.bp_method = h->cfg.bp_method;
-    S.ms_scaling = P.ms_scaling; S.ps_clip = P.ps_clip; S.ps_form = h->cfg.ps_math_form; S.osd_enabled = P.osd_enabled; S.nlevels = h->nlevels;
-    S.synd = P.synd; S.llr0 = P.llr0; S.sel = P.sel; S.llr0_alt = P.llr0_alt; S.llr0_rows = P.llr0_rows;
-    S.rp = h->d_rp; S.ci = h->d_ci; S.cp = h->d_cp; S.ce = h->d_ce; S.erow = h->d_erow;
-    S.lvl_ptr = h->d_lvl_ptr; S.lvl_bits = h->d_lvl_bits;
-    S.out_bp = P.out_bp; S.out_osd0 = P.out_osd0; S.out_osdw = P.out_osdw; S.out_conv = P.out_conv; S.out_iters = P.out_iters;
-    S.out_llr = P.out_llr; S.llr_ws = P.llr_ws; S.osd_list = P.osd_list; S.counters = P.counters; S.iter_total = P.iter_total;
-    const size_t lds = bp_serial_lds_bytes(h->n);
+// ------------------------------------------------------------------ the CSR-edge kernels with their messages in HBM (bp_csr.hip.h)
+// Launch of one of them.  One persistent workgroup per shot with `lds` bytes of LDS and `msg_doubles` doubles of message
+// workspace: workgroups per CU (what LDS admits, at most 8), the grid, and the lane's message and LLR workspaces sized for it.
+template <class Params>
+static int launch_csr(bposd_handle* h, const DecodeCall& call, void (*kernel)(Params), Params& K, int nt, size_t lds, size_t msg_doubles, int family) {
     const int wg_per_cu = std::max<int>(1, std::min<size_t>(8, h->lds_per_cu / std::max<size_t>(lds, 1)));
-    const long long grid = std::max<long long>(1, std::min<long long>(P.B, (long long)h->num_cu * wg_per_cu));
+    const long long grid = std::max<long long>(1, std::min<long long>(K.io.B, (long long)h->num_cu * wg_per_cu));
     int rc;
-    if ((rc = ensure_lanes(h, &Lane::bpl_msg, sizeof(double) * (size_t)grid * h->E))) return rc;
+    if ((rc = ensure_lanes(h, &Lane::bpl_msg, sizeof(double) * (size_t)grid * msg_doubles))) return rc;
     if ((rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n))) return rc;
-    S.msg_ws = (double*)call.lane->bpl_msg.p;
-    S.llr_tmp = (double*)call.lane->bpl_llr.p;
-    { int rc_lds = set_max_lds(h, (const void*)bp_serial_kernel, lds); if (rc_lds) return rc_lds; }
-    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_SERIAL, 0, 0, 0, 0, false);
-    hipLaunchKernelGGL(bp_serial_kernel, dim3((unsigned)grid), dim3(BPS_NT), lds, call.lane->stream, S);
+    K.msg_ws = (double*)call.lane->bpl_msg.p;
+    K.llr_tmp = (double*)call.lane->bpl_llr.p;
+    if ((rc = set_max_lds(h, (const void*)kernel, lds))) return rc;
+    note_instance(h->last_bp_inst, family, 0, 0, 0, 0, false);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nt), lds, call.lane->stream, K);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
 
-// ------------------------------------------------------------------ any-degree BP (check degree > 16 or bit degree > 8)
+int launch_bp_serial(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
+    BpSerialParams S{};
+    copy_shot_fields(S.io, P);
+    S.io.tail_flag = nullptr;  // the serial-schedule kernel does not report its tail (decode_host.hip gates no chunk on it)
+    S.g = csr_graph(h);
+    S.bp_method = h->cfg.bp_method; S.ps_form = h->cfg.ps_math_form; S.nlevels = h->nlevels;
+    S.erow = h->d_erow; S.lvl_ptr = h->d_lvl_ptr; S.lvl_bits = h->d_lvl_bits;
+    return launch_csr(h, call, bp_serial_kernel, S, BPS_NT, bp_serial_lds_bytes(h->n), h->E, BPOSD_BP_KERNEL_SERIAL);
+}
+
+// any-degree BP (check degree > 16 or bit degree > 8)
 int launch_bp_any(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
     BpAnyParams A{};
-    A.m = P.m; A.n = P.n; A.E = h->E; A.B = P.B; A.max_iter = P.max_iter; A.bp_method = h->cfg.bp_method;
-    A.ms_scaling = P.ms_scaling; A.ps_clip = P.ps_clip; A.ps_form = h->cfg.ps_math_form; A.osd_enabled = P.osd_enabled;
-    A.synd = P.synd; A.llr0 = P.llr0; A.sel = P.sel; A.llr0_alt = P.llr0_alt; A.llr0_rows = P.llr0_rows;
-    A.rp = h->d_rp; A.ci = h->d_ci; A.cp = h->d_cp; A.ce = h->d_ce;
-    A.out_bp = P.out_bp; A.out_osd0 = P.out_osd0; A.out_osdw = P.out_osdw; A.out_conv = P.out_conv; A.out_iters = P.out_iters;
-    A.out_llr = P.out_llr; A.llr_ws = P.llr_ws; A.osd_list = P.osd_list; A.counters = P.counters; A.iter_total = P.iter_total;
-    A.tail_flag = P.tail_flag;
-    const size_t lds = bp_anydeg_lds_bytes(h->n);
-    const int wg_per_cu = std::max<int>(1, std::min<size_t>(8, h->lds_per_cu / std::max<size_t>(lds, 1)));
-    const long long grid = std::max<long long>(1, std::min<long long>(P.B, (long long)h->num_cu * wg_per_cu));
-    int rc;
-    if ((rc = ensure_lanes(h, &Lane::bpl_msg, sizeof(double) * (size_t)grid * 3 * h->E))) return rc;
-    if ((rc = ensure_lanes(h, &Lane::bpl_llr, sizeof(double) * (size_t)grid * h->n))) return rc;
-    A.msg_ws = (double*)call.lane->bpl_msg.p;
-    A.llr_tmp = (double*)call.lane->bpl_llr.p;
-    { int rc_lds = set_max_lds(h, (const void*)bp_anydeg_kernel, lds); if (rc_lds) return rc_lds; }
-    note_instance(h->last_bp_inst, BPOSD_BP_KERNEL_ANYDEG, 0, 0, 0, 0, false);
-    hipLaunchKernelGGL(bp_anydeg_kernel, dim3((unsigned)grid), dim3(BPA_NT), lds, call.lane->stream, A);
-    HIP_TRY(h, hipGetLastError());
-    return 0;
+    copy_shot_fields(A.io, P);
+    A.g = csr_graph(h);
+    A.bp_method = h->cfg.bp_method; A.ps_form = h->cfg.ps_math_form;
+    return launch_csr(h, call, bp_anydeg_kernel, A, BPA_NT, bp_anydeg_lds_bytes(h->n), 3 * (size_t)h->E, BPOSD_BP_KERNEL_ANYDEG);
 }
 
 int bp_serial_max_dv() { return BPS_MAXDV; }

@@ -12,14 +12,10 @@ namespace bposd_host {
 int launch_bp_relay(bposd_handle* h, const DecodeCall& call, const BpParams& P) {
     Lane& L = *call.lane;
     BpRelayParams A{};
-    A.m = P.m; A.n = P.n; A.E = h->E; A.B = P.B; A.ms_scaling = P.ms_scaling; A.osd_enabled = P.osd_enabled; A.packed_io = P.packed_io;
+    copy_shot_fields(A.io, P);
+    A.g = csr_graph(h);
     A.legs = h->relay_legs; A.stop_after = h->relay_stop; A.leg_init = h->relay_init;
     A.gammas = h->d_relay_gammas; A.leg_iters = h->d_relay_iters;
-    A.synd = P.synd; A.llr0 = P.llr0; A.sel = P.sel; A.llr0_alt = P.llr0_alt; A.llr0_rows = P.llr0_rows;
-    A.rp = h->d_rp; A.ci = h->d_ci; A.cp = h->d_cp; A.ce = h->d_ce;
-    A.out_bp = P.out_bp; A.out_osd0 = P.out_osd0; A.out_osdw = P.out_osdw; A.out_conv = P.out_conv; A.out_iters = P.out_iters;
-    A.out_llr = P.out_llr; A.llr_ws = P.llr_ws; A.osd_list = P.osd_list; A.counters = P.counters; A.iter_total = P.iter_total;
-    A.tail_flag = P.tail_flag;
     int rc;
     for (int l = 0; l < h->nlanes; ++l)  // a block that grows loses what it held
         if (h->lanes[l].relay_wt.bytes < sizeof(long long) * (size_t)P.B) h->lanes[l].relay_B = -1;
