@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "bposd_relay_stats",
     "bposd_set_lsd",
     "bposd_lsd_stats",
+    "bposd_set_lsd_order",
+    "bposd_lsd_order_stats",
     "bposd_set_osd_variant",
     "bposd_last_osd_kernel",
     "bposd_mc_create",
@@ -113,6 +115,7 @@ DEBUG_SYMBOLS = (
     "bposd_debug_last_pair_key",
     "bposd_debug_set_park",
     "bposd_debug_last_parked",
+    "bposd_debug_lsd_launches",
     "bposd_debug_obs_timing",
     "bposd_debug_dem_timing",
     "bposd_debug_dem_harvest",
@@ -369,6 +372,12 @@ def load():
     lib.bposd_set_lsd.restype = C.c_int
     lib.bposd_lsd_stats.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int64]
     lib.bposd_lsd_stats.restype = C.c_int
+    lib.bposd_set_lsd_order.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.bposd_set_lsd_order.restype = C.c_int
+    lib.bposd_lsd_order_stats.argtypes = [vp, C.c_int32, vp, vp, C.c_int64]
+    lib.bposd_lsd_order_stats.restype = C.c_int
+    lib.bposd_debug_lsd_launches.argtypes = [vp, vp]
+    lib.bposd_debug_lsd_launches.restype = C.c_int
     lib.bposd_last_error.argtypes = [vp]
     lib.bposd_last_error.restype = C.c_char_p
     lib.bposd_destroy.argtypes = [vp]

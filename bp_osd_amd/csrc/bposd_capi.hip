@@ -180,9 +180,12 @@ int launch_unpack(bposd_handle* h, hipStream_t st, const unsigned long long* d_w
 }
 
 // ---- what the decode entry points of this file and of decode_host.hip share (declared in internal.h)
-// Does this handle's OSD stage rank candidates by the channel's weights (else per-shot weight rows are never read)?
-bool osd_weighs_candidates(const bposd_handle* h) {
-    return h->cfg.osd_method >= BPOSD_OSD_E && h->cfg.osd_order > 0 && h->cfg.weight_fn == 0;
+// Does a stage behind BP -- the OSD stage, or the sweep of LSD mode inside the clusters -- rank candidates by the channel's
+// weights (else per-shot weight rows are never read)?
+bool stage_weighs_candidates(const bposd_handle* h) {
+    if (h->cfg.weight_fn != 0) return false;
+    if (h->lsd_on && h->lsd_method != BPOSD_LSD_0) return true;  // the sweep inside the clusters weighs like the OSD stage
+    return h->cfg.osd_method >= BPOSD_OSD_E && h->cfg.osd_order > 0;
 }
 
 // What every decode entry point checks before anything is enqueued (B == 0 is a valid call that does nothing).
@@ -783,9 +786,9 @@ int bposd_set_lsd(bposd_handle* h, int32_t on, int32_t max_cluster_bits, int32_t
     // check or a slot of a list of checks -- is below 0x8000 (a handle is created for m <= 16384)
     if (h->m > 0x8000)
         return fail(h, BPOSD_ERR_UNSUPPORTED, "LSD mode: m = %d checks do not fit lsd_kernel's 15-bit check indices", h->m);
-    if (lsd_lds_need(h->m, h->n) > h->lds_per_cu)
+    if (lsd_lds_need(h->m, h->n, lsd_higher_order(h)) > h->lds_per_cu)
         return fail(h, BPOSD_ERR_UNSUPPORTED, "LSD mode: the cluster state of m = %d checks and n = %d bits needs %zu bytes of LDS, the CU has %zu",
-                    h->m, h->n, lsd_lds_need(h->m, h->n), h->lds_per_cu);
+                    h->m, h->n, lsd_lds_need(h->m, h->n, lsd_higher_order(h)), h->lds_per_cu);
     DeviceGuard dev_guard(h->device);
     HIP_TRY(h, dev_guard.err);
     { int rcs = sync_all_lanes(h); if (rcs) return rcs; }  // earlier calls run without the mode
@@ -796,6 +799,58 @@ int bposd_set_lsd(bposd_handle* h, int32_t on, int32_t max_cluster_bits, int32_t
     h->lsd_max_bits = max_cluster_bits;
     h->lsd_max_checks = max_cluster_checks;
     h->lsd_on = true;
+    return BPOSD_OK;
+}
+
+int bposd_set_lsd_order(bposd_handle* h, int32_t method, int32_t order, int32_t min_free_bits, int32_t grow_bits_limit) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (method != BPOSD_LSD_0 && method != BPOSD_LSD_CS && method != BPOSD_LSD_E)
+        return fail(h, BPOSD_ERR_INVALID, "lsd: method = %d must be BPOSD_LSD_0, BPOSD_LSD_CS or BPOSD_LSD_E", method);
+    const int lo = method == BPOSD_LSD_0 ? 0 : 1, hi = method == BPOSD_LSD_0 ? 0 : method == BPOSD_LSD_CS ? 64 : 10;
+    if (order < lo || order > hi)
+        return fail(h, BPOSD_ERR_INVALID, "lsd: order = %d must be in [%d, %d] with method %s", order, lo, hi,
+                    method == BPOSD_LSD_0 ? "lsd_0" : method == BPOSD_LSD_CS ? "lsd_cs" : "lsd_e");
+    if (min_free_bits < 0 || min_free_bits > 64) return fail(h, BPOSD_ERR_INVALID, "lsd: min_free_bits = %d must be in [0, 64]", min_free_bits);
+    if (grow_bits_limit < 1 || grow_bits_limit > lsd_max_bits())
+        return fail(h, BPOSD_ERR_INVALID, "lsd: grow_bits_limit = %d must be in [1, %d] (the ceiling of lsd_kernel)", grow_bits_limit, lsd_max_bits());
+    const bool ho = method != BPOSD_LSD_0 || min_free_bits > 0;
+    if (h->lsd_on && lsd_lds_need(h->m, h->n, ho) > h->lds_per_cu)
+        return fail(h, BPOSD_ERR_UNSUPPORTED, "LSD mode: the cluster state of m = %d checks and n = %d bits with a sweep needs %zu bytes of LDS, the CU has %zu",
+                    h->m, h->n, lsd_lds_need(h->m, h->n, ho), h->lds_per_cu);
+    // (read on the host when a call is enqueued: the calls in flight keep what they were launched with)
+    h->lsd_method = method;
+    h->lsd_order = order;
+    h->lsd_min_free = min_free_bits;
+    h->lsd_grow_limit = grow_bits_limit;
+    return BPOSD_OK;
+}
+
+int bposd_lsd_order_stats(bposd_handle* h, int32_t lane, int32_t* max_free, int32_t* improved, int64_t B) {
+    if (!h) return BPOSD_ERR_INVALID;
+    if (lane == -1) lane = h->lsd_lane;
+    if (lane < 0 || lane >= h->nlanes) return fail(h, BPOSD_ERR_INVALID, "lane %d out of range", lane);
+    Lane& L = h->lanes[lane];
+    if (L.lsd_B < 0) return fail(h, BPOSD_ERR_INVALID, "the last call on lane %d did not run in LSD mode", lane);
+    if (!max_free && !improved) return (int)std::min<long long>(L.lsd_B, INT_MAX);
+    if (B != L.lsd_B) return fail(h, BPOSD_ERR_INVALID, "the last call on lane %d decoded %lld syndromes, not %lld", lane, L.lsd_B, (long long)B);
+    int32_t* const dst[2] = {max_free, improved};
+    if (L.lsd_words < 6) {  // the LSD-0 instance keeps four words: no free columns counted, no sweep
+        for (int k = 0; k < 2; ++k)
+            if (dst[k]) std::fill(dst[k], dst[k] + B, 0);
+        return BPOSD_OK;
+    }
+    DeviceGuard dev_guard(h->device);
+    HIP_TRY(h, dev_guard.err);
+    HIP_TRY(h, hipStreamSynchronize(L.stream));
+    for (int k = 0; k < 2; ++k)
+        if (dst[k]) HIP_TRY(h, hipMemcpy(dst[k], (const int*)L.lsd_stat.p + (size_t)(4 + k) * B, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost));
+    return BPOSD_OK;
+}
+
+int bposd_debug_lsd_launches(bposd_handle* h, int64_t launches[2]) {
+    if (!h || !launches) return BPOSD_ERR_INVALID;
+    launches[0] = h->lsd_launches[0];
+    launches[1] = h->lsd_launches[1];
     return BPOSD_OK;
 }
 
@@ -976,8 +1031,9 @@ int bposd_decode_batch_rows_device(bposd_handle* h, const uint8_t* d_synd, int64
                                    uint8_t* d_conv, int32_t* d_iters, double* d_llr) {
     if (!h) return BPOSD_ERR_INVALID;
     if (!d_prior_llr_rows) return fail(h, BPOSD_ERR_INVALID, "prior_llr_rows is required");
-    const bool weighs = h->cfg.osd_method != BPOSD_OSD_OFF && osd_weighs_candidates(h);
-    if (weighs && !d_cost_rows) return fail(h, BPOSD_ERR_INVALID, "cost_rows is required: this handle's OSD stage weighs its candidates with the channel");
+    const bool weighs = stage_weighs_candidates(h);
+    if (weighs && !d_cost_rows) return fail(h, BPOSD_ERR_INVALID, "cost_rows is required: this handle's %s weighs its candidates with the channel",
+                                                  h->lsd_on && h->lsd_method != BPOSD_LSD_0 ? "LSD sweep" : "OSD stage");
     if (const int rc = check_batch(h, B, d_synd, d_osdw); rc || B == 0) return rc;
     IoPtrs io{d_synd, nullptr, d_osdw, d_osd0, d_bp, d_conv, d_iters, d_llr};
     io.llr0_rows = d_prior_llr_rows;

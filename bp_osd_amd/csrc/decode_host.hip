@@ -348,7 +348,7 @@ int decode_host_impl(bposd_handle* h, const IoPtrs& host, int64_t B, bool packed
     hc.bp_only = bp_only;
     hc.osd_on = (h->cfg.osd_method != BPOSD_OSD_OFF || h->lsd_on) && !bp_only;  // (LSD mode rewrites rows behind BP like an OSD stage)
     hc.prob_rows = prob_rows;
-    hc.rows_cost = prob_rows && hc.osd_on && osd_weighs_candidates(h);
+    hc.rows_cost = prob_rows && hc.osd_on && stage_weighs_candidates(h);
     hc.rsn = row_bytes(h->n, packed);
     hc.rsm = row_bytes(h->m, packed);
     if (const SmallLayout small = small_layout(h, host, hc); !packed && small.total <= (size_t)1 << 20)

@@ -84,6 +84,7 @@ struct Lane {
     // [second-list slot][n]; the kernel's per-workgroup scratch; the second list's counters (lsd_kernel.hip.h)
     DevBuf lsd_stat, lsd_list2, lsd_llr2, lsd_ws;
     long long lsd_B = -1;
+    int lsd_words = 4;  // words per shot of that call: 4 (lsd_kernel<false>) or 6 (lsd_kernel<true>: + max_free | improved)
     DevArray<int> d_lsd_counters;
 };
 
@@ -177,6 +178,9 @@ struct bposd_handle {
     // LSD mode (bposd_set_lsd): lsd_kernel between the BP and the OSD stage; H by column (build_tables_lsd)
     bool lsd_on = false;
     int lsd_max_bits = 0, lsd_max_checks = 0;
+    // bposd_set_lsd_order: 0 lsd_0, 1 lsd_cs, 2 lsd_e; a sweep or growth for free bits selects lsd_kernel<true>
+    int lsd_method = 0, lsd_order = 0, lsd_min_free = 0, lsd_grow_limit = 256;
+    long long lsd_launches[2] = {0, 0};  // launches of lsd_kernel<false> / <true> (bposd_debug_lsd_launches)
     int lsd_lane = 0;  // lane of the last LSD launch (bposd_lsd_stats with lane = -1)
     DevArray<int> d_lsd_cp, d_lsd_cr;
 };
@@ -280,7 +284,8 @@ int osd_large_maxspan(bool cs);
 // ---- LSD mode (launch_lsd.hip: lsd_kernel, lsd_compact_kernel)
 int lsd_max_bits();
 int lsd_max_checks();
-size_t lsd_lds_need(int m, int n);
+size_t lsd_lds_need(int m, int n, bool higher_order);
+bool lsd_higher_order(const bposd_handle* h);  // does the handle's LSD mode run lsd_kernel<true>?
 int launch_lsd(bposd_handle* h, const DecodeCall& call, bposd::OsdParams& Q, long long B, bool osd_follows);
 int launch_lsd_compact(bposd_handle* h, const DecodeCall& call, const bposd::OsdParams& Q, const int* bp_list, const int* bp_counters,
                        uint8_t* cmp_osd0, uint8_t* cmp_osdw, long long B);
@@ -304,7 +309,7 @@ struct IoPtrs {
     int32_t* iters = nullptr;
     double* llr = nullptr;
     // a channel of its own for every syndrome (bposd_decode_batch_rows*): rows [B, n] of prior LLRs and of OSD-W weights
-    // as bposd_channel_tables makes them; cost_rows is null where OSD does not weigh candidates
+    // as bposd_channel_tables makes them; cost_rows is null where neither the OSD stage nor an LSD sweep weighs candidates
     const double* llr0_rows = nullptr;
     const double* cost_rows = nullptr;
 };
@@ -314,7 +319,7 @@ struct ObsOut {
     uint8_t* conv = nullptr;
     int32_t* iters = nullptr;
 };
-bool osd_weighs_candidates(const bposd_handle* h);  // does the OSD stage rank candidates by the channel's weights?
+bool stage_weighs_candidates(const bposd_handle* h);  // does the OSD stage, or the sweep of LSD mode, rank candidates by the channel's weights?
 int check_batch(bposd_handle* h, int64_t B, const void* synd, const void* osdw);  // every decode entry point, before anything is enqueued
 int check_observables(bposd_handle* h);
 DecodeCall take_next_lane(bposd_handle* h);  // a stand-alone call on the handle's next lane, record 0 of a new "last call"

@@ -1,4 +1,4 @@
-// lsd_kernel.hip.h -- LSD-0: localized statistics decoding of the shots BP left open.
+// lsd_kernel.hip.h -- LSD: localized statistics decoding of the shots BP left open.
 //
 // The definition is the synchronous one of bp_osd_amd/lsd.py (lsd_decode_reference) and of the comment at bposd_set_lsd:
 // every unsatisfied check starts as a cluster; in a round every invalid cluster selects the first free bit in the OSD
@@ -19,6 +19,16 @@
 // A cluster's members are not kept: its bits are the joined bits whose first check lies in it, its checks the checks of
 // those bits (every check of a cluster with a bit is next to one of its bits: a seed check selected a neighbour).
 // Loop bounds: at most n rounds (every round joins a bit), every inner loop over a count fixed before it starts.
+//
+// lsd_kernel<false> is LSD-0.  lsd_kernel<true> (method lsd_cs / lsd_e, or min_free_bits > 0) adds, in `if constexpr (HO)`
+// blocks only: a valid cluster with fewer than min_free free columns and fewer than grow_limit bits stays on the inv / sel
+// list and selects like an invalid one (with nothing to select it is finished); a cluster that finishes is swept while its
+// reduced rows still sit in LDS -- one candidate per lane, 64 at a time, every lane walking the cluster's bits in ascending
+// bit index (perm, built by counting as cbs is) and adding the bit's cost (1.0 where the OSD stage counts bits, so one loop
+// serves both weights) where its candidate sets the bit; the lightest (weight, candidate index) over lanes and rounds goes
+// into a second bitmap xw.  A cluster that merges later is eliminated and swept again over all its bits, so at the end xw
+// holds the final clusters' rows.  LDS of the sweep: prow[p] the pivot row of column position p (LSD_NONE: a free column),
+// fcol the free column positions in order, perm; the costs by column position take the place of the sort keys (ck).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,14 +69,26 @@ struct LsdParams {
     int* __restrict__ st_rounds;
     int* __restrict__ st_clusters;
     int* __restrict__ st_maxbits;
-    int* ws;                            // [gridDim.x][2 m + n]
+    int* ws;                            // [gridDim.x][lsd_ws_ints]
+    // ---- lsd_kernel<true> only
+    int method, order;                  // 0 lsd_0, 1 lsd_cs, 2 lsd_e
+    int min_free, grow_limit;
+    int e_msb_first;                    // the handle's osd_e_bit_order
+    const double* __restrict__ cost;       // as OsdParams: null = the OSD stage counts bits
+    const uint8_t* __restrict__ sel;
+    const double* __restrict__ cost_alt;
+    const double* __restrict__ cost_rows;
+    int* __restrict__ st_maxfree;       // [B] each
+    int* __restrict__ st_improved;
 };
 
-__host__ __device__ inline size_t lsd_ws_ints(int m, int n) { return 2 * (size_t)m + (size_t)n; }
+// inv | sel | jb, and for lsd_kernel<true> the free columns of every finished cluster at its root check
+__host__ __device__ inline size_t lsd_ws_ints(int m, int n, bool ho = false) { return (ho ? 3 : 2) * (size_t)m + (size_t)n; }
 __host__ __device__ inline size_t lsd_pad8(size_t x) { return (x + 7) & ~(size_t)7; }
 // uf | lrow | taken | xsol | syn | rows | keys | cb | cbs | cc | pivcol | rsy | used | 16 control ints
-__host__ __device__ inline size_t lsd_lds_bytes(int m, int n) {
-    return 2 * lsd_pad8(2 * (size_t)m) + lsd_pad8(4 * (size_t)((n + 31) / 32)) + 8 * (size_t)((n + 63) / 64) + lsd_pad8(4 * (size_t)((m + 31) / 32)) +
+// lsd_kernel<true> appends: xw | prow | fcol | perm
+__host__ __device__ inline size_t lsd_lds_bytes(int m, int n, bool ho = false) {
+    return (ho ? 8 * (size_t)((n + 63) / 64) + 3 * 2 * (size_t)LSD_MAXB : 0) + 2 * lsd_pad8(2 * (size_t)m) + lsd_pad8(4 * (size_t)((n + 31) / 32)) + 8 * (size_t)((n + 63) / 64) + lsd_pad8(4 * (size_t)((m + 31) / 32)) +
            8 * (size_t)LSD_MAXC * LSD_WPR + 8 * (size_t)LSD_MAXB + 3 * 2 * (size_t)LSD_MAXB + 2 * (size_t)LSD_MAXC + 2 * (size_t)LSD_MAXC + 64;
 }
 
@@ -90,6 +112,49 @@ __device__ __forceinline__ int lsd_lanes_below(unsigned long long bal, int lane)
     return __popcll(bal & ((1ull << lane) - 1ull));
 }
 
+// the free column positions candidate c sets, as a mask over column positions (the enumeration of the OSD stage: osd_kernel.hip.h)
+__device__ __forceinline__ void lsd_candidate(int c, int method, int w, int kp, int msb, const unsigned short* fcol, unsigned long long F[LSD_WPR]) {
+#pragma unroll
+    for (int x = 0; x < LSD_WPR; ++x) F[x] = 0ull;
+    int t0 = -1, t1 = -1;
+    unsigned int pat = 0u;
+    if (c < 0) return;
+    if (method == 2) pat = (unsigned int)c + 1u;
+    else if (c < kp) t0 = c;
+    else {  // pairs a < b < w, a outer
+        int q = c - kp, a = 0;
+        while (q >= w - 1 - a) { q -= w - 1 - a; ++a; }
+        t0 = a;
+        t1 = a + 1 + q;
+    }
+    for (int b = 0; b < (method == 2 ? w : 2); ++b) {
+        int t;
+        if (method == 2) t = ((pat >> b) & 1u) ? (msb ? w - 1 - b : b) : -1;
+        else t = b == 0 ? t0 : t1;
+        if (t < 0) continue;
+        const int p = fcol[t];
+#pragma unroll
+        for (int x = 0; x < LSD_WPR; ++x) F[x] |= (p >> 6) == x ? 1ull << (p & 63) : 0ull;
+    }
+}
+
+// does the candidate with the free columns F set the bit at column position p?
+__device__ __forceinline__ bool lsd_candidate_bit(int p, const unsigned short* prow, const unsigned long long* rows, const unsigned char* rsy,
+                                                  const unsigned long long F[LSD_WPR]) {
+    const int r = prow[p];
+    if (r == LSD_NONE) {
+        unsigned long long f = 0ull;
+#pragma unroll
+        for (int x = 0; x < LSD_WPR; ++x) f |= (p >> 6) == x ? F[x] : 0ull;
+        return (f >> (p & 63)) & 1ull;
+    }
+    unsigned long long acc = 0ull;
+#pragma unroll
+    for (int x = 0; x < LSD_WPR; ++x) acc ^= rows[r * LSD_WPR + x] & F[x];
+    return ((__popcll(acc) ^ rsy[r]) & 1) != 0;
+}
+
+template <bool HO>
 __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int m = P.m, n = P.n, lane = threadIdx.x, tie = P.tie_policy;
@@ -108,10 +173,15 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
     unsigned short* cc = reinterpret_cast<unsigned short*>(q8);   q8 += 2 * (size_t)LSD_MAXC;   // a cluster's checks
     unsigned char* rsy = q8;                                      q8 += LSD_MAXC;               // syndrome bit of a row
     unsigned char* used = q8;                                     q8 += LSD_MAXC;               // the row is a pivot row
-    int* sh = reinterpret_cast<int*>(q8);
-    int* inv = P.ws + (size_t)blockIdx.x * lsd_ws_ints(m, n);
+    int* sh = reinterpret_cast<int*>(q8);                         q8 += 64;
+    unsigned int* xw = reinterpret_cast<unsigned int*>(q8);       q8 += 8 * (size_t)wpn;        // (HO) the sweep's rows
+    unsigned short* prow = reinterpret_cast<unsigned short*>(q8); q8 += 2 * (size_t)LSD_MAXB;
+    unsigned short* fcol = reinterpret_cast<unsigned short*>(q8); q8 += 2 * (size_t)LSD_MAXB;
+    unsigned short* perm = reinterpret_cast<unsigned short*>(q8);
+    int* inv = P.ws + (size_t)blockIdx.x * lsd_ws_ints(m, n, HO);
     int* sel = inv + m;
     int* jb = sel + m;
+    int* cfree = jb + n;  // (HO)
 
     for (;;) {
         if (lane == 0) sh[0] = atomicAdd(&P.lsd_counters[3], 1);
@@ -124,6 +194,8 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
         for (int c = lane; c < m; c += LSD_NT) uf[c] = LSD_NONE;
         for (int w = lane; w < tw; w += LSD_NT) taken[w] = 0u;
         for (int w = lane; w < 2 * wpn; w += LSD_NT) xsol[w] = 0u;
+        if constexpr (HO)
+            for (int w = lane; w < 2 * wpn; w += LSD_NT) xw[w] = 0u;
         for (int w = lane; w < sw; w += LSD_NT) {
             unsigned int v = 0u;
             for (int b = 0; b < 32 && 32 * w + b < m; ++b) v |= (bp_synd_bit(P.synd, P.packed_io, s, m, 32 * w + b) ? 1u : 0u) << b;
@@ -329,6 +401,8 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
                 bool bad = false;
                 for (int r = lane; r < ncc; r += LSD_NT) bad |= !used[r] && rsy[r];
                 const bool valid = __ballot(bad) == 0ull;
+                bool keep = !valid;
+                int nfree = 0;
                 if (valid) {  // the solution on the greedy column basis replaces whatever its bits held
                     for (int t = lane; t < nb; t += LSD_NT) atomicAnd(&xsol[cbs[t] >> 5], ~(1u << (cbs[t] & 31)));
                     __syncthreads();
@@ -337,7 +411,14 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
                             const int j = cbs[pivcol[r]];
                             atomicOr(&xsol[j >> 5], 1u << (j & 31));
                         }
-                } else {  // the first free bit in column order next to one of its checks
+                    if constexpr (HO) {  // free = bits - pivots; short of free columns and below the growth limit: unfinished
+                        int npiv = 0;
+                        for (int base = 0; base < ncc; base += LSD_NT) npiv += __popcll(__ballot(base + lane < ncc && used[base + lane]));
+                        nfree = nb - npiv;
+                        keep = nfree < P.min_free && nb < P.grow_limit;
+                    }
+                }
+                if (keep) {  // the first free bit in column order next to one of its checks
                     int best = -1;
                     double bl = 0.0;
                     for (int r = lane; r < ncc; r += LSD_NT) {
@@ -350,11 +431,79 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
                         }
                     }
                     best = lsd_wave_first(bl, best, tie);
-                    if (lane == 0) {
-                        inv[nkeep] = R;
-                        sel[nkeep] = best;
+                    if constexpr (HO) keep = !valid || best >= 0;  // a valid cluster with nothing to select is finished
+                    if (keep) {
+                        if (lane == 0) {
+                            inv[nkeep] = R;
+                            sel[nkeep] = best;
+                        }
+                        ++nkeep;
                     }
-                    ++nkeep;
+                }
+                if constexpr (HO) {
+                    if (!keep) {  // finished: the sweep over its reduced rows
+                        __syncthreads();
+                        for (int t = lane; t < nb; t += LSD_NT) prow[t] = LSD_NONE;
+                        __syncthreads();
+                        for (int r = lane; r < ncc; r += LSD_NT)
+                            if (used[r]) prow[pivcol[r]] = (unsigned short)r;
+                        __syncthreads();
+                        int kp = 0;
+                        for (int base = 0; base < nb; base += LSD_NT) {
+                            const int t = base + lane;
+                            const bool f = t < nb && prow[t] == LSD_NONE;
+                            const unsigned long long bal = __ballot(f);
+                            if (f) fcol[kp + lsd_lanes_below(bal, lane)] = (unsigned short)t;
+                            kp += __popcll(bal);
+                        }
+                        if (lane == 0) cfree[R] = kp;
+                        int bc = -1;
+                        const int w = min(P.order, kp);
+                        if (P.method != 0 && kp > 0) {
+                            for (int t = lane; t < nb; t += LSD_NT) {  // ascending bit index by counting; the costs by column position
+                                const int j = cbs[t];
+                                int rk = 0;
+                                for (int u = 0; u < nb; ++u) rk += cbs[u] < j ? 1 : 0;
+                                perm[rk] = (unsigned short)t;
+                                double cj = 1.0;
+                                if (P.cost) {
+                                    cj = P.cost[j];
+                                    if (P.cost_rows) cj = P.cost_rows[(size_t)s * n + j];
+                                    else if (P.sel && P.sel[(size_t)s * n + j] != 0) cj = P.cost_alt[j];
+                                }
+                                ck[t] = cj;
+                            }
+                            __syncthreads();
+                            const int ncand = P.method == 1 ? kp + w * (w - 1) / 2 : (1 << w) - 1;
+                            double bw = 0.0;
+#pragma clang loop unroll(disable)
+                            for (int base = -LSD_NT; base < ncand; base += LSD_NT) {  // (the first pass weighs the baseline, candidate -1)
+                                const int c = base < 0 ? -1 : base + lane;
+                                unsigned long long F[LSD_WPR];
+                                lsd_candidate(c < ncand ? c : -1, P.method, w, kp, P.e_msb_first, fcol, F);
+                                double wgt = 0.0;
+#pragma clang loop unroll(disable)
+                                for (int i = 0; i < nb; ++i) {
+                                    const int p = perm[i];
+                                    if (lsd_candidate_bit(p, prow, rows, rsy, F)) wgt += ck[p];
+                                }
+                                if (base < 0) bw = wgt;
+                                else if (c < ncand && wgt < bw) { bw = wgt; bc = c; }
+                            }
+#pragma unroll
+                            for (int off = 32; off > 0; off >>= 1) {  // the lightest; ties to the lower candidate index
+                                const double ow = __shfl_xor(bw, off);
+                                const int oc = __shfl_xor(bc, off);
+                                if (ow < bw || (ow == bw && oc < bc)) { bw = ow; bc = oc; }
+                            }
+                        }
+                        for (int t = lane; t < nb; t += LSD_NT) atomicAnd(&xw[cbs[t] >> 5], ~(1u << (cbs[t] & 31)));
+                        __syncthreads();
+                        unsigned long long F[LSD_WPR];
+                        lsd_candidate(bc, P.method, w, kp, P.e_msb_first, fcol, F);
+                        for (int t = lane; t < nb; t += LSD_NT)
+                            if (lsd_candidate_bit(t, prow, rows, rsy, F)) atomicOr(&xw[cbs[t] >> 5], 1u << (cbs[t] & 31));
+                    }
                 }
                 __syncthreads();
             }
@@ -371,6 +520,23 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
         }
         // ---- results
         const bool solved = status == 0;
+        if constexpr (HO) {
+            __syncthreads();
+            int maxf = 0;
+            bool diff = false;
+            if (solved) {
+                for (int c = lane; c < m; c += LSD_NT)
+                    if (uf[c] == (unsigned short)c) maxf = max(maxf, cfree[c]);
+                for (int w = lane; w < 2 * wpn; w += LSD_NT) diff |= xw[w] != xsol[w];
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) maxf = max(maxf, __shfl_xor(maxf, off));
+            const bool any_diff = __ballot(diff) != 0ull;
+            if (lane == 0) {
+                P.st_maxfree[s] = maxf;
+                P.st_improved[s] = any_diff ? 1 : 0;
+            }
+        }
         if (lane == 0) {
             P.st_status[s] = status;
             P.st_rounds[s] = rounds;
@@ -392,6 +558,7 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
                     unsigned int v = 0u;
                     for (int b = 0; b < 32 && 32 * w + b < n; ++b) v |= (llr[32 * w + b] <= 0.0 ? 1u : 0u) << b;
                     xsol[w] = v;
+                    if constexpr (HO) xw[w] = v;
                 }
                 __syncthreads();
             }
@@ -399,11 +566,12 @@ __global__ __launch_bounds__(LSD_NT) void lsd_kernel(const LsdParams P) {
             for (int o = 0; o < 4; ++o) {
                 if (!outs[o]) continue;
                 const size_t row = o < 2 ? (size_t)s : (size_t)slot;
+                const unsigned int* const src = (HO && (o & 1) == 0) ? xw : xsol;  // (HO) osdw: the sweep's rows
                 if (P.packed_io) {
                     for (int w = lane; w < wpn; w += LSD_NT)
-                        ((unsigned long long*)outs[o])[row * wpn + w] = (unsigned long long)xsol[2 * w] | ((unsigned long long)xsol[2 * w + 1] << 32);
+                        ((unsigned long long*)outs[o])[row * wpn + w] = (unsigned long long)src[2 * w] | ((unsigned long long)src[2 * w + 1] << 32);
                 } else {
-                    for (int i = lane; i < n; i += LSD_NT) outs[o][row * n + i] = (uint8_t)((xsol[i >> 5] >> (i & 31)) & 1u);
+                    for (int i = lane; i < n; i += LSD_NT) outs[o][row * n + i] = (uint8_t)((src[i >> 5] >> (i & 31)) & 1u);
                 }
             }
         }

@@ -183,6 +183,8 @@ class BpOsdDecoder:
         if relay is not None:
             self.set_relay(relay)
         self._lsd = None
+        from .lsd import LsdConfig
+        self._lsd_order = LsdConfig()  # the order settings the handle holds (they survive switching the mode off)
         if lsd is not None:
             self.set_lsd(lsd)
 
@@ -236,20 +238,29 @@ class BpOsdDecoder:
         decoder -- and of the engines built on it -- runs ``lsd_kernel`` over the shots BP leaves open and the OSD stage only
         over the shots LSD does not solve (``bposd_set_lsd``).  Not together with relay mode.  Off, the decoder launches
         what it launched before."""
-        from .lsd import LsdConfig
+        from .lsd import LSD_METHODS, LsdConfig
         if cfg is None:
             _lib.check(self._lib, self._h, self._lib.bposd_set_lsd(self._h, 0, 0, 0))
             self._lsd = None
             return
         if not isinstance(cfg, LsdConfig):
             raise TypeError("lsd must be an LsdConfig or None")
-        _lib.check(self._lib, self._h, self._lib.bposd_set_lsd(self._h, 1, cfg.max_cluster_bits, cfg.max_cluster_checks))
-        self._lsd = cfg
+        order = lambda c: (LSD_METHODS.index(c.method), c.order, c.min_free_bits, c.grow_bits_limit)
+        before = order(self._lsd_order)
+        # the order first: bposd_set_lsd checks the LDS of the kernel instance in force
+        _lib.check(self._lib, self._h, self._lib.bposd_set_lsd_order(self._h, *order(cfg)))
+        try:
+            _lib.check(self._lib, self._h, self._lib.bposd_set_lsd(self._h, 1, cfg.max_cluster_bits, cfg.max_cluster_checks))
+        except Exception:  # refused: the handle as it was
+            self._lib.bposd_set_lsd_order(self._h, *before)
+            raise
+        self._lsd = self._lsd_order = cfg
 
     def lsd_stats(self, lane=None):
-        """dict(status, rounds, clusters, max_bits: int32 [B]) of the last call that ran on ``lane`` (default: the lane of the
+        """dict(status, rounds, clusters, max_bits, max_free, improved: int32 [B]) of the last call that ran on ``lane`` (default: the lane of the
         last LSD launch) in LSD mode: per shot 0 solved, 1 a cluster outgrew a cap, 2 no bit left to select, -1 BP converged;
-        the rounds in which bits joined; the clusters and the most bits in one when the shot ended.  Waits for that lane.  A
+        the rounds in which bits joined; the clusters and the most bits in one when the shot ended; the most free columns in
+        one final cluster and whether the sweep changed the row (zeros without a sweep or growth).  Waits for that lane.  A
         host-pointer call that was cut into several chunks leaves each lane the words of its last chunk only."""
         lane = -1 if lane is None else int(lane)  # (-1: the lane of the last LSD launch)
         B = self._lib.bposd_lsd_stats(self._h, lane, None, None, None, None, 0)  # (no arrays: that call's batch size)
@@ -258,7 +269,18 @@ class BpOsdDecoder:
         out = {k: np.empty(B, np.int32) for k in ("status", "rounds", "clusters", "max_bits")}
         if B:
             _lib.check(self._lib, self._h, self._lib.bposd_lsd_stats(self._h, lane, *(v.ctypes.data for v in out.values()), B))
+        more = {k: np.zeros(B, np.int32) for k in ("max_free", "improved")}
+        if B:
+            _lib.check(self._lib, self._h, self._lib.bposd_lsd_order_stats(self._h, lane, *(v.ctypes.data for v in more.values()), B))
+        out.update(more)
         return out
+
+    def lsd_launches(self):
+        """(launches of the LSD-0 instance of ``lsd_kernel``, launches of the instance with a sweep or growth for free bits)
+        of this decoder so far (``bposd_debug_lsd_launches``)."""
+        k = np.zeros(2, np.int64)
+        _lib.check(self._lib, self._h, self._lib.bposd_debug_lsd_launches(self._h, k.ctypes.data))
+        return int(k[0]), int(k[1])
 
     # ------------------------------------------------------------------ lifetime
     def __del__(self):
@@ -577,7 +599,8 @@ class BpOsdDecoder:
         [B, n]) with ``alt_channel_probs`` (host array of n floats) is the per-shot two-valued channel of
         :meth:`decode_batch`.  ``d_prior_llr_rows`` / ``d_cost_rows`` (device float64 [B, n], the two arrays of
         :meth:`channel_tables`) give every shot a channel of its own; ``d_cost_rows`` may be None where OSD does not weigh
-        candidates with the channel (``osd_off``, ``osd_0``, order 0, ``weight_fn=1``).  The rows stay the caller's and
+        candidates with the channel (``osd_off``, ``osd_0``, order 0, ``weight_fn=1``) and no LSD sweep is set
+        (``LsdConfig(method="lsd_cs" | "lsd_e")`` weighs with the shot's row whatever the OSD method).  The rows stay the caller's and
         unchanged until :meth:`synchronize`."""
         self._timing_override = None
         if d_prior_llr_rows is not None:

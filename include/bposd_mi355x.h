@@ -206,7 +206,8 @@ int bposd_decode_batch_rows(bposd_handle *h, const uint8_t *syndromes, int64_t B
                             uint8_t *osdw, uint8_t *osd0, uint8_t *bp, uint8_t *converged, int32_t *iters, double *llr);
 
 /* Device-pointer form: d_prior_llr_rows and d_cost_rows are [B, n] doubles on the device as bposd_channel_tables makes them
- * (d_cost_rows may be NULL where the OSD stage does not weigh candidates, see above; it is required otherwise).  The caller
+ * (d_cost_rows may be NULL where the OSD stage does not weigh candidates, see above, and no sweep of LSD mode is set -- a
+ * handle with LSD mode on and BPOSD_LSD_CS / _E weighs with the shot's row whatever the OSD method; it is required otherwise).  The caller
  * owns the rows and keeps them unchanged until the call's lane is synchronised.  Asynchronous like bposd_decode_batch_device. */
 int bposd_decode_batch_rows_device(bposd_handle *h, const uint8_t *d_syndromes, int64_t B, const double *d_prior_llr_rows,
                                    const double *d_cost_rows, uint8_t *d_osdw, uint8_t *d_osd0, uint8_t *d_bp,
@@ -380,7 +381,7 @@ int bposd_set_relay(bposd_handle *h, int32_t legs, const double *gammas, const i
 int bposd_relay_stats(bposd_handle *h, int32_t lane, int32_t *solutions, int32_t *best_leg, int64_t *weight, int64_t B);
 
 /*
- * BP+LSD (localized statistics decoding of order 0, Hillmann et al., 2024): a mode of the handle.  With it on, every decode
+ * BP+LSD (localized statistics decoding, Hillmann et al., 2024): a mode of the handle.  With it on, every decode
  * call (host, device and packed pointers, per-shot channels, observables, the DEM engine) runs lsd_kernel over the list of
  * shots BP left open, in front of the OSD kernel, which then decodes only the shots LSD did not solve.  Per listed shot,
  * with l its posterior LLRs as the OSD stage would get them:
@@ -399,7 +400,32 @@ int bposd_relay_stats(bposd_handle *h, int32_t lane, int32_t *solutions, int32_t
  *   osd_method off they keep BP's decisions.  rounds = rounds in which bits joined, clusters and max_bits = the number of
  *   clusters and the most bits in one of them when the shot ended.  Shots BP converged on: status -1, zeros.
  * The OSD stage's rows of the shots it decodes are those of a handle without the mode.  It is this project's synchronous
- * definition, not upstream ldpc's BpLsdDecoder, whose sequential growth order differs; higher LSD orders are not offered.
+ * definition, not upstream ldpc's BpLsdDecoder, whose sequential growth order differs.
+ *
+ * Higher orders and growth for free bits (bposd_set_lsd_order; with its defaults -- BPOSD_LSD_0, order 0, min_free_bits 0,
+ * grow_bits_limit 256 -- the definition is the one above).  Everything not named here stays as above.
+ *   free = |V| - rank H[C, V]; the free columns of a cluster are the columns of V, in the order above, that are not in
+ *   the greedy column basis.  A bit joins with all its checks, so growth and merges never lower free.
+ *   A cluster is unfinished at the start of a round if it is invalid, or if it is valid, free < min_free_bits and
+ *   |V| < grow_bits_limit.  Every unfinished cluster selects as invalid clusters do above.  An invalid cluster with nothing
+ *   to select ends the shot with status 2; a valid unfinished cluster with nothing to select is finished and stays so
+ *   until it changes through a merge.  Rounds repeat while some cluster selects.  The caps work as above: growth for free
+ *   bits alone adds one bit at a time and stops at grow_bits_limit, but merges, and the checks joining bits bring, can
+ *   still overflow a cap (status 1).
+ *   On a solved shot the osd0 row is, per final cluster, the solution on the greedy column basis (the row above, on the
+ *   possibly larger clusters); the osdw row is, per final cluster, the lightest candidate of a sweep over the cluster's
+ *   reduced system.  With kp free columns and w' = min(order, kp), the baseline is the osd0 solution; BPOSD_LSD_CS tries
+ *   the kp single free columns in column order, then the pairs (a < b < w') with a outer and b inner; BPOSD_LSD_E tries
+ *   the patterns 1 .. 2^w' - 1, bit b of a pattern standing for free column b (for free column w' - 1 - b if the handle's
+ *   osd_e_bit_order is 1).  A candidate sets the free columns of its pattern to 1, every other free column to 0, and
+ *   solves the basis bits from the reduced rows.  Its weight is the OSD stage's weight for that shot restricted to V: the
+ *   number of set bits where the OSD kernels count bits (a uniform channel 0 < p < 1, or weight_fn = 1), otherwise the
+ *   fp64 sum, started at 0.0, of log(1/p_j) over the set bits of V in ascending bit index, p being the channel the OSD
+ *   kernel would use for that shot (the handle's, the two-valued per-shot choice, or the shot's own row).  A strictly
+ *   lighter candidate replaces the best, so the first one found wins ties (oracle/bposd_oracle.c:488-523 inside a
+ *   cluster): a cluster that holds every bit of the matrix gives the osd_cs / osd_e rows.
+ *   Two more words per listed shot: max_free = the most free columns in one final cluster, improved = 1 iff the osdw row
+ *   differs from the osd0 row; both are 0 unless status is 0.
  *
  * bposd_set_lsd(on = 0) switches the mode off: the handle launches what it did before and allocates nothing more for the
  * mode; what the mode has allocated (H by column, each lane's second list with its LLR rows, the four words per shot) stays
@@ -412,10 +438,23 @@ int bposd_relay_stats(bposd_handle *h, int32_t lane, int32_t *solutions, int32_t
  *
  * bposd_lsd_stats: as bposd_relay_stats, for the four words per shot of the last call that ran on `lane` (-1: the lane of
  * the last LSD launch); any array may be NULL, all NULL returns that call's batch size.
+ *
+ * bposd_set_lsd_order holds method (BPOSD_LSD_0 / _CS / _E), order (0 with BPOSD_LSD_0; 1..64 with _CS; 1..10 with _E),
+ * min_free_bits (0..64) and grow_bits_limit (1..256) on the handle; they take effect while LSD mode is on, in the calls
+ * that follow, and survive switching the mode off and on.  A fresh handle has the defaults.  A sweep or min_free_bits > 0
+ * selects the second instance of lsd_kernel, which holds a second row bitmap and the sweep's tables in LDS (1 bit per bit
+ * and 1 536 bytes more) and six words per shot; otherwise the LSD-0 instance runs as before.  BPOSD_ERR_INVALID (handle
+ * unchanged) names the value out of range; BPOSD_ERR_UNSUPPORTED (handle unchanged) if the mode is on and the second
+ * instance's state does not fit one CU's LDS.  bposd_set_lsd checks the LDS of the instance in force.
+ *
+ * bposd_lsd_order_stats: as bposd_lsd_stats, for max_free and improved; zeros after a call of the LSD-0 instance.
  */
+enum { BPOSD_LSD_0 = 0, BPOSD_LSD_CS = 1, BPOSD_LSD_E = 2 };
 int bposd_set_lsd(bposd_handle *h, int32_t on, int32_t max_cluster_bits, int32_t max_cluster_checks);
 int bposd_lsd_stats(bposd_handle *h, int32_t lane, int32_t *status, int32_t *rounds, int32_t *clusters, int32_t *max_bits,
                     int64_t B);
+int bposd_set_lsd_order(bposd_handle *h, int32_t method, int32_t order, int32_t min_free_bits, int32_t grow_bits_limit);
+int bposd_lsd_order_stats(bposd_handle *h, int32_t lane, int32_t *max_free, int32_t *improved, int64_t B);
 
 /*
  * Monte-Carlo engine: the device-resident form of the reference's harness loop

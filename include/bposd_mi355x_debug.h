@@ -93,6 +93,10 @@ int bposd_debug_set_park(bposd_handle *h, int32_t mode);
  * lane; valid until the lane's next call. */
 int bposd_debug_last_parked(bposd_handle *h, int32_t lane, int32_t *parked);
 
+/* Diagnostics: how often the handle has launched lsd_kernel<false> (launches[0], LSD-0) and lsd_kernel<true> (launches[1],
+ * a sweep or growth for free bits). */
+int bposd_debug_lsd_launches(bposd_handle *h, int64_t launches[2]);
+
 /* Diagnostics: duration of obs_kernel in the last observables call queued on `lane` (HIP events on the lane's stream; waits
  * for that lane), or, lane = -1, summed over the chunks of the last synchronous host-pointer observables call.  obs_kernel
  * runs behind the events of bposd_last_timing / bposd_lane_timing: their bp_ms and osd_ms do not include it. */
