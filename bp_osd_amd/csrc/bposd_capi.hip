@@ -590,6 +590,7 @@ int bposd_create(const bposd_config* cfg, const int32_t* indptr, const int32_t* 
         for (Event* e : {&l.ev_bp, &l.ev_osd, &l.ev_park, &l.ev_done, &l.ev_up, &l.ev_copy}) CREATE_HIP(hipEventCreateWithFlags(&e->raw, hipEventDisableTiming));
         CREATE_HIP(hipStreamCreateWithFlags(&l.copy_stream.raw, hipStreamNonBlocking));
         CREATE_HIP(l.d_counters.alloc(bposd_local_park::kCounterBytes));  // 4 counters + the 64-bit iteration total (one copy) + the park words: one memset
+        CREATE_HIP(hipMemset(l.d_counters, 0, bposd_local_park::kCounterBytes));  // (bposd_debug_last_parked of a lane no call has run on reads 0, not what the allocation held)
         CREATE_HIP(l.h_tail.alloc(64, hipHostMallocMapped));
         *l.h_tail.as<int>() = 0;
     }
